@@ -1,19 +1,24 @@
 """bench.py -- denoising-sampler throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one DDPM reverse step (p_sample: denoiser forward + x0-inpainting + [gated correction] + posterior update with
 in-kernel noise) over one batch of B=16 BEHAVE-shaped synthetic clips of T=100 frames per GPU (BASELINE config #2:
 eval_smpl_short.py, B=16, T=100, 1000-step DDPM, correction mode).
 
-The timed region is ALWAYS made of whole samples: max(3, ceil(K / 1000)) complete 1000-step samples, each with its 989 plain steps, its
-11 gated correction steps (t in {500,450,..,0}: SMPL-H FK + LBS, normals, signed nearest neighbours, contact-frame predictor) and
-the once-per-sample memory folding -- whatever --steps says, so that the headline is the rate of the workload eval_smpl_short.py runs,
-never a window of plain steps.  Every sample is clocked on its own (barrier + synchronize on both sides, max over ranks); `value` is
-computed from the MEDIAN sample, min / max / all travel in `ms_per_step_samples`.  `steps` in the JSON line is the number of steps
-really timed, `steps_requested` echoes --steps.  Inputs are resident in HBM before the clock starts.
+The timed region is exactly K steps: the first K steps of 1000-step samples run back to back, i.e. K // 1000 whole samples and then the
+first K % 1000 steps (t = 999 downwards) of one more.  A whole sample holds its 989 plain steps, its 11 gated correction steps
+(t in {500,450,..,0}: SMPL-H FK + LBS, normals, signed nearest neighbours, contact-frame predictor) and the once-per-sample memory
+folding; a partial sample holds the correction steps its timesteps reach (none for K % 1000 < 500), so only K >= 1000 gives the rate of
+the workload eval_smpl_short.py runs.  Every sample (whole or partial) is clocked on its own (barrier + synchronize on both sides, max
+over ranks); its ms per step travel in `ms_per_step_samples`.  `steps` in the JSON line is K.  Inputs are resident in HBM and every
+hipGraph the region replays is captured before the clock starts.
 
-value = frame-steps/s = 1000 * B_total * T / (median seconds per sample)  (whole job, all ranks; weak scaling: B=16 per GPU).
+value = frame-steps/s = K * B_total * T / (sum of the sample times)  (whole job, all ranks; weak scaling: B=16 per GPU).
+
+`--dump-outputs DIR`: after the timed region every rank writes the sample its last timed p_sample_loop call returned (the array a
+caller of the path receives) as DIR/sample_rank<r>.npy, float32; at most 64 MB in all (beyond that, a fixed seeded subset of the
+clips).  Inputs, weights and noise seeds are fixed, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself as N ranks (torch.distributed.run, one per GPU).
 After the timed region every rank scores its clips and the six per-clip metric vectors are collated with the path's one collective
@@ -325,6 +330,18 @@ def self_spawn(args):
     return subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0')))
 
 
+def dump_outputs(out_dir, sample, rank, world, budget=64 << 20):
+    """`sample` (what p_sample_loop returned) -> out_dir/sample_rank<rank>.npy as float32.  The ranks share `budget` bytes; a larger
+    output is cut to a fixed, seeded subset of its clips (axis 0, kept in order)."""
+    a = sample.detach().float().cpu().numpy()
+    per_clip = a[0].nbytes
+    keep = max(1, (budget // world) // per_clip)
+    if a.shape[0] > keep:
+        a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'sample_rank%d.npy' % rank), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def timed_samples(diff, model, corr, bt, y, n, seed0=233):
     """n complete 1000-step samples back to back on the current stream; returns (wall seconds, last sample)."""
     torch.cuda.synchronize()
@@ -369,6 +386,8 @@ def main():
     ap.add_argument('--no-extra-configs', action='store_true', help='skip the no_correction / B=32 / plain-window legs')
     ap.add_argument('--clips-per-gpu', type=int, default=B_PER_GPU,
                     help='NOT the BASELINE configuration unless 16: batch-scaling experiments only (DESIGN.md §4.1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s output sample to DIR/sample_rank<r>.npy (float32, <= 64 MB in all)')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_spawn(args))
@@ -392,8 +411,11 @@ def main():
         raise SystemExit('bench.py: --gpus %d but WORLD_SIZE=%d' % (args.gpus, world))
     dev = torch.device('cuda', local)
     torch.cuda.set_device(dev)
-    K = max(1, args.steps)
-    n_samples = max(3, (K + STEPS - 1) // STEPS)      # whole samples only (the headline always contains the correction path), at least three for a spread
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be >= 1')
+    K = args.steps
+    segments = [STEPS] * (K // STEPS) + ([K % STEPS] if K % STEPS else [])      # steps per timed sample: whole samples, then a partial one
+    n_samples = len(segments)
     log('building world (weights, SMPL-H stand-in, clips) on %s' % dev)
     model, corr, bt, y, assets = build_world(dev, rank)
     log('world ready')
@@ -402,25 +424,34 @@ def main():
     # untimed warm-up: W plain steps + one correction call (first-use allocations, code objects)
     run_steps(diff, model, corr, bt, y, max(1, args.warmup), seed=7)
     run_steps(diff, model, corr, bt, y, 57, seed=7)        # setup, not a step count: captures every hipGraph block size (49+7+1)
+    run_steps(diff, model, corr, bt, y, 50, seed=7, first_t=549)     # setup: captures 49 plain steps + a correction step as one graph (t = 549..500)
     corr.apply(bt['noise'].clone(), 500, y)
     route_ok = route_check(diff, model, corr, bt, y)          # untimed: the route about to be timed == the eager route, 60 steps across t = 500, bit for bit
     torch.cuda.synchronize()
     log('warm-up done')
 
     # the once-per-sample memory folding runs inside the clock (p_sample_loop folds `cond` at the start of every sample).  Every sample is its
-    # own timed region: barrier + synchronize on both sides, MAX over ranks; the headline is the MEDIAN sample
+    # own timed region: barrier + synchronize on both sides, MAX over ranks; the headline is the K steps over the sum of the samples
     sample_s, sample_ranks = [], []
-    for s_i in range(n_samples):
+    for s_i, n_i in enumerate(segments):
         idist.barrier()
-        wall_local, out = timed_samples(diff, model, corr, bt, y, 1, seed0=233 + s_i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = run_steps(diff, model, corr, bt, y, n_i, seed=233 + s_i)
+        torch.cuda.synchronize()
+        wall_local = time.perf_counter() - t0
         idist.barrier()
         sample_s.append(idist.max_over_ranks(wall_local, dev))
         sample_ranks.append(idist.gather_scalar(wall_local, dev))       # every rank's own clock around the same region: a straggler shows
     assert torch.isfinite(out).all()
-    wall = sorted(sample_s)[len(sample_s) // 2]                        # median sample (n odd by default: 3)
-    wall_ranks = sample_ranks[sample_s.index(wall)]
-    n_timed = n_samples * STEPS
-    log('timed region: %d whole samples of %d steps (incl. %d correction steps each): %s s; median %.4f' % (n_samples, STEPS, 11, ['%.4f' % w for w in sample_s], wall))
+    wall = sum(sample_s)
+    wall_ranks = [sum(w_) for w_ in zip(*sample_ranks)]
+    n_timed = K
+    n_corr = sum(sum(1 for t_ in range(STEPS - 1, STEPS - 1 - n_i, -1) if corr.is_active(t_)) for n_i in segments)
+    log('timed region: %d steps in %d sample(s) of %s steps (%d correction steps): %s s; total %.4f' % (K, n_samples, segments, n_corr, ['%.4f' % w for w in sample_s], wall))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+        log('outputs of the last timed step written to %s' % args.dump_outputs)
 
     # ---- eval leg, all ranks: every rank scores its clips, ONE all-gather (RCCL over xGMI) collates the six per-clip metric vectors
     from interdiff_amd import eval as ev
@@ -550,23 +581,23 @@ def main():
     log('cpu baseline done' if cpu else 'cpu baseline skipped')
     Btot = B_PER_GPU * world
     split = getattr(model, 'ffn_math', 'exact') == 'split'
-    line = dict(metric='denoising frame-steps/sec (denoising-steps/sec x B x T frames)', value=STEPS * Btot * T / wall,
-                unit='frame-steps/s', n_gpus=world, steps=n_timed, steps_requested=K, warmup=args.warmup, ms_per_step=1e3 * wall / STEPS,
+    line = dict(metric='denoising frame-steps/sec (denoising-steps/sec x B x T frames)', value=n_timed * Btot * T / wall,
+                unit='frame-steps/s', n_gpus=world, steps=n_timed, steps_requested=K, warmup=args.warmup, ms_per_step=1e3 * wall / n_timed,
                 higher_is_better=True, scaling='weak', vs_baseline=None,
                 dtype='f32 (every contraction of the denoiser -- feed-forward block, QKV projection, self-attention, row-block contractions and the two token GEMMs: every fp32 operand as two f16 planes, 3 f16 MFMAs per product, fp32 accumulate; SMPL and everything else fp32 MFMA / VALU)' if split else 'f32',
-                data='synthetic', steps_per_sec=STEPS / wall,
-                ms_per_step_samples=dict(median=1e3 * wall / STEPS, min=1e3 * min(sample_s) / STEPS, max=1e3 * max(sample_s) / STEPS,
-                                         all=[round(1e3 * w_ / STEPS, 5) for w_ in sample_s], n=n_samples,
-                                         note='every whole 1000-step sample clocked on its own (barrier + synchronize both sides, max over ranks); value = from the median'),
-                steps_note='--steps is advisory: the timed region is always max(3, ceil(steps / 1000)) WHOLE 1000-step samples (989 plain + 11 corrected steps each)',
-                ms_per_step_by_rank=dict(min=1e3 * min(wall_ranks) / STEPS, max=1e3 * max(wall_ranks) / STEPS,
-                                         all=[round(1e3 * w_ / STEPS, 5) for w_ in wall_ranks], of='the median sample'),
+                data='synthetic', steps_per_sec=n_timed / wall,
+                ms_per_step_samples=dict(min=1e3 * min(w_ / n_ for w_, n_ in zip(sample_s, segments)), max=1e3 * max(w_ / n_ for w_, n_ in zip(sample_s, segments)),
+                                         all=[round(1e3 * w_ / n_, 5) for w_, n_ in zip(sample_s, segments)], steps_each=segments, n=n_samples,
+                                         note='every sample (whole, or the first steps of one) clocked on its own (barrier + synchronize both sides, max over ranks); value = all steps over the summed times'),
+                steps_note='--steps K times exactly K steps: K // 1000 whole 1000-step samples, then the first K % 1000 steps (t = 999 downwards) of one more',
+                ms_per_step_by_rank=dict(min=1e3 * min(wall_ranks) / n_timed, max=1e3 * max(wall_ranks) / n_timed,
+                                         all=[round(1e3 * w_ / n_timed, 5) for w_ in wall_ranks], of='the whole timed region'),
                 timed_route_equals_eager_route=dict(ok=route_ok, how='60 steps from t = 520 (corrected step t = 500 inside), graph route vs eager route fed the same Philox stream, torch.equal'),
                 config=dict(workload='eval_smpl_short.py correction mode: BEHAVE-shaped SMPL-H clips, B=%d per GPU, T=%d '
                                      '(10 past + 90 future), C=144, 1000-step cosine DDPM, 2048 object points, real '
                                      'ObjProjector checkpoint, synthetic denoiser/SMPL-H weights' % (B_PER_GPU, T),
-                            global_batch=Btot, seq_len=T, samples_in_region=n_samples, correction_steps_in_region=11 * n_samples,
-                            plain_steps_in_region=989 * n_samples, timesteps='%d whole sample(s): t = 999..0' % n_samples,
+                            global_batch=Btot, seq_len=T, samples_in_region=n_samples, correction_steps_in_region=n_corr,
+                            plain_steps_in_region=n_timed - n_corr, timesteps='%d whole sample(s): t = 999..0' % (K // STEPS) + ('' if K % STEPS == 0 else ', then t = 999..%d' % (STEPS - K % STEPS)),
                             parallelism='clips sharded x%d' % world, ffn_math=getattr(model, 'ffn_math', 'exact')))
     line['eval_collation'] = dict(collective='ONE all_gather of [7, B_local] fp32 (count header + six metric rows), %d rank(s)' % world,
                                   backend=coll.get('backend'), rccl_version=coll.get('rccl_version'), single_rank_all_gather=coll.get('single_rank_all_gather'), note_rccl=coll.get('note'),
@@ -652,7 +683,7 @@ def main():
                                     frac=ach / PEAK_F32_MFMA_TFLOPS, traffic=None, us_per_launch=us, us_per_launch_best=dom_best, algorithmic_flop_per_launch=flops,
                                     note='exact-fp32 arithmetic selected (INTERDIFF_FFN_MATH=exact): v_mfma_f32_16x16x4_f32, priced against the fp32-input MFMA peak')
         # the whole step against the chip: what the matrix pipes and the memory system would need for one step's algorithmic work, next to what a step takes
-        step_us = 1e6 * wall / STEPS
+        step_us = 1e6 * wall / n_timed
         alg_flop = FLOP_PER_TOKEN * rows
         exe_flop = EXECUTED_FLOP_PER_TOKEN(T) * rows
         matrix_roof = PEAK_F16_MFMA_TFLOPS / 3 if split else PEAK_F32_MFMA_TFLOPS
@@ -671,7 +702,7 @@ def main():
                                   '(tools/dma_ceiling.hip: 12 B/clk/CU x 256 CUs x 2.4 GHz)'),
             frac=max(mat_us, mem_us) / step_us,
             gap_note='a step takes %.1fx its binding roof: 21 strictly dependent launches (~1.7 us boundary each), each a fetch -> compute -> store latency chain on <= 250 workgroups, plus the '
-                     'amortised hook (11 corrected steps per 1000); DESIGN.md 4' % (step_us / max(mat_us, mem_us)))
+                     'amortised hook (%d corrected of the %d timed steps); DESIGN.md 4' % (step_us / max(mat_us, mem_us), n_corr, n_timed))
         line['arithmetic_by_layer'] = model.arithmetic_report() if hasattr(model, 'arithmetic_report') else None
         try:
             txt, bad = _lib.exclusive_cu_report()
