@@ -163,9 +163,10 @@ typedef struct {
     /* encoder side ("next" row, MDM._get_embeddings): [std, QaN x6, std] without cross-attention; uses sa_*, qc, wk,
      * ff*, ln_w/ln_b[0..1] (= norm1, norm2); valid when has_encoder != 0 */
     idf_mdm_layer enc_layer[IDF_MDM_LAYERS];
-    /* tile-configuration overrides for A/B measurements (tools/kbench.py), indexed by IDF_TUNE_*; all zero = the shipped
-     * configuration.  A field of the handle, not process state: two models in one process never see each other's overrides.
-     * One entry is NOT only for A/B runs -- tune[IDF_TUNE_FFN], the row tile of the fused feed-forward block: 0 = by the rows of
+    /* per-handle kernel selection, indexed by IDF_TUNE_*; all zero = exact fp32 arithmetic with the row tile picked per launch.  A field of the
+     * handle, not process state: two models in one process never see each other's selection.  Two entries are meaningful; the other six are
+     * reserved and must be zero (interdiff_mdm_forward*, interdiff_mdm_encode and interdiff_mdm_ffn return IDF_E_INVAL otherwise).
+     * tune[IDF_TUNE_FFN], the row tile of the fused feed-forward block: 0 = by the rows of
      * the launch (16-row tiles up to 800 rows, 64-row tiles from 2800 rows on, 32-row tiles
      * otherwise: csrc/ffn.h ffn_tile_for_rows), 1 = 32-row tiles, 2 = 16-row tiles, 3 = 64-row tiles.  The 32-row kernel agrees with
      * the other two to rounding (7e-7 of the output scale), not bit for bit: a caller that steps ONE batch as several calls on row subsets (the
@@ -175,7 +176,7 @@ typedef struct {
      * 1 = split-f16 (every fp32 operand as two f16 planes, three v_mfma_f32_16x16x32_f16 per product, fp32 accumulate: fp32-grade
      * results at 1/43 of the matrix-pipe time, csrc/ffn_h2.h) for every layer whose ffn_pack_h2 is set, exact fp32 for the others.  Its
      * 16-, 32- and 64-row tiles are bit-identical, so with 1 the row tile is a pure performance choice.  2 = like 1 for the feed-forward block and the QKV
-     * projection, exact fp32 in the row block (A/B runs). */
+     * projection, exact fp32 in the row block. */
     int32_t tune[8];
     /* split-f16 plane fragments of the two token GEMMs at the ends of a step (csrc/tail_h2.h; mdm.py pack_tail_h2), 0 = not packed (token width != 144
      * or a value outside the f16 range): out_w as [9 output tiles][8 K steps][2 planes][64 lanes][8 halves], in_w as [16][5][2][64][8] (K = 144 padded to 160) */
@@ -510,10 +511,10 @@ enum {
 int interdiff_profile_begin(int32_t capacity);
 int interdiff_profile_end(double *ms_per_kind, int64_t *count_per_kind);
 
-/* indices into idf_mdm_weights.tune (value 0 = the shipped default) */
+/* indices into idf_mdm_weights.tune; indices 0-2 and 5-7 are reserved and must be zero (they held the retired A/B overrides
+ * IDF_TUNE_GEMM_EMBED / _QKV / _OUTPROJ / _HEADS, IDF_TUNE_CONTACT and IDF_TUNE_MISC) */
 enum {
-    IDF_TUNE_GEMM_EMBED = 0, IDF_TUNE_GEMM_QKV, IDF_TUNE_GEMM_OUTPROJ, IDF_TUNE_FFN, IDF_TUNE_FFN_MATH,
-    IDF_TUNE_GEMM_HEADS, IDF_TUNE_CONTACT, IDF_TUNE_MISC, IDF_TUNE_COUNT
+    IDF_TUNE_FFN = 3, IDF_TUNE_FFN_MATH = 4, IDF_TUNE_COUNT = 8
 };
 
 #ifdef __cplusplus

@@ -16,7 +16,7 @@ vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_ui
 MDM_LAYERS = 8
 FFN_SLICES = 5              # IDF_FFN_SLICES: partial output slabs of the fused feed-forward kernel
 STEP_EMBED_READY, STEP_EMBED_NEXT = 1, 2          # flags of interdiff_mdm_forward_step_ex (IDF_STEP_*)
-TUNE = dict(embed=0, qkv=1, outproj=2, ffn=3, ffn_math=4, heads=5, contact=6, misc=7)      # indices into MdmWeights.tune (IDF_TUNE_*)
+TUNE = dict(ffn=3, ffn_math=4)      # indices into MdmWeights.tune (IDF_TUNE_*); the other six entries are reserved and must stay zero
 
 
 class SmplModel(C.Structure):

@@ -1,4 +1,4 @@
-// THE DEFAULT self-attention of the split arithmetic since round 5 (tune[IDF_TUNE_MISC] = 6 selects the fp32 kernel of denoiser.hip instead).  Round 4 built it and
+// THE DEFAULT self-attention of the split arithmetic since round 5 (the fp32 kernel of denoiser.hip is its fallback).  Round 4 built it and
 // left it off the route: owning the CU costs the overlap of two co-resident workgroups, and with V staged as fp32 and transposed through LDS it was 1.5 % slower over whole
 // samples (profiles/r04_attn_split_f16_ab.txt).  With V kept row-major and read by ds_read_b64_tr_b16 -- no staging, no transposition, two barriers fewer: 17.4 k -> 15.2 k
 // cycles per workgroup -- it is 1.2 % FASTER than the fp32 kernel (profiles/r05_attn_split_f16_ab.txt); a denoiser forward is 3.2e-7 from the fp64 answer with it, 4.6e-7 without.

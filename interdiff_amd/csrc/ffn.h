@@ -58,7 +58,7 @@ __device__ __forceinline__ float4 ldsv4(const float *p) { return *reinterpret_ca
 // Workgroup -> (M tile, slice): M-tile-major over XCD-AFFINE logical ids (round 4).  Workgroup id runs on XCD id % 8, each with its own L2;
 // giving one XCD consecutive logical ids puts ALL slices of an M tile on one XCD, so the tile's input rows (x2: 32 KiB; for the QKV
 // kernel 32 rows x up to five slabs = 160 KiB) cross the fabric once instead of once per slice, and the tile's output slabs are written
-// from one XCD.  Measured on the split-f16 kernel in one process (tools/ffn_h2_ab.py, profiles/r04_ffn_split_f16_ab.txt): denoiser forward
+// from one XCD.  Measured on the split-f16 kernel in one process (profiles/r04_ffn_split_f16_ab.txt): denoiser forward
 // 212 vs 226-230 us, whole samples 0.2363 vs 0.2437 ms/step against plain ids (where the five slices of a tile land on five XCDs);
 // slice-major affine ids (an XCD streams one or two of the five weight streams instead of all) win a burst of launches and lose in situ.
 __device__ __forceinline__ void xcd_affine_tile(int nwg, int id, int nsl, int &mt, int &sl) {

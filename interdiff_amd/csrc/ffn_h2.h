@@ -163,7 +163,7 @@ __device__ __forceinline__ void idf_sload16(const float *p, f4s &a, f4s &b, f4s 
 // LW = LOADER waves (round 6; 0 or 8): with 8, the workgroup is sixteen waves at 128 registers each (still the whole register file) and the weight ring is fed by waves 8..15 alone --
 // they issue every LDS-DMA piece of a step (three or four each) and own every vmcnt wait -- while waves 0..7 compute exactly as before without ever touching the vector-memory issue:
 // a wave that issues a 1-KiB piece SITS in its issue slot until the CU's request path takes it (60-100 cycles apiece with eight waves asking), which is what a K step cost beyond its
-// 192-384 MFMA cycles (tools/experiments/ffn_h2f.h measured it).  Same instructions per accumulator: same bits.
+// 192-384 MFMA cycles (an experimental kernel of round 6 measured it).  Same instructions per accumulator: same bits.
 template <int TT, int S, int MODE = 0, int LW = 0>
 __global__ __launch_bounds__(NT + 64 * LW) void ffn_h2_kernel(const float *__restrict__ x2, int M, int nwg, const float *__restrict__ pack,
                                                      const float *__restrict__ b1p, const float *__restrict__ b2,
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(NT + 64 * LW) void ffn_h2_kernel(const float *__res
     };
     stamp();
     // Workgroup order.  order 0 (shipped): M-tile-major over XCD-AFFINE logical ids (ffn.h xcd_affine_tile: all five slices of an M tile on one
-    // XCD -- its x2 rows cross the fabric once, its slabs are written from one XCD).  A/B only (tools/ffn_h2_ab.py): order 1 = slice-major
+    // XCD -- its x2 rows cross the fabric once, its slabs are written from one XCD).  Measured and not adopted (the launcher passes 0): order 1 = slice-major
     // affine ids (an XCD streams one or two of the five 432-KiB weight streams: 13 instead of 40 slice loads per launch), order 2 = plain ids
     // (rounds 1-3: the five slices of a tile on five XCDs).  One process (profiles/r04_ffn_split_f16_ab.txt): bursts 10.6 / 10.5 / 12.1 us,
     // denoiser forward 212 / 234-238 / 226-230 us, whole samples with correction 0.2363 / 0.2446 / 0.2437 ms per step for orders 0 / 1 / 2.
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(NT + 64 * LW) void ffn_h2_kernel(const float *__res
     const int xq = nwg >> 3, xr = nwg & 7, xcd = id & 7;
     const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (id >> 3);
     // order 0: ffn.h's M-tile-major ids; 1: slice-major over XCD-affine ids; 2: M-tile-major over XCD-affine ids (an XCD holds ALL slices of its M tiles: x2 rows
-    // cross the fabric once instead of five times, every XCD still streams all five slices)   (A/B: tools/ffn_h2_ab.py)
+    // cross the fabric once instead of five times, every XCD still streams all five slices)
     const int sl = order == 1 ? wg / nmt : (order == 2 ? id % NSL : wg % NSL), mt = order == 1 ? wg - sl * nmt : (order == 2 ? id / NSL : wg / NSL), m0 = mt * BM;
     const float *stream = idf_uniform_ptr(pack + (size_t)sl * SLICE_FLOATS);
     const uint32_t lane16 = lane << 4;
@@ -514,12 +514,9 @@ __global__ __launch_bounds__(NT + 64 * LW) void ffn_h2_kernel(const float *__res
 // Since round 5 the launchers VERIFY the claim (common.h idf_exclusive_cu: occupancy query == 1, LDS == 160 KiB, >= 256 registers allocated) and hand back
 // IDF_NOT_EXCLUSIVE where it does not hold; the caller then runs the fp32 kernel of ffn.h.
 constexpr int LDS_REQUEST = 160 * 1024;
-#ifndef IDF_FFN_H2_SLOTS
-#define IDF_FFN_H2_SLOTS 4
-#endif
-constexpr int FFN_H2_SLOTS = IDF_FFN_H2_SLOTS;            // ring slots of the 16- and 32-row kernels: 4 = planes + ring fill the CU's LDS exactly (3: rounds 4a; -D for A/B)
+constexpr int FFN_H2_SLOTS = 4;            // ring slots of the 16- and 32-row kernels: 4 = planes + ring fill the CU's LDS exactly (3: rounds 4a)
 template <int TT, int S, int LW = 0>
-inline int launch_h2_tt(hipStream_t s, const float *x2, int M, const float *pack, const float *b1p, const float *b2, float *parts, int order) {
+inline int launch_h2_tt(hipStream_t s, const float *x2, int M, const float *pack, const float *b1p, const float *b2, float *parts) {
     constexpr int BM = 16 * TT;
     static_assert(BM * 1024 + S * SLOT <= LDS_REQUEST, "LDS");
     static idf_excl_cache excl;
@@ -527,24 +524,17 @@ inline int launch_h2_tt(hipStream_t s, const float *x2, int M, const float *pack
                                      LW ? (TT == 1 ? "ffn_h2_kernel<16 rows, loader waves>" : (TT == 2 ? "ffn_h2_kernel<32 rows, loader waves>" : "ffn_h2_kernel<64 rows, loader waves>"))
                                         : (TT == 1 ? "ffn_h2_kernel<16 rows>" : (TT == 2 ? "ffn_h2_kernel<32 rows>" : "ffn_h2_kernel<64 rows>")), NT + 64 * LW, excl);
     if (dyn != LDS_REQUEST) return IDF_NOT_EXCLUSIVE;            // (the kernel has no static LDS: its dynamic request IS the CU's 160 KiB)
-    hipLaunchKernelGGL((ffn_h2_kernel<TT, S, 0, LW>), dim3((unsigned)(idf_cdiv(M, BM) * NSL)), dim3(NT + 64 * LW), LDS_REQUEST, s, x2, M, (int)(idf_cdiv(M, BM) * NSL), pack, b1p, b2, parts, order);
+    hipLaunchKernelGGL((ffn_h2_kernel<TT, S, 0, LW>), dim3((unsigned)(idf_cdiv(M, BM) * NSL)), dim3(NT + 64 * LW), LDS_REQUEST, s, x2, M, (int)(idf_cdiv(M, BM) * NSL), pack, b1p, b2, parts, 0);
     return IDF_OK;
 }
 // rows: 16 / 32 / 64 = the M tile (csrc/ffn.h ffn_tile_for_rows picks it from the launch's rows when 0); all three produce the same bits
-// order 3 (A/B only): XCD-affine M-tile-major ids like order 0, with the THREE-slot ring of the round's first builds
-inline int launch_ffn_h2(hipStream_t s, const float *x2, int M, const float *pack, const float *b1p, const float *b2, float *parts, int rows, int order) {
-    if (order == 3) {
-        if (rows == 16) return launch_h2_tt<1, 3>(s, x2, M, pack, b1p, b2, parts, 0);
-        if (rows == 64) return launch_h2_tt<4, 2>(s, x2, M, pack, b1p, b2, parts, 0);
-        return launch_h2_tt<2, 3>(s, x2, M, pack, b1p, b2, parts, 0);
-    }
-    if (rows == 16) return launch_h2_tt<1, FFN_H2_SLOTS>(s, x2, M, pack, b1p, b2, parts, order);
-    if (rows == 64) return launch_h2_tt<4, 2>(s, x2, M, pack, b1p, b2, parts, order);
+inline int launch_ffn_h2(hipStream_t s, const float *x2, int M, const float *pack, const float *b1p, const float *b2, float *parts, int rows) {
+    if (rows == 16) return launch_h2_tt<1, FFN_H2_SLOTS>(s, x2, M, pack, b1p, b2, parts);
+    if (rows == 64) return launch_h2_tt<4, 2>(s, x2, M, pack, b1p, b2, parts);
     // 32 rows: sixteen waves, eight of them loaders (round 6: -5.5 % per launch back to back, 10.5 -> 9.9 us: shorter prologue, 16 waves on the slab stores, the GELU phase with the ring kept full;
     // the K steps themselves do not move: they run at the ~45 B/clk a CU gets from its XCD's L2 -- profiles/r06_ffn_loader_waves.txt).  The 16-row tile gains 1 %, the 64-row tile does not fit
-    // 128 registers: both keep eight waves.  order 4 (A/B only, tune[IDF_TUNE_MISC] = 10): the eight-wave form of rounds 4-5.
-    if (order == 4) return launch_h2_tt<2, FFN_H2_SLOTS>(s, x2, M, pack, b1p, b2, parts, 0);
-    return launch_h2_tt<2, FFN_H2_SLOTS, 8>(s, x2, M, pack, b1p, b2, parts, order);
+    // 128 registers: both keep eight waves.
+    return launch_h2_tt<2, FFN_H2_SLOTS, 8>(s, x2, M, pack, b1p, b2, parts);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -569,34 +559,27 @@ constexpr int QBM = 32;
 // fetch planes instead of each splitting K and V again.  The power of two a row is divided by needs no look at the OUTPUT: the kernel already divides every INPUT row by its own
 // 2^e (Sc[row]; |x'| < 1), so |v_c| <= 2^e ||W_c||_1 + |b_c| -- a bound every slice of the launch computes identically from three static L1 norms and three bias maxima per layer
 // (the six floats behind the packed stream: mdm.py qkv_bounds).  scales_out[row][4] = the three 2^(E - 15) the attention multiplies back (q, k, v; written by slice 0).
-// LW = loader waves (round 6; 0 or 8), as in ffn_h2_kernel: with 8 the workgroup is sixteen waves at 128 registers; every wave takes two of the 32 rows through the slab sum / LayerNorm /
-// split prologue (a row is one wave's latency chain: four rows per wave were four chains in a row), waves 8..15 then feed the ring, waves 0..7 multiply, all sixteen store.  Same bits.
-template <int NP, bool PLANES = false, int LW = 0>
-__global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float *__restrict__ A, size_t a_pstride, int M, int nwg, const float *__restrict__ pack,
+template <int NP, bool PLANES = false>
+__global__ __launch_bounds__(NT) void ln_linear_h2_kernel(const float *__restrict__ A, size_t a_pstride, int M, int nwg, const float *__restrict__ pack,
                                                            const float *__restrict__ lnw, const float *__restrict__ lnb, int nsl_grid, int step_B,
                                                            const float *__restrict__ bias, float *__restrict__ C, int ldc, int N,
                                                            float *__restrict__ xn_out, int64_t *__restrict__ step_state,
                                                            int64_t *__restrict__ step_ts, float *__restrict__ planes_out, float *__restrict__ scales_out) {
     // (argument order: the first 14 dwords -- what the weight stream and the row requests need -- arrive preloaded in SGPRs: build.py)
     extern __shared__ __attribute__((aligned(1024))) float smem[];
-    static_assert(LW == 0 || LW == 8, "loader waves");
-    if constexpr (LW == 0) asm volatile("" ::: "v255");            // exclusive CU, like the feed-forward kernel (see launch_h2_tt)
-    else asm volatile("" ::: "v127");
-    constexpr int NTH = NT + 64 * LW, NWT = NTH / 64;
+    asm volatile("" ::: "v255");            // exclusive CU, like the feed-forward kernel (see launch_h2_tt)
     float *Xs = smem, *ring = smem + QBM * 256, *Sc = ring + 3 * (QSTEP / 4), *Sd = Sc + QBM;      // Sc [32]: 2^e of every row; Sd [32][8] (PLANES): the row's q / k / v dividers and their inverses
     const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool loader = LW > 0 && wave >= NW, issues = LW == 0 || loader;
-    const int iw = LW > 0 ? (wave & 7) : wave;          // index among the waves that feed the ring
     int mt, sl;
     idf_ffn::xcd_affine_tile(nwg, blockIdx.x, nsl_grid, mt, sl);
     const int m0 = mt * QBM, n0 = sl * QHS;
     const float *stream = idf_uniform_ptr(pack + (size_t)sl * QSLICE_FLOATS);
-    const uint32_t vsrc = (uint32_t)(iw * 1024) + (uint32_t)(lane << 4);
-    const uint32_t sdst = idf_lds_addr(ring) + (uint32_t)(iw * 1024);
-    const bool low = iw < NW / 2;                         // issuing waves 0..3: a third DMA instruction per step
+    const uint32_t vsrc = (uint32_t)(wave * 1024) + (uint32_t)(lane << 4);
+    const uint32_t sdst = idf_lds_addr(ring) + (uint32_t)(wave * 1024);
+    const bool low = wave < NW / 2;                       // waves 0..3: a third DMA instruction per step
     auto issue_step = [&](int P) {
-        if (P >= 8 || !issues) return;
+        if (P >= 8) return;
         const uint32_t so = (uint32_t)(P * QSTEP), dof = (uint32_t)((P % 3) * QSTEP);
         idf_dma16_s(stream, vsrc + so, sdst + dof);
         idf_dma16_s(stream, vsrc + so + 8192u, sdst + dof + 8192u);
@@ -617,14 +600,14 @@ __global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float 
     {   // rows: slab sum, LayerNorm (null lnw: layer 0 takes the embedding as it is), residual copy, row scale, split into the plane image
         const float4 gw = lnw ? *reinterpret_cast<const float4 *>(lnw + lane * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
         const float4 gb = lnw ? *reinterpret_cast<const float4 *>(lnb + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 v[QBM / NWT];
+        float4 v[QBM / NW];
 #pragma unroll
-        for (int i = 0; i < QBM / NWT; ++i) v[i] = ld4_sum<NP>(A + (size_t)min(m0 + wave + NWT * i, M - 1) * D + lane * 4, a_pstride);
+        for (int i = 0; i < QBM / NW; ++i) v[i] = ld4_sum<NP>(A + (size_t)min(m0 + wave + NW * i, M - 1) * D + lane * 4, a_pstride);
         idf_args_now(bias, C, ldc, N, xn_out, step_state, step_ts);      // the rest of the argument segment, behind the requests
         if (step_state && blockIdx.x == 0 && threadIdx.x == 0) sampler_prepare_step(step_state, step_ts, step_B);
 #pragma unroll
-        for (int i = 0; i < QBM / NWT; ++i) {
-            const int row = wave + NWT * i;
+        for (int i = 0; i < QBM / NW; ++i) {
+            const int row = wave + NW * i;
             float4 x = v[i];
             if (lnw) {
                 float mean, rstd;
@@ -709,12 +692,10 @@ __global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float 
             __builtin_amdgcn_s_barrier();
         }
         issue_step(P + 2);
-        if (!loader) {
-            rd(P, F[P & 1]);
-            if (P > 0) mma(F[(P - 1) & 1]);
-        }
+        rd(P, F[P & 1]);
+        if (P > 0) mma(F[(P - 1) & 1]);
     }
-    if (!loader) mma(F[1]);
+    mma(F[1]);
     // epilogue: x 2^e of the row, + bias, through LDS (over the ring, once every wave is done reading it), 16-byte row stores (write-through)
     constexpr int QCS = QHS + 4;
     float *Cs = ring;
@@ -722,7 +703,7 @@ __global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float 
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-        if (!loader && (a == 0 || two)) {
+        if (a == 0 || two) {
             const int col = (c0 + a) * 16 + 4 * g;
             float4 bv;
             bv.x = bias[min(n0 + col, N - 1)]; bv.y = bias[min(n0 + col + 1, N - 1)]; bv.z = bias[min(n0 + col + 2, N - 1)]; bv.w = bias[min(n0 + col + 3, N - 1)];
@@ -758,8 +739,8 @@ __global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float 
     __syncthreads();
     if constexpr (PLANES) {
 #pragma unroll
-        for (int it = 0; it < (QBM * (QHS / 8) + NTH - 1) / NTH; ++it) {
-            const int idx = tid + it * NTH, row = idx / (QHS / 8), c8 = (idx - row * (QHS / 8)) << 3, gr = m0 + row, gc = n0 + c8;
+        for (int it = 0; it < (QBM * (QHS / 8) + NT - 1) / NT; ++it) {
+            const int idx = tid + it * NT, row = idx / (QHS / 8), c8 = (idx - row * (QHS / 8)) << 3, gr = m0 + row, gc = n0 + c8;
             if (idx < QBM * (QHS / 8) && gr < M && gc < N) {
                 const int t = gc >> 8, grp = gc >> 6, o = gc & 63;
                 const float dn = Sd[8 * row + t];
@@ -775,36 +756,33 @@ __global__ __launch_bounds__(NT + 64 * LW) void ln_linear_h2_kernel(const float 
         }
     } else {
 #pragma unroll
-        for (int it = 0; it < (QBM * (QHS / 4) + NTH - 1) / NTH; ++it) {
-            const int idx = tid + it * NTH, row = idx / (QHS / 4), c4 = (idx - row * (QHS / 4)) << 2, gr = m0 + row;
+        for (int it = 0; it < (QBM * (QHS / 4) + NT - 1) / NT; ++it) {
+            const int idx = tid + it * NT, row = idx / (QHS / 4), c4 = (idx - row * (QHS / 4)) << 2, gr = m0 + row;
             if (idx < QBM * (QHS / 4) && gr < M && n0 + c4 < N) idf_store16_wt(C + (size_t)gr * ldc + n0 + c4, *reinterpret_cast<const float4 *>(Cs + row * QCS + c4));
         }
     }
 }
 
-#ifndef IDF_QKV_LOADER_WAVES
-#define IDF_QKV_LOADER_WAVES 0            // 0 (shipped): eight waves; 8: sixteen waves, eight of them loaders -- built and measured in round 6 (-DIDF_QKV_LOADER_WAVES=8): the same time in situ
-#endif                                    // (8.45 / 7.47 vs 8.49 / 7.63 us and 8.53 / 7.57 vs 8.46 / 7.51 us, whole samples within 0.2 %: profiles/r06_qkv_waves_ab.txt) -- unlike the feed-forward block,
-                                          // this kernel has only 160 KiB of stream and a 20-KiB epilogue per workgroup for the extra waves to shorten
+// (a sixteen-wave form with eight loader waves, as in ffn_h2_kernel, was built and measured in round 6: the same time in situ, profiles/r06_qkv_waves_ab.txt --
+// unlike the feed-forward block, this kernel has only 160 KiB of stream and a 20-KiB epilogue per workgroup for the extra waves to shorten)
 template <int NP>
 inline int launch_ln_linear_h2(hipStream_t s, const float *A, size_t a_pstride, const float *lnw, const float *lnb, int M, int N,
                                const float *pack, const float *bias, float *C, int ldc, float *xn_out, int64_t *step_state = nullptr,
                                int64_t *step_ts = nullptr, int step_B = 0, float *planes_out = nullptr, float *scales_out = nullptr) {
-    constexpr int LW = IDF_QKV_LOADER_WAVES, NTH = NT + 64 * LW;
     static idf_excl_cache excl, excl_p;
     if (planes_out) {                                  // the plane-pair output of the QKV projection (N = 768, the bounds behind the stream): see the kernel
-        const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, true, LW>), NP == 1 ? "ln_linear_h2_kernel<1 slab, planes out>" : "ln_linear_h2_kernel<5 slabs, planes out>", NTH, excl_p);
+        const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, true>), NP == 1 ? "ln_linear_h2_kernel<1 slab, planes out>" : "ln_linear_h2_kernel<5 slabs, planes out>", NT, excl_p);
         if (dyn != LDS_REQUEST) return IDF_NOT_EXCLUSIVE;
         if (!A) return IDF_OK;                         // (availability query: nothing to launch)
         const int nsl = (int)idf_cdiv(N, QHS);
-        hipLaunchKernelGGL((ln_linear_h2_kernel<NP, true, LW>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NTH), LDS_REQUEST, s, A, a_pstride, M,
+        hipLaunchKernelGGL((ln_linear_h2_kernel<NP, true>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NT), LDS_REQUEST, s, A, a_pstride, M,
                            (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, planes_out, scales_out);
         return IDF_OK;
     }
-    const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, false, LW>), NP == 1 ? "ln_linear_h2_kernel<1 slab>" : "ln_linear_h2_kernel<5 slabs>", NTH, excl);
+    const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, false>), NP == 1 ? "ln_linear_h2_kernel<1 slab>" : "ln_linear_h2_kernel<5 slabs>", NT, excl);
     if (dyn != LDS_REQUEST) return IDF_NOT_EXCLUSIVE;
     const int nsl = (int)idf_cdiv(N, QHS);
-    hipLaunchKernelGGL((ln_linear_h2_kernel<NP, false, LW>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NTH), LDS_REQUEST, s, A, a_pstride, M,
+    hipLaunchKernelGGL((ln_linear_h2_kernel<NP, false>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NT), LDS_REQUEST, s, A, a_pstride, M,
                        (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, (float *)nullptr, (float *)nullptr);
     return IDF_OK;
 }

@@ -85,22 +85,12 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const idf_smpl_model m, c
     }
 }
 
-#ifndef IDF_SMPL_FT
-#define IDF_SMPL_FT 32
-#define IDF_SMPL_SF 16
-#endif
-constexpr int FT = IDF_SMPL_FT, VT = 64, NTC = 3 * VT;  // frames / vertices / coordinates per workgroup
+constexpr int FT = 32, VT = 64, NTC = 3 * VT;           // frames / vertices / coordinates per workgroup
 constexpr int BT = 256;                                 // threads (4 waves x 48 coordinates); two workgroups share a CU (one's skinning phase beside the other's MFMA loop)
 constexpr int FM = FT / 16;                             // 16-frame MFMA tiles per wave (each basis fragment feeds FM*4 MFMAs)
 constexpr int STS = NTC + 1;                            // stage row stride
-constexpr int SF = IDF_SMPL_SF;                         // frames per skinning sub-step (their joint transforms are staged in LDS)
-#ifndef IDF_SMPL_TBF                                     // (tools/smpl_probe.hip rebuilds this file with other block shapes)
-#define IDF_SMPL_TBF 10
-#define IDF_SMPL_TBV 4
-#define IDF_SMPL_FRAME_SLOW 1
-#endif
-constexpr int TBF = IDF_SMPL_TBF, TBV = IDF_SMPL_TBV;   // workgroup order: blocks of TBF frame tiles x TBV vertex tiles (L2 working set ~2.9 MiB)
-constexpr bool FRAME_SLOW = IDF_SMPL_FRAME_SLOW;        // consecutive blocks walk the vertex blocks of one frame block (else the frame blocks of one vertex block)
+constexpr int SF = 16;                                  // frames per skinning sub-step (their joint transforms are staged in LDS)
+constexpr int TBF = 10, TBV = 4;                        // workgroup order: blocks of TBF frame tiles x TBV vertex tiles (L2 working set ~2.9 MiB)
 
 // One workgroup = 32 frames x 64 vertices.  Phase 1: the blend-shape GEMM feat[32,KB] x blend[KB,192] on the fp32 MFMA; the feature
 // tile sits in LDS, each wave streams the basis rows of its 48 output coordinates straight from global memory (three register sets,
@@ -123,27 +113,18 @@ __global__ __launch_bounds__(BT) void smpl_blend_skin_kernel(const idf_smpl_mode
     // so the logical index is permuted to give one XCD CONSECUTIVE logical workgroups.  (2) The logical index walks blocks of
     // TBF frame tiles x TBV vertex tiles: the ~64 workgroups an XCD runs at a time then share TBV basis slices (4 x 368 KiB) and
     // TBF frame tiles' features + joint transforms (10 x 141 KiB) -- 2.9 MiB, resident.  Consecutive blocks keep the frame block
-    // and move to the next vertex block.  Fabric-side reads per call (rocprofv3 FETCH_SIZE, tools/smpl_probe.hip rebuilt with
+    // and move to the next vertex block.  Fabric-side reads per call (rocprofv3 FETCH_SIZE, this file rebuilt with
     // other shapes): 144 MB this way, 203 MB with the vertex block kept instead, 142-210 MB for 17x3 / 25x2 / 10x8 / 13x4 blocks
     // -- and 430-440 us for ALL of them: the 40-MB basis + 7 MB of per-frame operands live in the Infinity Cache and the kernel
     // is bound by its matrix and skinning phases, not by these reads.  (Frame-tile-major order cycled each XCD through all 7 MiB
     // of features + transforms for every vertex tile; round 1 additionally spread each basis slice over all eight L2s: 657 MB.)
-    const int nft = (int)((N + FT - 1) / FT), nvt = (V + VT - 1) / VT, nfb = (nft + TBF - 1) / TBF;
+    const int nft = (int)((N + FT - 1) / FT), nvt = (V + VT - 1) / VT;
     const int nwg = gridDim.x, id = blockIdx.x;
-#ifdef IDF_SMPL_XF                                      // tools/smpl_probe.hip only: XCD x owns frame part x % XF, vertex part x / XF; frames fast
-    constexpr int XF = IDF_SMPL_XF, XV = 8 / XF;
-    const int nfp = (nft + XF - 1) / XF, nvp = (nvt + XV - 1) / XV, xcd = id & 7, l = id >> 3;
-    (void)nwg; (void)nfb;
-    const int fl = l % nfp, vpl = l / nfp;
-    const int ftile = (xcd % XF) * nfp + fl, vtile = (xcd / XF) * nvp + vpl;
-    if (vpl >= nvp) return;
-#else
     const int xq = nwg >> 3, xr = nwg & 7, xcd = id & 7;
     const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (id >> 3);
     const int blk = lid / (TBF * TBV), wi = lid - blk * (TBF * TBV);
     const int nvb = (nvt + TBV - 1) / TBV;
-    const int ftile = (FRAME_SLOW ? blk / nvb : blk % nfb) * TBF + wi % TBF, vtile = (FRAME_SLOW ? blk % nvb : blk / nfb) * TBV + wi / TBF;
-#endif
+    const int ftile = blk / nvb * TBF + wi % TBF, vtile = blk % nvb * TBV + wi / TBF;
     if (ftile >= nft || vtile >= nvt) return;          // ragged edge blocks (workgroup-uniform)
     const int64_t f0 = (int64_t)ftile * FT;
     const int v0 = vtile * VT;
@@ -325,11 +306,7 @@ extern "C" int interdiff_smpl_forward(const idf_smpl_model *m, const float *pose
     static std::atomic<uint64_t> lds_ok{0};
     if (lds > 64 * 1024 && idf_opt_in_lds(reinterpret_cast<const void *>(smpl_blend_skin_kernel<30>), 150 * 1024, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
     idf_prof_mark(IDF_K_SMPL_BLEND_SKIN, s);
-#ifdef IDF_SMPL_XF
-    const unsigned nwg_launch = (unsigned)(8 * idf_cdiv(idf_cdiv(N, FT), IDF_SMPL_XF) * idf_cdiv(idf_cdiv(m->V, VT), 8 / IDF_SMPL_XF));
-#else
     const unsigned nwg_launch = (unsigned)(idf_cdiv(idf_cdiv(N, FT), TBF) * idf_cdiv(idf_cdiv(m->V, VT), TBV) * TBF * TBV);
-#endif
     hipLaunchKernelGGL(smpl_blend_skin_kernel<30>, dim3(nwg_launch), dim3(BT), lds, s, *m,
                        feat, A, trans, N, verts, v_posed);
     idf_prof_mark(-1, s);

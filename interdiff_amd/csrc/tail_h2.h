@@ -53,7 +53,7 @@ struct TailArgs {
     int n_steps;
     float *u0;                    // [M][256]
     int M, T;
-    int plain_ids;                // A/B only (tune[IDF_TUNE_MISC] == 7): workgroup id -> row tile as in round 4 (tile = id); 0 = XCD-affine (below)
+    int plain_ids;                // 0 (the library always passes 0) = XCD-affine (below); 1 = workgroup id -> row tile as in round 4 (tile = id), measured and not adopted
 };
 
 template <int MODE, bool RAGGED>

@@ -483,10 +483,6 @@ class MDM:
         self.rowblock_math = os.environ.get('INTERDIFF_ROWBLOCK_MATH', ROWBLOCK_MATH_DEFAULT)
         if self.rowblock_math not in ('split', 'exact'):
             raise ValueError("rowblock_math must be 'split' or 'exact'")
-        # the split-f16 row block: 8 = the eight-wave kernel (csrc/denoiser.hip rowblock8_kernel, shipped since round 5), 4 = round 4's four-wave kernel (A/B runs)
-        self.rowblock_waves = int(os.environ.get('INTERDIFF_ROWBLOCK_WAVES', '8'))
-        if self.rowblock_waves not in (4, 8):
-            raise ValueError('rowblock_waves must be 4 or 8')
         self.pn = self.pn_arena = None
         if 'pcEmbedding.Linear.weight' in state_dict:
             self.pn, self.pn_arena = pack_pointnet2(state_dict, self.device)
@@ -662,7 +658,7 @@ class MDM:
 
     def ffn_graph_key(self, rows):
         """What a captured launch sequence bakes in about the feed-forward block (the sampler's graph cache key, diffusion.py)."""
-        return (self.ffn_class_for_rows(rows), self.ffn_math, self.ffn_rows, getattr(self, 'rowblock_math', 'exact'), getattr(self, 'rowblock_waves', 8))
+        return (self.ffn_class_for_rows(rows), self.ffn_math, self.ffn_rows, getattr(self, 'rowblock_math', 'exact'))
 
     def _pick_ffn_tile(self, rows, own_rows=None):
         """The fused feed-forward block has 16-, 32- and 64-row kernels (csrc/ffn.h); the 32-row one agrees with the other two to
@@ -679,8 +675,6 @@ class MDM:
                 tile = 16 if own_rows <= self.FFN16_MAX_ROWS else 64
         self.w.tune[_lib.TUNE['ffn']] = {16: 2, 64: 3}.get(tile, 1)
         self.w.tune[_lib.TUNE['ffn_math']] = (1 if getattr(self, 'rowblock_math', 'exact') == 'split' else 2) if getattr(self, 'ffn_math', 'exact') == 'split' else 0
-        if self.w.tune[_lib.TUNE['misc']] in (0, 8):            # (other values of the A/B switch are left to whoever set them)
-            self.w.tune[_lib.TUNE['misc']] = 8 if getattr(self, 'rowblock_waves', 8) == 4 else 0
 
     def arithmetic_report(self, device_verdicts=True):
         """Which arithmetic every contraction of a denoiser forward takes under the current ``ffn_math`` / ``rowblock_math`` selection, layer by
@@ -708,10 +702,10 @@ class MDM:
                      rowblock='split' if (rb_split and ly.rb_h2_ok and (not ly.is_qan or (ly.qc_h2 and l > 0)) and not (bad('rowblock8_kernel<' + kind) and bad('rowblock_kernel<' + kind))) else 'exact')
             if not ly.is_qan:
                 slabs = '1 slab' if l == 0 else '5 slabs'
-                attn_packed = bool(split and ly.sa_out_frag_h2 and w.tune[_lib.TUNE['misc']] != 6)
-                planes = bool(attn_packed and ly.sa_in_pack_h2 and ly.qkv_bounds_ok and w.tune[_lib.TUNE['misc']] != 9 and not bad('ln_linear_h2_kernel<' + slabs + ', planes out>') and not bad('self_attn_h2_kernel<planes in>'))
+                attn_packed = bool(split and ly.sa_out_frag_h2)
+                planes = bool(attn_packed and ly.sa_in_pack_h2 and ly.qkv_bounds_ok and not bad('ln_linear_h2_kernel<' + slabs + ', planes out>') and not bad('self_attn_h2_kernel<planes in>'))
                 d['qkv'] = 'split' if (split and ly.sa_in_pack_h2 and (planes or not any(n == 'ln_linear_h2_kernel<%s>' % slabs for n in failing))) else 'exact'
-                # csrc/denoiser.hip: the split-f16 attention kernel unless tune misc == 6 (A/B) or its fragments were not packed; clips longer than 192 frames take the fp32 kernel at launch time (not known here)
+                # csrc/denoiser.hip: the split-f16 attention kernel unless its fragments were not packed; clips longer than 192 frames take the fp32 kernel at launch time (not known here)
                 d['self_attention'] = 'split' if (attn_packed and (planes or 'self_attn_h2_kernel' not in failing)) else 'exact'
                 d['qkv_hands_over_planes'] = planes
             layers.append(d)

@@ -112,10 +112,11 @@ def test_mdm_forward_split_f16_vs_exact_and_fp64(lib):
         assert err['exact'] <= 1e-5, (B, T, err)
 
 
-def test_mdm_forward_with_either_self_attention_kernel(lib):
-    """The split-f16 self-attention (csrc/attn_h2.h: the default of the split arithmetic since round 5) and the fp32 kernel it replaced (tune[IDF_TUNE_MISC] = 6; also what a
-    clip longer than 192 frames takes) against the oracle in float64 at the bench shape, the longest clip of either kernel, the reference's default clip length and clips shorter
-    than a key tile: the split-f16 kernel is as close to fp64 as the fp32 one (within 2x)."""
+def test_mdm_forward_with_either_self_attention_kernel_by_deny_list(lib):
+    """The split-f16 self-attention (csrc/attn_h2.h: the default of the split arithmetic since round 5) and the fp32 kernel it replaced (what the debug deny list of
+    'self_attn_h2_kernel' selects; also what a clip longer than 192 frames takes) against the oracle in float64 at the bench shape, the longest clip of either kernel, the
+    reference's default clip length and clips shorter than a key tile: the split-f16 kernel is as close to fp64 as the fp32 one (within 2x).  A handle with a reserved
+    tune entry set is refused (include/interdiff_hip.h idf_mdm_weights.tune)."""
     from interdiff_amd import _lib
     from interdiff_amd.mdm import MDM
     sd = fx.mdm_weights()
@@ -125,14 +126,23 @@ def test_mdm_forward_with_either_self_attention_kernel(lib):
         x, ts, cond = fx.mdm_inputs(B, T)
         ref = oden.mdm_forward(sd64, x.double(), ts, cond.double())
         err = {}
-        for name, misc in (('fp32_attention', 6), ('split_attention', 0)):
-            m.w.tune[_lib.TUNE['misc']] = misc
-            got = m(x.to(DEV), ts.to(DEV), y={'cond': cond.to(DEV)}).cpu().double()
+        for name, deny in (('fp32_attention', 'self_attn_h2_kernel'), ('split_attention', '')):
+            try:
+                _lib.debug_deny_exclusive(deny)
+                got = m(x.to(DEV), ts.to(DEV), y={'cond': cond.to(DEV)}).cpu().double()
+            finally:
+                _lib.debug_deny_exclusive('')
             err[name] = float((got - ref).abs().max() / ref.abs().max())
-        m.w.tune[_lib.TUNE['misc']] = 0
         fx.record_parity('mdm_forward_split_attention_vs_fp64_B%d_T%d' % (B, T), **err)
         assert err['split_attention'] <= max(2 * err['fp32_attention'], 2e-6), (B, T, err)
         assert err['fp32_attention'] <= 2e-6, (B, T, err)
+    x, ts, cond = fx.mdm_inputs(2, 12)
+    try:
+        m.w.tune[7] = 6                                  # a reserved entry (once the A/B switch of the attention kernel)
+        with pytest.raises(RuntimeError):
+            m(x.to(DEV), ts.to(DEV), y={'cond': cond.to(DEV)})
+    finally:
+        m.w.tune[7] = 0
 
 
 def test_mdm_no_rotary_switch(lib):

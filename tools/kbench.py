@@ -1,10 +1,9 @@
 """Kernel-level A/B bench on one MI355X (not part of the product path).
 
-    python tools/kbench.py [--B 16] [--T 100] [--reps 20] [--sweep]
+    python tools/kbench.py [--B 16] [--T 100] [--reps 20]
 
 Times every kernel kind of one denoiser forward (HIP events on the launch stream, via the library's profile
-hooks) and, with --sweep, re-times the forward under every tile configuration of each GEMM call site
-(idf_mdm_weights.tune, a field of the model handle), and times the fused FFN kernel against the two-GEMM form it replaced.  Output: one table per sweep + a JSON line, so the numbers can be pasted into profiles/.
+hooks) and the fused FFN kernel against the two-GEMM form it replaced.  Output: one table + a JSON line, so the numbers can be pasted into profiles/.
 """
 import argparse
 import ctypes as C
@@ -19,11 +18,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from interdiff_amd import synthetic as syn, _lib          # noqa: E402
 from interdiff_amd.mdm import MDM, ffn_parts, linear        # noqa: E402
-
-TUNE = _lib.TUNE
-KIND_OF = dict(embed='embed', qkv='gemm_qkv', outproj='gemm_outproj', heads='gemm_heads')
-CFGS = {0: 'default', 1: '32x64 ks1 kc32', 2: '32x64 ks1 kc64', 3: '32x64 ks2 kc64', 4: '64x64 ks1 kc32', 5: '32x32 ks1 kc64',
-        6: '32x32 ks2 kc64', 7: '64x32 ks1 kc32', 8: '64x32 ks2 kc64', 9: 'reg-staged 32x64 kc32'}
 
 
 def profile_forward(lib, model, x, ts, y, reps):
@@ -107,8 +101,6 @@ def main():
     ap.add_argument('--B', type=int, default=16)
     ap.add_argument('--T', type=int, default=100)
     ap.add_argument('--reps', type=int, default=20)
-    ap.add_argument('--sweep', action='store_true')
-    ap.add_argument('--sites', default='outproj,qkv,heads,embed')
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     lib = _lib.load()
@@ -126,27 +118,9 @@ def main():
     for k, v in base.items():
         if not k.startswith('_'):
             print('   %-14s %8.2f us' % (k, v))
-    result = dict(B=args.B, T=args.T, default=base, wall_us=wall, sweeps={})
+    result = dict(B=args.B, T=args.T, default=base, wall_us=wall)
     result['ffn'] = ffn_ab(model, args.B * args.T)
     print('== feed-forward block at M=%d (graph-replayed bursts, us per layer): %s' % (args.B * args.T, json.dumps(result['ffn'])))
-    if args.sweep:
-        ref = model(x, ts, y=y).clone()
-        for site in args.sites.split(','):
-            cfgs = range(5) if site == 'embed' else range(10)
-            row = {}
-            for c in cfgs:
-                model.w.tune[TUNE[site]] = c
-                p = profile_forward(lib, model, x, ts, y, args.reps)
-                # out-projection: cfg 0 = folded into the attention kernel (no GEMM launch), so compare the whole attention block
-                row[c] = (sum(p.get(k, 0.0) for k in ('self_attn', 'gemm_outproj', 'rowblock_std')) if site == 'outproj' else p[KIND_OF[site]])
-                err = ((model(x, ts, y=y) - ref).abs().max() / ref.abs().max()).item()
-                assert err < (2e-5 if site == 'outproj' else 1e-5), (site, c, err)      # (per-head partial sums round differently)
-            model.w.tune[TUNE[site]] = 0
-            result['sweeps'][site] = row
-            print('== %s' % site)
-            for c, v in row.items():
-                print('   cfg %d %-18s %8.2f us%s' % (c, CFGS[c] if site != 'embed' else 'embed variant', v,
-                                                     ' (self_attn + out-projection + row block)' if site == 'outproj' else ''))
     print(json.dumps(result))
 
 

@@ -49,10 +49,10 @@ int main(int argc, char **argv) {
         for (int k = 0; k < 3; ++k) { ly.ln_w[k] = take(256); ly.ln_b[k] = take(256); }
     }
     if (h2) w.tune[IDF_TUNE_FFN_MATH] = 1;
-    if (h2 == 1 && waves4) w.tune[IDF_TUNE_MISC] = 8;
+    if (h2 == 1 && waves4) interdiff_debug_deny_exclusive("rowblock8_kernel");      // the eight-wave kernel refused: its four-wave fallback runs
     w.rb_tokens = tokens;
     const int tv = (h2 == 1 && !waves4) ? (tokens ? tokens : (B * ((T + 7) / 8) <= 256 ? 8 : 16)) : 16;
-    if (h2 == 2) w.tune[IDF_TUNE_MISC] = 5;       // the split-f16 attention kernel (csrc/attn_h2.h)        // (no split-f16 FFN / QKV streams are set: those stay exact)
+    // h2 = 2: the split-f16 attention kernel (csrc/attn_h2.h) runs because sa_out_frag_h2 is set (no split-f16 FFN / QKV streams are set: those stay exact)
     if (off > arena_floats) { printf("arena too small\n"); return 1; }
     float *memctx, *x, *x0;
     int64_t *ts;
