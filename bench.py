@@ -1,6 +1,6 @@
 """bench.py -- denoising-sampler throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one DDPM reverse step (p_sample: denoiser forward + x0-inpainting + [gated correction] + posterior update with
 in-kernel noise) over one batch of B=16 BEHAVE-shaped synthetic clips of T=100 frames per GPU (BASELINE config #2:
@@ -21,10 +21,15 @@ caller of the path receives) as DIR/sample_rank<r>.npy, float32; at most 64 MB i
 clips).  Inputs, weights and noise seeds are fixed, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself as N ranks (torch.distributed.run, one per GPU).
-After the timed region every rank scores its clips and the six per-clip metric vectors are collated with the path's one collective
-(RCCL all-gather); rank 0 then measures, outside the clock: the same sample in no_correction mode, BASELINE config #3 (B=32),
-a K-step window of plain steps, the per-kernel profile + roofline kernel, the conditioning path, the post-optimisation row and the
-CPU baseline.
+
+A plain run does only what the headline needs: it sets up (a process group, through RCCL even for one rank), warms up (graph
+captures included, and the timed route checked against the eager route on 60 steps), times the K steps, writes the outputs if asked
+and prints the JSON line.  That set-up stays in every run because the timed steps follow it: without the process group and the
+route check, --steps 20 timed 0.190 instead of 0.221 ms per step on an MI355X (--steps 1000: 0.1885 instead of 0.1902), so
+ms_per_step would no longer mean what it did.  `--full` adds every measurement after the clock: every rank scores its clips and
+the six per-clip metric vectors are collated with the path's one collective (RCCL all-gather); rank 0 then measures the same sample
+in no_correction mode, BASELINE config #3 (B=32), a K-step window of plain steps, the per-kernel profile + roofline kernel, the
+conditioning path, the post-optimisation row and the CPU baseline.  The --no-* options leave legs out of a --full run.
 """
 import argparse
 import ctypes as C
@@ -380,10 +385,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=STEPS)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-profile', action='store_true')
-    ap.add_argument('--no-postopt', action='store_true')
-    ap.add_argument('--no-extra-configs', action='store_true', help='skip the no_correction / B=32 / plain-window legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg (eval collation, extra configurations, kernel profile + roofline, '
+                         'conditioning, post-optimisation, CPU baseline)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-kernel-profile', action='store_true', help='--full without the kernel profile and roofline')
+    ap.add_argument('--no-postopt', action='store_true', help='--full without the post-optimisation leg')
+    ap.add_argument('--no-extra-configs', action='store_true', help='--full without the no_correction / B=32 / plain-window legs')
     ap.add_argument('--clips-per-gpu', type=int, default=B_PER_GPU,
                     help='NOT the BASELINE configuration unless 16: batch-scaling experiments only (DESIGN.md §4.1)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -453,30 +461,31 @@ def main():
         dump_outputs(args.dump_outputs, out, rank, world)
         log('outputs of the last timed step written to %s' % args.dump_outputs)
 
-    # ---- eval leg, all ranks: every rank scores its clips, ONE all-gather (RCCL over xGMI) collates the six per-clip metric vectors
-    from interdiff_amd import eval as ev
-    clip_batch = dict(gt=bt['gt'], cond=bt['cond'], hand_pose=bt['hand_pose'], beta=bt['beta'], obj_points=bt['obj_points'])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    per_clip, means = ev.evaluate_sharded(model, diff, corr, clip_batch, PAST, mode='correction', diverse_samples=1, seed=1000,
-                                          presharded=True)
-    torch.cuda.synchronize()
-    eval_s = time.perf_counter() - t0
-    assert all(v.numel() == B_PER_GPU * world for v in per_clip.values())
-    coll = idist.collective_backend_info()
-    if world == 1 and coll['backend'] == 'nccl':      # one rank: evaluate_sharded took the world == 1 shortcut -- push the same vectors through RCCL explicitly
-        mine = {k: v.clone() for k, v in per_clip.items()}
-        back, header = idist.gather_metrics(mine, 1, counts=[B_PER_GPU], return_header=True, force_collective=True, check_header=True)
-        assert all(torch.equal(back[k], mine[k]) for k in mine)
-        coll['single_rank_all_gather'] = 'issued (1-rank nccl group, header verified)'
-    if rccl_note:
-        coll['note'] = rccl_note
+    # ---- eval leg (--full), all ranks: every rank scores its clips, ONE all-gather (RCCL over xGMI) collates the six per-clip metric vectors
+    if args.full:
+        from interdiff_amd import eval as ev
+        clip_batch = dict(gt=bt['gt'], cond=bt['cond'], hand_pose=bt['hand_pose'], beta=bt['beta'], obj_points=bt['obj_points'])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        per_clip, means = ev.evaluate_sharded(model, diff, corr, clip_batch, PAST, mode='correction', diverse_samples=1, seed=1000,
+                                              presharded=True)
+        torch.cuda.synchronize()
+        eval_s = time.perf_counter() - t0
+        assert all(v.numel() == B_PER_GPU * world for v in per_clip.values())
+        coll = idist.collective_backend_info()
+        if world == 1 and coll['backend'] == 'nccl':      # one rank: evaluate_sharded took the world == 1 shortcut -- push the same vectors through RCCL explicitly
+            mine = {k: v.clone() for k, v in per_clip.items()}
+            back, header = idist.gather_metrics(mine, 1, counts=[B_PER_GPU], return_header=True, force_collective=True, check_header=True)
+            assert all(torch.equal(back[k], mine[k]) for k in mine)
+            coll['single_rank_all_gather'] = 'issued (1-rank nccl group, header verified)'
+        if rccl_note:
+            coll['note'] = rccl_note
     idist.shutdown()              # no collective after this point: rank 0 alone takes the extra legs below
     if rank != 0:
         return
 
     extra = {}
-    if not args.no_extra_configs:
+    if args.full and not args.no_extra_configs:
         w_nc, o_nc = timed_samples(diff, model, None, bt, y, 1)
         extra['no_correction'] = dict(workload='the same clips, eval_smpl_short.py --mode no_correction (1000 plain steps)', steps=STEPS,
                                       ms_per_step=1e3 * w_nc / STEPS, value=STEPS * B_PER_GPU * T / w_nc, unit='frame-steps/s')
@@ -544,7 +553,7 @@ def main():
                                                  equals_eager_route_on_2_windows_60_steps_across_t500=True)
         log('extra configurations done')
     prof = None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         prof = kernel_profile(diff, model, corr, bt, y)
         dom_us, dom_best = time_dominant_kernel(model, dev)
         burst_us, burst_best = time_dominant_kernel(model, dev, cycle_layers=False)
@@ -559,26 +568,29 @@ def main():
             exact_fwd_us = time_forward_graph(model, bt, y, dev)
             model.ffn_math = 'split' 
         log('kernel profile done')
-    # once-per-sample conditioning path ("next" row): PointNet++ object encoder + embeddings + 8-layer encoder
-    ei = tt(syn.make_embedding_inputs(seed=77, B=B_PER_GPU, T=T, n_points=P), dev)
-    args_e = (ei['body_pose'], ei['body_trans'], ei['obj_angles'], ei['obj_trans'], ei['obj_points'], PAST)
-    model._get_embeddings(*args_e)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
+    enc_ms = None
+    if args.full:
+        # once-per-sample conditioning path ("next" row): PointNet++ object encoder + embeddings + 8-layer encoder
+        ei = tt(syn.make_embedding_inputs(seed=77, B=B_PER_GPU, T=T, n_points=P), dev)
+        args_e = (ei['body_pose'], ei['body_trans'], ei['obj_angles'], ei['obj_trans'], ei['obj_points'], PAST)
         model._get_embeddings(*args_e)
-    e1.record()
-    e1.synchronize()
-    enc_ms = e0.elapsed_time(e1) / 5
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            model._get_embeddings(*args_e)
+        e1.record()
+        e1.synchronize()
+        enc_ms = e0.elapsed_time(e1) / 5
     post = None
-    if not args.no_postopt:
+    if args.full and not args.no_postopt:
         post = postopt_bench(corr.smpl, assets[1], dev, with_cpu=(world == 1 and not args.no_cpu_baseline))
         log('post-optimisation bench done')
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(assets, tt({k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in bt.items()}),
                            {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in y.items()})
-    log('cpu baseline done' if cpu else 'cpu baseline skipped')
+    if args.full:
+        log('cpu baseline done' if cpu else 'cpu baseline skipped')
     Btot = B_PER_GPU * world
     split = getattr(model, 'ffn_math', 'exact') == 'split'
     line = dict(metric='denoising frame-steps/sec (denoising-steps/sec x B x T frames)', value=n_timed * Btot * T / wall,
@@ -599,11 +611,12 @@ def main():
                             global_batch=Btot, seq_len=T, samples_in_region=n_samples, correction_steps_in_region=n_corr,
                             plain_steps_in_region=n_timed - n_corr, timesteps='%d whole sample(s): t = 999..0' % (K // STEPS) + ('' if K % STEPS == 0 else ', then t = 999..%d' % (STEPS - K % STEPS)),
                             parallelism='clips sharded x%d' % world, ffn_math=getattr(model, 'ffn_math', 'exact')))
-    line['eval_collation'] = dict(collective='ONE all_gather of [7, B_local] fp32 (count header + six metric rows), %d rank(s)' % world,
-                                  backend=coll.get('backend'), rccl_version=coll.get('rccl_version'), single_rank_all_gather=coll.get('single_rank_all_gather'), note_rccl=coll.get('note'),
-                                  seconds_sample_plus_metrics=eval_s, clips=Btot, means=means,
-                                  sharding='every rank draws the whole batch\'s noise at its clips\' global position (shard=): a sharded run equals the unsharded one bit for bit (tests)',
-                                  note='random-init denoiser: the metric values only serve as parity evidence against the oracle')
+    if args.full:
+        line['eval_collation'] = dict(collective='ONE all_gather of [7, B_local] fp32 (count header + six metric rows), %d rank(s)' % world,
+                                      backend=coll.get('backend'), rccl_version=coll.get('rccl_version'), single_rank_all_gather=coll.get('single_rank_all_gather'), note_rccl=coll.get('note'),
+                                      seconds_sample_plus_metrics=eval_s, clips=Btot, means=means,
+                                      sharding='every rank draws the whole batch\'s noise at its clips\' global position (shard=): a sharded run equals the unsharded one bit for bit (tests)',
+                                      note='random-init denoiser: the metric values only serve as parity evidence against the oracle')
     line.update(extra)
     if prof:
         split = getattr(model, 'ffn_math', 'exact') == 'split'
@@ -716,7 +729,8 @@ def main():
                                         matrix_roof_tflops=(PEAK_F16_MFMA_TFLOPS / 3 if split else PEAK_F32_MFMA_TFLOPS), launches=22,
                                         how='MDM.forward (22 launches, B=%d T=%d) replayed from a hipGraph, HIP events on its stream' % (B_PER_GPU, T))
         line['kernels_us_event_to_event'] = {k: round(v['us_avg'], 2) for k, v in prof.items()}    # includes the launch gap + event records
-    line['conditioning_ms_per_sample'] = enc_ms        # MDM._get_embeddings, outside the timed region (once per 1000 steps)
+    if enc_ms is not None:
+        line['conditioning_ms_per_sample'] = enc_ms    # MDM._get_embeddings, outside the timed region (once per 1000 steps)
     if post:
         line['post_optimisation'] = post                    # "next" row N4 (optimization.py), outside the timed region
     if cpu:

@@ -1,7 +1,7 @@
 #!/bin/bash
-# copies the judged summaries of one measurement set (tools/profile_round_r06.sh on the GPU box -> gpurun_out/<tag>_*) into profiles/ under their committed names, then renders the tables
+# copies the judged summaries of one measurement set (tools/profile_round_r06.sh on the GPU box -> $IDF_PROFILE_OUT/<tag>_*, default profile_out/) into profiles/ under their committed names, then renders the tables
 tag=${1:-r06}; cd "$(dirname "$0")/.."
-g=gpurun_out; p=profiles
+g=${IDF_PROFILE_OUT:-profile_out}; p=profiles
 cp $g/${tag}_bench.json $p/${tag}_bench.json
 cp $g/${tag}_bench_kernel_stats.txt $p/${tag}_kernel_stats_bench.txt
 cp $g/${tag}_bench_two_chains_kernel_stats.txt $p/${tag}_kernel_stats_bench_two_chains.txt

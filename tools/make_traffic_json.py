@@ -1,7 +1,7 @@
 """profiles/traffic.json from the counter passes and the kernel stats of one measurement set (not product code):
 
-    python tools/make_traffic_json.py <tag> [--dir gpurun_out]      reads <dir>/<tag>_fetch_size_kbench_pmc.txt, <tag>_write_size_kbench_pmc.txt, <tag>_sq_kbench_pmc.txt,
-                                                                    <tag>_bench_kernel_stats.txt; writes profiles/traffic.json (+ a copy <dir>/<tag>_traffic.json)
+    python tools/make_traffic_json.py <tag> [--dir DIR]      reads <dir>/<tag>_fetch_size_kbench_pmc.txt, <tag>_write_size_kbench_pmc.txt, <tag>_sq_kbench_pmc.txt,
+                                                      <tag>_bench_kernel_stats.txt (DIR: $IDF_PROFILE_OUT, default profile_out/); writes profiles/traffic.json (+ a copy <dir>/<tag>_traffic.json)
 
 What bench.py's `roofline` block reads back as RECORDED values of the kernel build named in `kernel_id` (bench.py DOMINANT_KERNEL_ID): per-launch fabric-side bytes of the feed-forward
 kernel (FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for 16-B/lane streaming reads on gfx950 + WRITE_SIZE as reported, KiB -> bytes), its rocprofv3 in-situ mean duration, and its
@@ -41,7 +41,7 @@ def in_situ(path):
 
 def main():
     tag = sys.argv[1]
-    d = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == '--dir' else 'gpurun_out'
+    d = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == '--dir' else os.environ.get('IDF_PROFILE_OUT', 'profile_out')
     d = os.path.join(ROOT, d)
     fetch = pmc(os.path.join(d, tag + '_fetch_size_kbench_pmc.txt'), 'FETCH_SIZE')
     write = pmc(os.path.join(d, tag + '_write_size_kbench_pmc.txt'), 'WRITE_SIZE')
