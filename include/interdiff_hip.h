@@ -416,6 +416,44 @@ int interdiff_metrics(const idf_correction_ctx *c, const float *obj_pred, const 
                       void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * HO-GCN skeleton mode (eval_skeleton.py; tokens C = 106 = body 21x3 | object keypoints 12x3 |
+ * pose [trans 3, quaternion xyzw 4]).  Device code: csrc/skeleton.h, launchers csrc/skeleton.hip.
+ * Predictor ObjProjector of model/correction_skeleton.py:7-137 with BatchNorm folded into the 1x1
+ * convolutions at pack time (interdiff_amd/skeleton.py: pack_skeleton_objprojector; arena layout
+ * there).  Built for n_pre = T = past_len + future_len = 20, 21 joints, channel widths
+ * cin, cout <= 64 (IDF_E_INVAL otherwise).
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t T, past_len, J, n_pre;   /* 20, 10, 21, 20                                    */
+    const float *arena;
+    int64_t dct_pad;           /* [n_pre][past_len]  DCT with the idx_pad frames folded in */
+    int64_t dct;               /* [n_pre][T]                                             */
+    int64_t idct;              /* [T][n_pre]                                             */
+    int64_t layer[12];         /* 3 stacks x 4 layers; each: see pack_skeleton_objprojector */
+    int32_t cin[12], cout[12];
+} idf_skel_objproj;
+
+/* replaces ObjProjector.sample (model/correction_skeleton.py:84-137): obj_angles [T,B,4] quaternion
+ * xyzw, obj_trans [T,B,3], human_points [T,B,J,3] -> quat_out [T,B,4] xyzw, trans_out [T,B,3]. */
+int interdiff_skeleton_objprojector_sample(const idf_skel_objproj *op, const float *obj_angles,
+                                           const float *obj_trans, const float *human_points, int32_t B,
+                                           float *quat_out, float *trans_out, void *stream);
+/* replaces eval_skeleton.denoised_fn (eval_skeleton.py:82-111) for one gated step: x [B,1,106,T] (read
+ * only), gt = inpainted_motion [B,1,106,T] (only its past pose rows are read), zero_pose_obj [B,12,3]
+ * -> out [B,1,106,T] = blend_t * x + (1 - blend_t) * [body, calc_obj_pred(pose'), pose'] with
+ * blend_t = t / 1000.  One launch, one workgroup per clip.  The gate (t <= 500, t % 50 == 0) is the
+ * caller's. */
+int interdiff_skeleton_correction(const idf_skel_objproj *op, const float *x, const float *gt,
+                                  const float *zero_pose_obj, int32_t B, int32_t T, float blend_t,
+                                  float *out, void *stream);
+/* replaces calc_metric_single (eval_skeleton.py:46-68) over frames [from_frame, T): body [T,B,21*3],
+ * obj [T,B,12*3], pose [T,B,7] (pred and gt each) -> out4 = {mpjpe_h, mpjpe_o, translation_error,
+ * rotation_error}.  One workgroup, fixed reduction order: repeated calls give the same bits. */
+int interdiff_skeleton_metrics(const float *body_pred, const float *body_gt, const float *obj_pred,
+                               const float *obj_gt, const float *pose_pred, const float *pose_gt,
+                               int32_t T, int32_t B, int32_t from_frame, float *out4, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Physics post-optimisation ("next" row N4)   replaces optimization.py:19-173 (optimize):
  * Adam (lr 1e-3) over the rotation MATRICES of the 52 SMPL-H joints and of the object plus the two
  * translations of every frame, loss = penetration + regularisers + temporal smoothness + static-foot

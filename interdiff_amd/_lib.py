@@ -9,7 +9,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('INTERDIFF_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libinterdiff_hip.so')      # (the override: A/B builds of the SAME library under build_ab/, tools/ only)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
@@ -52,6 +52,12 @@ class PointNet2(C.Structure):
 class ObjProj(C.Structure):
     _fields_ = [('T', i32), ('past_len', i32), ('P', i32), ('n_pre', i32), ('arena', vp),
                 ('dct_pad', i64), ('dct', i64), ('idct', i64), ('hand_bonus', i64),
+                ('layer', i64 * 12), ('cin', i32 * 12), ('cout', i32 * 12)]
+
+
+class SkelObjProj(C.Structure):
+    _fields_ = [('T', i32), ('past_len', i32), ('J', i32), ('n_pre', i32), ('arena', vp),
+                ('dct_pad', i64), ('dct', i64), ('idct', i64),
                 ('layer', i64 * 12), ('cin', i32 * 12), ('cout', i32 * 12)]
 
 
@@ -120,6 +126,9 @@ _SIGS = {
                                     vp, vp, sz, vp]),
     'interdiff_contact_nn_workspace_bytes': (sz, [C.POINTER(CorrectionCtx), i32, i32]),
     'interdiff_contact_nn': (C.c_int, [C.POINTER(CorrectionCtx), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_objprojector_sample': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, vp, vp, vp]),
+    'interdiff_skeleton_correction': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, i32, f32, vp, vp]),
+    'interdiff_skeleton_metrics': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
