@@ -453,6 +453,39 @@ int interdiff_skeleton_metrics(const float *body_pred, const float *body_gt, con
                                const float *obj_gt, const float *pose_pred, const float *pose_gt,
                                int32_t T, int32_t B, int32_t from_frame, float *out4, void *stream);
 
+/* ---- the skeleton DENOISER (model/diffusion_skeleton.py MDM): the decoder / encoder of idf_mdm_weights with token width
+ * C = n_body + 3 n_points + 7 = 106 (W_in = [bodyEmbedding | objEmbedding | 7 zero columns], feed-forward width <= 1024 zero-padded
+ * into the 1024-wide streams) and a KEYPOINT HEAD instead of two plain linears: bodyFinalLinear gives the n_body body channels,
+ * objFinalLinear 7 pose values (translation xyz | quaternion xyzw), and the 3 n_points object-keypoint channels of x0 are
+ * calc_obj_pred(pose, zero_pose_obj) = R(q) z_k + translation with pytorch3d's un-normalised quaternion_to_matrix
+ * (two_s = 2 / (q . q)), formed in the epilogue of the heads GEMM (csrc/skel_head.h).  All offsets in floats into w->arena. */
+typedef struct idf_skel_head {
+    int32_t n_body, n_points;      /* 63, 12 (3 n_points a multiple of 4, at most 48) */
+    int32_t n_tiles, reserved;     /* 32-row column tiles of the packed head: ceil(n_body / 25); reserved = 0 */
+    int64_t out_w, out_b;          /* [32 n_tiles][256], [32 n_tiles]: per tile the 7 objFinalLinear rows, then 25 bodyFinalLinear rows (zero past n_body) */
+    int64_t shape_w, shape_b;      /* shapeEmbedding [256][3 n_points], [256] (0, 0: no encoder side) */
+} idf_skel_head;
+/* replaces MDM.forward (diffusion_skeleton.py:250-257): interdiff_mdm_forward for the skeleton model; zero_pose_obj [B,n_points,3]
+ * (16-byte aligned), x / x0 [B,1,C,T].  w->C must be n_body + 3 n_points + 7.  Exact-fp32 heads GEMM (the split-f16 step tail serves
+ * C = 144 only). */
+int interdiff_skeleton_mdm_forward(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, const float *x,
+                                   const int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, float *x0,
+                                   void *ws, size_t ws_bytes, void *stream);
+/* interdiff_mdm_forward_step for the skeleton model: one plain reverse step, the update over all C channels -- the derived keypoint
+ * channels included -- inside the heads GEMM's epilogue.  Same bits as interdiff_skeleton_mdm_forward followed by
+ * interdiff_posterior_step_dev(ts != NULL); replaces gaussian_diffusion.py:425-461 (p_sample) around diffusion_skeleton.py:250-257. */
+int interdiff_skeleton_mdm_forward_step(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
+                                        int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
+                                        const uint8_t *mask, const float *table, int64_t *state, void *ws, size_t ws_bytes,
+                                        void *stream);
+/* replaces MDM._get_embeddings (diffusion_skeleton.py:194-215): the per-clip additive feature of interdiff_mdm_encode is
+ * shapeEmbedding(zero_pose_obj.view(B, 3 n_points)) (one fp32-MFMA GEMM into the workspace), x_past [B,1,C,Tp] holds the past
+ * frames (the pose channels meet zero columns of W_in) -> cond [Tp,B,256]. */
+size_t interdiff_skeleton_mdm_encode_workspace_bytes(int32_t B, int32_t Tp);
+int interdiff_skeleton_mdm_encode(const idf_mdm_weights *w, const idf_skel_head *head, const float *zero_pose_obj,
+                                  const float *x_past, int32_t B, int32_t Tp, float *cond, void *ws, size_t ws_bytes,
+                                  void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Physics post-optimisation ("next" row N4)   replaces optimization.py:19-173 (optimize):
  * Adam (lr 1e-3) over the rotation MATRICES of the 52 SMPL-H joints and of the object plus the two

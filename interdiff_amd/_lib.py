@@ -61,6 +61,11 @@ class SkelObjProj(C.Structure):
                 ('layer', i64 * 12), ('cin', i32 * 12), ('cout', i32 * 12)]
 
 
+class SkelHead(C.Structure):
+    _fields_ = [('n_body', i32), ('n_points', i32), ('n_tiles', i32), ('reserved', i32),
+                ('out_w', i64), ('out_b', i64), ('shape_w', i64), ('shape_b', i64)]
+
+
 class CorrectionCtx(C.Structure):
     _fields_ = [('smpl', C.POINTER(SmplModel)), ('objproj', C.POINTER(ObjProj)),
                 ('faces', vp), ('adj_ptr', vp), ('adj_face', vp), ('adj_corner', vp), ('markers_idx', vp),
@@ -129,6 +134,10 @@ _SIGS = {
     'interdiff_skeleton_objprojector_sample': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, vp, vp, vp]),
     'interdiff_skeleton_correction': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, i32, f32, vp, vp]),
     'interdiff_skeleton_metrics': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    'interdiff_skeleton_mdm_forward': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+    'interdiff_skeleton_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_mdm_encode_workspace_bytes': (sz, [i32, i32]),
+    'interdiff_skeleton_mdm_encode': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),

@@ -1582,6 +1582,12 @@ void run_heads(hipStream_t s, const Args &g, int np, bool post) {
     if (np == NSL) run_heads_np<NSL>(s, g, post);
     else run_heads_np<1>(s, g, post);
 }
+// the same GEMM with the skeleton denoiser's keypoint head in its epilogue (skel_head.h); the layer input is always the feed-forward's NSL slabs
+void run_skel_heads(hipStream_t s, const Args &g, bool post) {
+    if (!post) launch_glds<32, 32, 2, 2, 2, 64, A_LN, E_SKEL, 3, NSL>(s, g);
+    else if (g.T & 3) launch_glds<32, 32, 2, 2, 2, 64, A_LN, E_SKEL_POST_RAGGED, 3, NSL>(s, g);
+    else launch_glds<32, 32, 2, 2, 2, 64, A_LN, E_SKEL_POST, 3, NSL>(s, g);
+}
 // QKV projection: the LayerNorm+linear kernel of ffn.h
 // step_state != null (layer 0 of interdiff_mdm_forward_step): one thread of the launch does the step's sampler bookkeeping (philox.h)
 // pack_h2 != null: the split-f16 form (ffn_h2.h ln_linear_h2_kernel: tune[IDF_TUNE_FFN_MATH] == 1 and the layer's sa_in_pack_h2 is set)
@@ -1847,10 +1853,15 @@ struct StepPost {
     const float *table;
     int64_t *state, *ts;
 };
+// the skeleton model's head (interdiff_skeleton_mdm_*): null h = the two plain linears of idf_mdm_weights
+struct SkelHead {
+    const idf_skel_head *h;
+    const float *zero_pose_obj;
+};
 
 template <int MS>
 int mdm_forward_impl_t(const idf_mdm_weights *w, const float *memctx, const float *x, const int64_t *ts, int32_t B, int32_t T, float *x0,
-                       void *ws, size_t ws_bytes, void *stream, const StepPost &post, int32_t flags) {
+                       void *ws, size_t ws_bytes, void *stream, const StepPost &post, int32_t flags, const SkelHead &sk) {
     using ML = MemLay<MS>;
     constexpr int G_FRAG = ML::G_FRAG, G_H2 = ML::G_H2;
     const int mlen = idf_mem_len(w);
@@ -1868,7 +1879,7 @@ int mdm_forward_impl_t(const idf_mdm_weights *w, const float *memctx, const floa
     // The two ends of the step as split-f16 "step tail" launches (tail_h2.h): with the split arithmetic, the SMPL token width and the packer's plane
     // fragments.  flags (interdiff_mdm_forward_step_ex) then chain consecutive plain steps: IDF_STEP_EMBED_READY = the previous call's tail has already
     // written this step's embedding into the workspace, IDF_STEP_EMBED_NEXT = this call's tail writes the next step's.  Ignored otherwise.
-    const bool tail_h2 = tune[IDF_TUNE_FFN_MATH] != 0 && w->out_w_h2 != 0 && w->in_w_h2 != 0 && C == idf_tail_h2::CW && w->tail_h2_ok != 0 && idf_tail_h2::tail_exclusive_ok((T & 3) != 0);
+    const bool tail_h2 = !sk.h && tune[IDF_TUNE_FFN_MATH] != 0 && w->out_w_h2 != 0 && w->in_w_h2 != 0 && C == idf_tail_h2::CW && w->tail_h2_ok != 0 && idf_tail_h2::tail_exclusive_ok((T & 3) != 0);
     idf_tail_h2::TailArgs ta{};
     if (tail_h2) {
         ta.win = ar + w->in_w_h2; ta.in_b = ar + w->in_b; ta.temb = ar + w->temb_table; ta.pe = ar + w->pe; ta.ts = ts; ta.n_steps = w->n_steps;
@@ -1999,17 +2010,29 @@ int mdm_forward_impl_t(const idf_mdm_weights *w, const float *memctx, const floa
         if (post.x) {
             g.post_x = post.x; g.post_gt = post.gt; g.post_mask = post.mask; g.post_table = post.table; g.post_state = post.state;
         }
-        run_heads(s, g, u_np, post.x != nullptr);
+        if (sk.h) {      // keypoint head: the packed [pose | body] tiles, x0 = body | R(q) zero_pose_obj + trans | pose (skel_head.h)
+            g.W = ar + sk.h->out_w; g.bias = ar + sk.h->out_b; g.N = 32 * sk.h->n_tiles;
+            g.resid = sk.zero_pose_obj; g.Ka = sk.h->n_body; g.n_steps = sk.h->n_points;
+            run_skel_heads(s, g, post.x != nullptr);
+        } else {
+            run_heads(s, g, u_np, post.x != nullptr);
+        }
     }
     idf_prof_mark(-1, s);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
 }
 int mdm_forward_impl(const idf_mdm_weights *w, const float *memctx, const float *x, const int64_t *ts, int32_t B, int32_t T, float *x0,
-                     void *ws, size_t ws_bytes, void *stream, const StepPost &post, int32_t flags = 0) {
+                     void *ws, size_t ws_bytes, void *stream, const StepPost &post, int32_t flags = 0, const SkelHead &sk = SkelHead{}) {
     if (!w || w->mem_len < 0 || w->mem_len > MEMX || !idf_tune_reserved_clear(w)) return IDF_E_INVAL;
-    return idf_mem_len(w) == MEM ? mdm_forward_impl_t<MEM>(w, memctx, x, ts, B, T, x0, ws, ws_bytes, stream, post, flags)
-                                 : mdm_forward_impl_t<MEMX>(w, memctx, x, ts, B, T, x0, ws, ws_bytes, stream, post, flags);
+    return idf_mem_len(w) == MEM ? mdm_forward_impl_t<MEM>(w, memctx, x, ts, B, T, x0, ws, ws_bytes, stream, post, flags, sk)
+                                 : mdm_forward_impl_t<MEMX>(w, memctx, x, ts, B, T, x0, ws, ws_bytes, stream, post, flags, sk);
+}
+// a skeleton head the epilogue serves, on a handle of the matching token width
+bool skel_head_ok(const idf_mdm_weights *w, const idf_skel_head *h, const float *z) {
+    if (!w || !h || !z || h->reserved != 0 || !skel_head_shape_ok(h->n_body, h->n_points, h->n_tiles)) return false;
+    if (w->C != h->n_body + 3 * h->n_points + 7 || ((3 * h->n_points) & 3) || (reinterpret_cast<uintptr_t>(z) & 15)) return false;
+    return h->out_w > 0 && h->out_b > 0;
 }
 }  // namespace
 
@@ -2043,6 +2066,46 @@ extern "C" int interdiff_mdm_forward_step_ex(const idf_mdm_weights *w, const flo
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 3) return IDF_E_INVAL;
     if (!w || w->layer[0].is_qan) return IDF_E_INVAL;
     return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts}, flags);
+}
+
+// The skeleton denoiser (model/diffusion_skeleton.py MDM.forward): the forward above with the keypoint head (skel_head.h) in the last GEMM's epilogue
+extern "C" int interdiff_skeleton_mdm_forward(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, const float *x,
+                                              const int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, float *x0,
+                                              void *ws, size_t ws_bytes, void *stream) {
+    if (!x0 || !skel_head_ok(w, head, zero_pose_obj)) return IDF_E_INVAL;
+    if (!(T & 3) && (reinterpret_cast<uintptr_t>(x0) & 15)) return IDF_E_INVAL;
+    return mdm_forward_impl(w, memctx, x, ts, B, T, x0, ws, ws_bytes, stream, StepPost{}, 0, SkelHead{head, zero_pose_obj});
+}
+
+// ... and its fused plain step: the update covers all C channels of x, the derived keypoint channels included
+extern "C" int interdiff_skeleton_mdm_forward_step(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
+                                                   int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
+                                                   const uint8_t *mask, const float *table, int64_t *state, void *ws, size_t ws_bytes,
+                                                   void *stream) {
+    if (!x || !ts || !table || !state || (mask && !gt) || T <= 0 || !skel_head_ok(w, head, zero_pose_obj)) return IDF_E_INVAL;
+    if (!(T & 3) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 15 || (reinterpret_cast<uintptr_t>(mask) & 3))) return IDF_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 3) return IDF_E_INVAL;
+    if (w->layer[0].is_qan) return IDF_E_INVAL;
+    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts}, 0, SkelHead{head, zero_pose_obj});
+}
+
+// Encoder side of the skeleton model (MDM._get_embeddings): pc[b] = shapeEmbedding(zero_pose_obj[b]) by the register-staged fp32-MFMA GEMM
+// (K = 3 n_points is no multiple of the LDS-DMA kernel's chunk) into the tail of the workspace, then interdiff_mdm_encode
+extern "C" size_t interdiff_skeleton_mdm_encode_workspace_bytes(int32_t B, int32_t Tp) {
+    return interdiff_mdm_encode_workspace_bytes(B, Tp) + idf_align((size_t)(B > 0 ? B : 0) * D * sizeof(float));
+}
+extern "C" int interdiff_skeleton_mdm_encode(const idf_mdm_weights *w, const idf_skel_head *head, const float *zero_pose_obj,
+                                             const float *x_past, int32_t B, int32_t Tp, float *cond, void *ws, size_t ws_bytes,
+                                             void *stream) {
+    if (!x_past || !cond || !ws || B <= 0 || Tp <= 0 || !skel_head_ok(w, head, zero_pose_obj) || !w->has_encoder || head->shape_w <= 0 || head->shape_b <= 0) return IDF_E_INVAL;
+    if (ws_bytes < interdiff_skeleton_mdm_encode_workspace_bytes(B, Tp)) return IDF_E_NOMEM;
+    const size_t enc = interdiff_mdm_encode_workspace_bytes(B, Tp);
+    float *pc = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + enc);
+    Args g{};
+    g.A = zero_pose_obj; g.lda = 3 * head->n_points; g.K = 3 * head->n_points; g.W = w->arena + head->shape_w; g.bias = w->arena + head->shape_b;
+    g.C = pc; g.ldc = D; g.M = B; g.N = D; g.T = 1;
+    launch<32, 64, 2, 2, 32, A_PLAIN, E_BIAS>(idf_stream(stream), g);
+    return interdiff_mdm_encode(w, pc, x_past, B, Tp, cond, ws, enc, stream);
 }
 
 // 1 when interdiff_mdm_forward_step_ex honours its flags for this handle (split arithmetic selected, token width 144, plane fragments packed); 0: they are ignored

@@ -21,8 +21,10 @@ namespace idf_gemm {
 
 enum { A_PLAIN = 0, A_LN = 1, A_TOKT = 2, A_TOKT_R = 3 };      // A_TOKT_R: token gather for a token width that is no multiple of 4 (Args.Ka)
 constexpr bool is_tokt(int a) { return a == A_TOKT || a == A_TOKT_R; }
-enum { E_BIAS = 0, E_GELU = 1, E_RESID = 2, E_HEADS = 3, E_EMBED = 4, E_HEADS_POST = 5, E_HEADS_POST_RAGGED = 6 };      // 6: E_HEADS_POST for T % 4 != 0 (per-row update)
-constexpr bool is_post(int epi) { return epi == E_HEADS_POST || epi == E_HEADS_POST_RAGGED; }
+enum { E_BIAS = 0, E_GELU = 1, E_RESID = 2, E_HEADS = 3, E_EMBED = 4, E_HEADS_POST = 5, E_HEADS_POST_RAGGED = 6,      // 6: E_HEADS_POST for T % 4 != 0 (per-row update)
+       E_SKEL = 7, E_SKEL_POST = 8, E_SKEL_POST_RAGGED = 9 };      // the skeleton denoiser's keypoint head (skel_head.h): x0 written out | fused step | fused step, T % 4 != 0
+constexpr bool is_skel(int epi) { return epi == E_SKEL || epi == E_SKEL_POST || epi == E_SKEL_POST_RAGGED; }
+constexpr bool is_post(int epi) { return epi == E_HEADS_POST || epi == E_HEADS_POST_RAGGED || epi == E_SKEL_POST || epi == E_SKEL_POST_RAGGED; }
 
 struct Args {
     const float *A;
@@ -35,7 +37,7 @@ struct Args {
     float *C;
     int ldc, M, N;
     float *xn_out;                  // A_LN: normalised rows [M][256] written by the blockIdx.y == 0 column (nullable)
-    const float *resid;             // E_RESID, leading dimension ldc
+    const float *resid;             // E_RESID, leading dimension ldc.  E_SKEL*: zero_pose_obj [B][n_points][3], with Ka = n_body and n_steps = n_points (skel_head.h)
     int T;                          // tokens per clip (A_TOKT, E_HEADS, E_EMBED)
     const int64_t *ts;              // E_EMBED: timestep per clip
     const float *temb, *pe;         // E_EMBED: [n_steps][N], [max_T][N]
@@ -293,6 +295,10 @@ __device__ __forceinline__ void epilogue_rows(const Args &g, float *cs, const f3
         if (gr < g.M && gc < g.N) idf_store16_wt(g.C + (size_t)gr * g.ldc + gc, ld4(cs + row * CS + c4 * 4));      // read next by other XCDs: write through
     }
 }
+
+}  // namespace idf_gemm
+#include "skel_head.h"
+namespace idf_gemm {
 
 template <int BM, int BN, int WM, int WN, int KC, int APRO, int EPI, int NP = 1>
 __global__ __launch_bounds__(WM *WN * 64) void gemm_kernel(const Args g) {
@@ -581,8 +587,12 @@ __global__ __launch_bounds__(WM *WN *KS * 64) void gemm_glds_kernel(const Args g
     if constexpr (EPI == E_RESID) {
         if (ks == 0) load_resid<TM, TN>(g, rres, m0 + wm * TM * 16 + kq * 4, n0 + wn * TN * 16 + li);
     }
-    PostOperands<is_post(EPI) ? TM : 1, is_post(EPI) ? TN : 1> po;
-    if constexpr (is_post(EPI)) {
+    PostOperands<is_post(EPI) && !is_skel(EPI) ? TM : 1, is_post(EPI) && !is_skel(EPI) ? TN : 1> po;
+    SkelPre skp;
+    if constexpr (is_skel(EPI)) {
+        static_assert(!is_skel(EPI) || (BM == 32 && BN == 32 && NW == 8 && SMEM >= 32 * SKH_CS + 32 * SKH_ZMAX), "the keypoint head's tile: 32 x 32, 512 threads");
+        skel_prefetch<EPI>(g, skp, m0, nt_, tid);
+    } else if constexpr (is_post(EPI)) {
         if (ks == 0) post_prefetch<TM, TN, EPI == E_HEADS_POST_RAGGED>(g, po, m0 + wm * TM * 16 + kq * 4, n0 + wn * TN * 16 + li);
     }
     if constexpr (APRO == A_LN) {
@@ -693,6 +703,17 @@ __global__ __launch_bounds__(WM *WN *KS * 64) void gemm_glds_kernel(const Args g
         static_assert(BM * (BN + 4) <= (SMEM > RED ? SMEM : RED), "C tile must fit the operand buffers");
         if constexpr (KS > 1) __syncthreads();                    // the split-K partials have been read
         epilogue_rows<BM, BN, TM, TN, EPI, NW * 64>(g, smem, acc, rres, bvs, ks == 0, wm * TM * 16, wn * TN * 16, kq, li, m0, n0, tid);
+    } else if constexpr (is_skel(EPI)) {
+        __syncthreads();                  // the k-loop's and the split-K reduction's LDS reads are done: the buffer takes the x0 tile
+        if (ks == 0) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) smem[((wm * TM + i) * 16 + kq * 4 + r) * SKH_CS + (wn * TN + j) * 16 + li] = acc[i][j][r] + bvs[j];
+        }
+        skel_epilogue<EPI>(g, smem, smem + 32 * SKH_CS, skp, m0, nt_, tid);
     } else {
         if constexpr (is_post(EPI)) {
             if (ks == 0) epilogue_post<TM, TN, EPI == E_HEADS_POST_RAGGED>(g, acc, bvs, po, m0 + wm * TM * 16 + kq * 4, n0 + wn * TN * 16 + li);

@@ -120,6 +120,8 @@ class GaussianDiffusion:
             assert img.shape == m.shape == y['inpainted_motion'].shape
             mu8, gc = (m if m.dtype == torch.uint8 else m.view(torch.uint8)).contiguous(), y['inpainted_motion'].contiguous()
         cond = y['cond']
+        # a denoiser that takes a per-clip constant beside y (the skeleton model's zero_pose_obj [B,12,3], a TOP-LEVEL model_kwargs entry: eval_skeleton.py:126)
+        zpo = model_kwargs.get('zero_pose_obj')
         # The captured graphs read the sample's inputs from buffers this cache entry OWNS (x, gt, mask, cond): one capture per
         # (denoiser, shape) then serves every sample -- an eval loop or an autoregressive rollout feeds a new cond / gt per sample
         # and must not pay a re-capture (57 denoiser forwards) each time.
@@ -127,6 +129,8 @@ class GaussianDiffusion:
         # context, so they must die with it (a cache keyed by id(model) would replay freed memory once the id is recycled).
         cache = model.__dict__.setdefault('_graph_cache', {})
         key = (self._uid, tuple(img.shape), has_mask, tuple(cond.shape), model.ffn_graph_key(rows) if hasattr(model, 'ffn_graph_key') else 0)    # the captured launches bake the feed-forward kernel choice in
+        if zpo is not None:
+            key += (tuple(zpo.shape),)
         st = cache.get(key)
         if st is None:
             st = SimpleNamespace(x=torch.zeros_like(img), x0=torch.empty_like(img), ts=torch.zeros(B, dtype=torch.int64, device=dev),
@@ -134,6 +138,10 @@ class GaussianDiffusion:
                                  gt=torch.empty_like(img) if has_mask else None,
                                  mask=torch.empty(img.shape, dtype=torch.uint8, device=dev) if has_mask else None, graphs={})
             st.kwargs = {'y': {'cond': st.cond}}              # what the captured denoiser calls see
+            st.zpo = None
+            if zpo is not None:
+                st.zpo = torch.empty(zpo.shape, dtype=torch.float32, device=dev)
+                st.kwargs['zero_pose_obj'] = st.zpo
             if len(cache) >= MAX_GRAPH_SHAPES:
                 # drop this cache's graphs, the buffers IT allocated (x, x0, cond, chain and hook workspaces) and the entries of the denoiser's
                 # per-shape pools that were created FOR these graphs (st.pool_keys, recorded below); pool entries that existed before -- a
@@ -149,6 +157,9 @@ class GaussianDiffusion:
         else:
             fresh = False
         st.cond.copy_(cond)
+        if zpo is not None:
+            st.zpo.copy_(zpo)
+        zkw = lambda ch: {} if st.zpo is None else {'zero_pose_obj': st.zpo[ch.sl]}      # a chain's clips of it
         if has_mask:
             st.gt.copy_(gc)
             st.mask.copy_(mu8)
@@ -219,7 +230,7 @@ class GaussianDiffusion:
                     ch.stream.wait_stream(cur)
                     with torch.cuda.stream(ch.stream):
                         for i in range(k):
-                            model.forward_step(ch.x, ch.ts, table, ch.state, gt=ch.gt, mask=ch.mask, memctx=ch.memctx, ws=ch.ws, batch_rows=rows, **link(i))
+                            model.forward_step(ch.x, ch.ts, table, ch.state, gt=ch.gt, mask=ch.mask, memctx=ch.memctx, ws=ch.ws, batch_rows=rows, **link(i), **zkw(ch))
                 for ch in st.chains:
                     cur.wait_stream(ch.stream)
             else:
@@ -353,6 +364,7 @@ class GaussianDiffusion:
         lib = _lib.load()
         dev, B = st.x.device, st.x.shape[0]
         chains, h = st.chains, st.x.shape[0] // len(st.chains)
+        zkw = lambda ch: {} if st.zpo is None else {'zero_pose_obj': st.zpo[ch.sl]}
         end = t_start - todo
         # ---- the schedule, the same for every chain: plain runs in captured block sizes, hook steps, dump points
         prog, i, it = [], t_start, 0
@@ -387,12 +399,12 @@ class GaussianDiffusion:
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
                         for _ in range(k):
-                            model.forward_step(ch.x, ch.ts, table, ch.state, gt=ch.gt, mask=ch.mask, memctx=ch.memctx, ws=ch.ws, batch_rows=rows)
+                            model.forward_step(ch.x, ch.ts, table, ch.state, gt=ch.gt, mask=ch.mask, memctx=ch.memctx, ws=ch.ws, batch_rows=rows, **zkw(ch))
                     ch.graphs[k] = g
             if need_fwd and 'fwd' not in ch.graphs:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    model(ch.x, ch.ts, out=ch.x0, memctx=ch.memctx, ws=ch.ws, batch_rows=rows)
+                    model(ch.x, ch.ts, out=ch.x0, memctx=ch.memctx, ws=ch.ws, batch_rows=rows, **zkw(ch))
                 ch.graphs['fwd'] = g
         for c, ch in enumerate(chains):
             ch.state.copy_(torch.tensor([t_start, 0, int(seed) & 0x7FFFFFFFFFFFFFFF, 0, 0, 0, elem0 + c * ch.x.numel(), 0], dtype=torch.int64))

@@ -332,8 +332,9 @@ class _Arena:
         return torch.from_numpy(np.concatenate(self.parts)).to(device)
 
 
-def pack_mdm_weights(sd, device, n_steps=1000, max_T=512, rotary=ROTARY_DEFAULT):
-    """state_dict (reference key names, tensors or arrays) -> (MdmWeights struct, arena tensor)."""
+def pack_mdm_weights(sd, device, n_steps=1000, max_T=512, rotary=ROTARY_DEFAULT, extra=None):
+    """state_dict (reference key names, tensors or arrays) -> (MdmWeights struct, arena tensor).  ``extra``: dict name -> array of further
+    operands for the same arena (a model built on this one, skeleton.py); each value is replaced by its offset in floats."""
     g = lambda k: _np(sd[k]).astype(np.float32)
     ar = _Arena()
     w = _lib.MdmWeights()
@@ -432,6 +433,9 @@ def pack_mdm_weights(sd, device, n_steps=1000, max_T=512, rotary=ROTARY_DEFAULT)
             for k in range(2):
                 ly.ln_w[k] = ar.add(g(p + 'norm%d.weight' % (k + 1)))
                 ly.ln_b[k] = ar.add(g(p + 'norm%d.bias' % (k + 1)))
+    if extra is not None:
+        for k in list(extra):
+            extra[k] = ar.add(extra[k])
     arena = ar.tensor(device)
     w.arena = arena.data_ptr()
     return w, arena
@@ -465,10 +469,10 @@ class MDM:
     graph_safe = True        # forward() enqueues kernels only (no allocation / sync once warmed up): hipGraph-capturable
     accepts_batch_rows = True        # forward() / forward_step() take ``batch_rows=`` (the sampler's shard / chain plumbing)
 
-    def __init__(self, state_dict, device='cuda', n_steps=1000, rotary=ROTARY_DEFAULT):
+    def __init__(self, state_dict, device='cuda', n_steps=1000, rotary=ROTARY_DEFAULT, extra=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
-        self.w, self.arena = pack_mdm_weights(state_dict, self.device, n_steps=n_steps, rotary=rotary)
+        self.w, self.arena = pack_mdm_weights(state_dict, self.device, n_steps=n_steps, rotary=rotary, extra=extra)
         self._mem_key, self._mem_cond, self._memctx, self._ws = None, None, None, None
         self._ws_shape, self._ws_pool, self._memctx_pool = None, {}, {}
         self._memlen_of = {}                      # folded-memory buffer address -> (memory length, floats): the length travels with the buffer (_bind_memory)
@@ -716,6 +720,15 @@ class MDM:
     def forward(self, x, timesteps, y=None, out=None, memctx=None, ws=None, batch_rows=None):
         """``memctx`` / ``ws``: caller-owned folded memory and workspace, as in ``forward_step`` (then ``y`` is not consulted).
         ``batch_rows``: B * T of the batch this call is a chain of (default: this call's own)."""
+        return self._forward(x, timesteps, y, out, memctx, ws, batch_rows)
+
+    def _launch_forward(self, memctx, x, ts, B, T, out, ws, **head):
+        """The library call of a forward (a model with another head overrides it: skeleton.py)."""
+        _lib.check(self.lib.interdiff_mdm_forward(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                  _lib.dptr(ts, torch.int64), B, T, _lib.dptr(out, torch.float32),
+                                                  _lib.dptr(ws), ws.numel(), _lib.stream()), 'mdm_forward')
+
+    def _forward(self, x, timesteps, y, out, memctx, ws, batch_rows, **head):
         B, one, Cc, T = x.shape
         self._pick_ffn_tile(batch_rows or B * T, B * T)
         if memctx is None:
@@ -734,9 +747,7 @@ class MDM:
             out = torch.empty_like(x)
         if ws is None:
             ws = self._workspace(B, T)
-        _lib.check(self.lib.interdiff_mdm_forward(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
-                                                  _lib.dptr(ts, torch.int64), B, T, _lib.dptr(out, torch.float32),
-                                                  _lib.dptr(ws), ws.numel(), _lib.stream()), 'mdm_forward')
+        self._launch_forward(memctx, x, ts, B, T, out, ws, **head)
         return out
 
     __call__ = forward
@@ -760,6 +771,17 @@ class MDM:
         caller-owned folded memory (``prepare_memory(cond, into=)``) and workspace (``workspace_bytes(B, T)`` bytes) instead of the
         model's -- what lets two chains of one sample run side by side; ``batch_rows`` then names the whole batch's B * T (see
         ``_pick_ffn_tile``)."""
+        return self._forward_step(x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows,
+                                  (_lib.STEP_EMBED_READY if embed_ready else 0) | (_lib.STEP_EMBED_NEXT if embed_next else 0))
+
+    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, **head):
+        """The library call of a fused plain step (a model with another head overrides it: skeleton.py)."""
+        _lib.check(self.lib.interdiff_mdm_forward_step_ex(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                          _lib.dptr(timesteps, torch.int64), B, T, _lib.dptr(gt, allow_none=True),
+                                                          _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(state),
+                                                          _lib.dptr(ws), ws.numel(), flags, _lib.stream()), 'mdm_forward_step')
+
+    def _forward_step(self, x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows, flags, **head):
         B, one, Cc, T = x.shape
         self._pick_ffn_tile(batch_rows or B * T, B * T)
         if one != 1 or Cc != self.w.C or not x.is_contiguous():
@@ -772,11 +794,7 @@ class MDM:
         self._bind_memory(memctx, B)
         if ws is None:
             ws = self._workspace(B, T)
-        flags = (_lib.STEP_EMBED_READY if embed_ready else 0) | (_lib.STEP_EMBED_NEXT if embed_next else 0)
-        _lib.check(self.lib.interdiff_mdm_forward_step_ex(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
-                                                          _lib.dptr(timesteps, torch.int64), B, T, _lib.dptr(gt, allow_none=True),
-                                                          _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(state),
-                                                          _lib.dptr(ws), ws.numel(), flags, _lib.stream()), 'mdm_forward_step')
+        self._launch_step(memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, **head)
         return x
 
 

@@ -1,4 +1,6 @@
-"""HO-GCN skeleton mode (eval_skeleton.py): the correction predictor ``ObjProjector.sample``
+"""HO-GCN skeleton mode (eval_skeleton.py): the denoiser ``MDM`` of model/diffusion_skeleton.py (``SkeletonMDM``: conditioning
+encoder with the shape embedding, feed-forward width 256, keypoint head ``calc_obj_pred`` inside the heads GEMM; csrc/skel_head.h),
+the sampling glue ``sample_once_proj`` (eval_skeleton.py:114-142), the correction predictor ``ObjProjector.sample``
 (model/correction_skeleton.py:84-137), the correction hook ``denoised_fn`` (eval_skeleton.py:82-111) and the metrics
 ``calc_metric_single`` (:46-68) on ``interdiff_skeleton_*`` (csrc/skeleton.hip).
 
@@ -19,6 +21,7 @@ import torch
 from . import _lib
 from .correction import correction_gate
 from .objprojector import dct_matrices, _fold, _np
+from . import mdm as _mdm
 
 STACKS = ('st_gcnns_relative', 'st_gcnns', 'st_gcnns_all')
 N_PRE, N_JOINTS, N_OBJ = 20, 21, 12
@@ -212,3 +215,148 @@ def skeleton_metrics(body_pred, body_gt, obj_pred, obj_gt, pose_pred, pose_gt, f
     _check(lib.interdiff_skeleton_metrics(*[_lib.dptr(a) for a in args], T, B, from_frame, _lib.dptr(out), _lib.stream()), 'skeleton_metrics')
     v = out.cpu().tolist()
     return dict(mpjpe_h=v[0], mpjpe_o=v[1], translation_error=v[2], rotation_error=v[3])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the skeleton denoiser (model/diffusion_skeleton.py MDM)
+# ---------------------------------------------------------------------------------------------------------------
+HEAD_POSE, HEAD_BODY = 7, 25                     # rows of a 32-row column tile of the packed head: pose first, then body (csrc/skel_head.h)
+
+
+def pad_ffn_width(w1, b1, w2, width=_mdm.FF):
+    """linear1 [ff,256] / [ff], linear2 [256,ff] of a narrower feed-forward block -> the 1024-wide matrices the packed streams are built
+    from: the added hidden units have zero weight and zero bias, gelu(0) = 0, and they meet zero columns of linear2 -- they contribute
+    exactly nothing (csrc/ffn.h relies on the same for units 1024..1039), so every kernel and range proof of the 1024-wide block holds."""
+    w1, b1, w2 = (np.asarray(a, np.float32) for a in (w1, b1, w2))
+    ff = w1.shape[0]
+    if ff > width or ff % 16 or ff < 16 or w1.shape != (ff, _mdm.D) or w2.shape != (_mdm.D, ff) or b1.shape != (ff,):
+        raise ValueError('feed-forward width %d: need a multiple of 16, at most %d, with linear1 [ff,%d] and linear2 [%d,ff]' % (ff, width, _mdm.D, _mdm.D))
+    w1p, b1p, w2p = np.zeros((width, _mdm.D), np.float32), np.zeros(width, np.float32), np.zeros((_mdm.D, width), np.float32)
+    w1p[:ff], b1p[:ff], w2p[:, :ff] = w1, b1, w2
+    return w1p, b1p, w2p
+
+
+def pack_skeleton_head(body_w, body_b, obj_w, obj_b):
+    """bodyFinalLinear [n_body,256] / [n_body], objFinalLinear [7,256] / [7] -> (W [32 tiles][256], b [32 tiles], tiles): every 32-row
+    column tile of the heads GEMM starts with the 7 pose rows and carries 25 body rows (zero past n_body), so that the workgroup of any
+    tile holds the pose of its token rows (csrc/skel_head.h)."""
+    body_w, body_b, obj_w, obj_b = (np.asarray(a, np.float32) for a in (body_w, body_b, obj_w, obj_b))
+    n_body = body_w.shape[0]
+    if obj_w.shape != (HEAD_POSE, _mdm.D) or body_w.shape[1] != _mdm.D:
+        raise ValueError('objFinalLinear must be [7,%d] (translation | quaternion xyzw)' % _mdm.D)
+    tiles = -(-n_body // HEAD_BODY)
+    W, b = np.zeros((32 * tiles, _mdm.D), np.float32), np.zeros(32 * tiles, np.float32)
+    for t in range(tiles):
+        W[32 * t:32 * t + HEAD_POSE], b[32 * t:32 * t + HEAD_POSE] = obj_w, obj_b
+        n = min(HEAD_BODY, n_body - HEAD_BODY * t)
+        W[32 * t + HEAD_POSE:32 * t + HEAD_POSE + n] = body_w[HEAD_BODY * t:HEAD_BODY * t + n]
+        b[32 * t + HEAD_POSE:32 * t + HEAD_POSE + n] = body_b[HEAD_BODY * t:HEAD_BODY * t + n]
+    return W, b, tiles
+
+
+def skeleton_state_dict_for_pack(state_dict):
+    """The skeleton model's state_dict in the shape ``mdm.pack_mdm_weights`` packs: feed-forward blocks zero-padded to width 1024
+    (``pad_ffn_width``), objEmbedding with 7 zero columns for the pose channels the model does not embed (diffusion_skeleton.py:236-238).
+    The two head matrices stay as they are (their packed form is ``pack_skeleton_head``).  Returns (dict, ff_size)."""
+    sd = {k: _np(v).astype(np.float32) for k, v in _strip(state_dict).items() if not k.endswith('.pe')}
+    ff = sd['decoder.layers.0.linear1.weight'].shape[0]
+    for k in [k for k in sd if k.endswith('.linear1.weight')]:
+        p = k[:-len('linear1.weight')]
+        sd[p + 'linear1.weight'], sd[p + 'linear1.bias'], sd[p + 'linear2.weight'] = pad_ffn_width(sd[p + 'linear1.weight'], sd[p + 'linear1.bias'], sd[p + 'linear2.weight'])
+    sd['objEmbedding.weight'] = np.concatenate([sd['objEmbedding.weight'], np.zeros((_mdm.D, HEAD_POSE), np.float32)], axis=1)
+    return sd, ff
+
+
+class SkeletonMDM(_mdm.MDM):
+    """Drop-in for model/diffusion_skeleton.py ``MDM`` at the sampler seam: ``model(x, t, **{'y': {'cond': ...}, 'zero_pose_obj': z})``
+    with x [B,1,106,T].  ``MDM``'s decoder, encoder, memory and workspace machinery on the padded weights; the last launch of a forward
+    carries the keypoint head (``interdiff_skeleton_mdm_forward`` / ``_forward_step``)."""
+
+    def __init__(self, state_dict, device='cuda', n_steps=1000, rotary=_mdm.ROTARY_DEFAULT):
+        sd, self.ff_size = skeleton_state_dict_for_pack(state_dict)
+        self.n_body, self.n_points = sd['bodyEmbedding.weight'].shape[1], sd['shapeEmbedding.weight'].shape[1] // 3
+        hw, hb, tiles = pack_skeleton_head(sd['bodyFinalLinear.weight'], sd['bodyFinalLinear.bias'], sd['objFinalLinear.weight'], sd['objFinalLinear.bias'])
+        extra = dict(out_w=hw, out_b=hb, shape_w=sd['shapeEmbedding.weight'], shape_b=sd['shapeEmbedding.bias'])
+        super().__init__(sd, device=device, n_steps=n_steps, rotary=rotary, extra=extra)
+        self.w.C = self.n_body + 3 * self.n_points + HEAD_POSE          # (the packer counted the embedding's columns: the same number)
+        self.head = _lib.SkelHead(n_body=self.n_body, n_points=self.n_points, n_tiles=tiles, reserved=0, **extra)
+        self._zero = None
+
+    def _zpo(self, zero_pose_obj, B):
+        if zero_pose_obj is None:
+            raise ValueError("the skeleton denoiser needs model_kwargs['zero_pose_obj'] [B,%d,3]" % self.n_points)
+        if tuple(zero_pose_obj.shape) != (B, self.n_points, 3):
+            raise ValueError('zero_pose_obj must be [%d,%d,3]' % (B, self.n_points))
+        return zero_pose_obj if (zero_pose_obj.dtype == torch.float32 and zero_pose_obj.is_contiguous()) else zero_pose_obj.contiguous().float()
+
+    def forward(self, x, timesteps, zero_pose_obj=None, y=None, out=None, memctx=None, ws=None, batch_rows=None):
+        """``MDM.forward(x, timesteps, zero_pose_obj, y=)`` (diffusion_skeleton.py:250-257); the other operands as ``mdm.MDM.forward``."""
+        return self._forward(x, timesteps, y, out, memctx, ws, batch_rows, z=self._zpo(zero_pose_obj, x.shape[0]))
+
+    __call__ = forward
+
+    def _launch_forward(self, memctx, x, ts, B, T, out, ws, z):
+        _check(self.lib.interdiff_skeleton_mdm_forward(C.byref(self.w), C.byref(self.head), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                       _lib.dptr(ts, torch.int64), _lib.dptr(z), B, T, _lib.dptr(out, torch.float32),
+                                                       _lib.dptr(ws), ws.numel(), _lib.stream()), 'skeleton_mdm_forward')
+
+    @property
+    def step_chaining(self):
+        return False                              # the chained step tail is the split-f16 kernel of the 144-channel model (csrc/tail_h2.h)
+
+    def forward_step(self, x, timesteps, table, state, gt=None, mask=None, y=None, zero_pose_obj=None, memctx=None, ws=None, batch_rows=None):
+        """One plain reverse step with the update over all 106 channels inside the heads GEMM (interdiff_skeleton_mdm_forward_step);
+        operands as ``mdm.MDM.forward_step``."""
+        return self._forward_step(x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows, 0, z=self._zpo(zero_pose_obj, x.shape[0]))
+
+    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, z):
+        _check(self.lib.interdiff_skeleton_mdm_forward_step(C.byref(self.w), C.byref(self.head), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                            _lib.dptr(timesteps, torch.int64), _lib.dptr(z), B, T, _lib.dptr(gt, allow_none=True),
+                                                            _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(state),
+                                                            _lib.dptr(ws), ws.numel(), _lib.stream()), 'skeleton_mdm_forward_step')
+
+    def arithmetic_report(self, device_verdicts=True):
+        rep = super().arithmetic_report(device_verdicts)
+        rep['ff_size'] = self.ff_size
+        return rep
+
+    def _get_embeddings(self, body_gt, obj_gt, pose_gt, zero_pose_obj, past_len=10, batch_clips=None):
+        """``MDM._get_embeddings`` (model/diffusion_skeleton.py:194-215): body_gt [T,B,21,3], obj_gt [T,B,12,3], pose_gt [T,B,7],
+        zero_pose_obj [B,12,3] -> (cond [past_len,B,256], gt [T,B,106])."""
+        if not self.w.has_encoder:
+            raise RuntimeError('this state_dict has no encoder weights')
+        T, B = body_gt.shape[:2]
+        z = self._zpo(zero_pose_obj, B)
+        gt = torch.cat([body_gt.reshape(T, B, -1).float(), obj_gt.reshape(T, B, -1).float(), pose_gt.float()], dim=2)      # [T,B,106]
+        if gt.shape[2] != self.w.C:
+            raise ValueError('expected body [T,B,%d,3], obj [T,B,%d,3], pose [T,B,7]' % (self.n_body // 3, self.n_points))
+        x_past = gt[:past_len].permute(1, 2, 0).unsqueeze(1).contiguous()                                # [B,1,106,past]
+        self._pick_ffn_tile((batch_clips or B) * past_len, B * past_len)
+        ws = torch.empty(self.lib.interdiff_skeleton_mdm_encode_workspace_bytes(B, past_len), dtype=torch.uint8, device=self.device)
+        cond = torch.empty(past_len, B, _mdm.D, dtype=torch.float32, device=self.device)
+        _check(self.lib.interdiff_skeleton_mdm_encode(C.byref(self.w), C.byref(self.head), _lib.dptr(z), _lib.dptr(x_past), B, past_len,
+                                                      _lib.dptr(cond), _lib.dptr(ws), ws.numel(), _lib.stream()), 'skeleton_mdm_encode')
+        return cond, gt
+
+
+def sample_once_proj(batch, model, diffusion, obj_model=None, seed=None, past_len=10, device=None, **loop_kw):
+    """``sample_once_proj`` of eval_skeleton.py:114-142 (``obj_model=None``: eval_skeleton_no_correction.py's, identity hook).  ``batch``
+    = (body [B,T,21,3], obj keypoints [B,T,12,3], pose [B,T,7], zero_pose_obj [B,12,3]) as the dataset yields it; ``obj_model``: a
+    ``SkeletonObjProjector`` (or a ready ``HipSkeletonCorrection``).  Returns (obj_pred, body_pred, pose_pred, obj_gt, body_gt, pose_gt),
+    each [T,B,*] -- what ``skeleton_metrics`` takes.  ``loop_kw`` goes to ``p_sample_loop`` (``noise=``, ``step_noise=``, ``use_graph=``)."""
+    dev = torch.device(device) if device is not None else model.device
+    body_gt, obj_gt, pose_gt = (batch[i].transpose(0, 1).float().to(dev) for i in range(3))
+    zero_pose_obj = batch[3].float().to(dev).contiguous()
+    cond, gt = model._get_embeddings(body_gt, obj_gt, pose_gt, zero_pose_obj, past_len=past_len)
+    gt = gt.permute(1, 2, 0).unsqueeze(1).contiguous()                                                   # [B,1,106,T]
+    mask = torch.ones_like(gt, dtype=torch.bool)
+    mask[..., past_len:] = False
+    kw = {'y': {'cond': cond, 'inpainted_motion': gt, 'inpainting_mask': mask}, 'zero_pose_obj': zero_pose_obj}
+    hook = None
+    if obj_model is not None:
+        hook = obj_model if isinstance(obj_model, HipSkeletonCorrection) else HipSkeletonCorrection(obj_model, device=dev)
+    sample = diffusion.p_sample_loop(model, tuple(gt.shape), clip_denoised=False, model_kwargs=kw, denoised_fn=hook, seed=seed, **loop_kw)
+    nb, no = model.n_body, 3 * model.n_points
+    body_pred, obj_pred, pose_pred = torch.split(sample.squeeze(1).permute(2, 0, 1).contiguous(), [nb, no, HEAD_POSE], dim=2)
+    body_g, obj_g, pose_g = torch.split(gt.squeeze(1).permute(2, 0, 1).contiguous(), [nb, no, HEAD_POSE], dim=2)
+    return obj_pred, body_pred, pose_pred, obj_g, body_g, pose_g

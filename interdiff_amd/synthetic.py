@@ -91,6 +91,75 @@ def mdm_state_dict(seed=233, d=256, ff=1024, n_body=135, n_obj=9, n_queries=10):
     return sd
 
 
+def skeleton_mdm_state_dict(seed=1106, ff=256, d=256, n_joints=21, n_points=12, n_queries=10, quat_scale=0.15):
+    """Weights of the HO-GCN skeleton denoiser (model/diffusion_skeleton.py ``MDM``: key names and shapes, ``--ff_size 256`` as both
+    skeleton eval scripts build it): bodyEmbedding [d, 63], objEmbedding / shapeEmbedding [d, 36], decoder and encoder of 8 layers
+    [std, QaN x6, std], bodyFinalLinear [63, d], objFinalLinear [7, d] (translation xyz | quaternion xyzw).  Its own draw order
+    (``mdm_state_dict`` is pinned by goldens and stays as it is).  A trained head emits near-unit quaternions; a default-initialised one
+    does not, and calc_obj_pred's 2 / (q . q) is ill-conditioned near zero: the four quaternion rows are scaled by ``quat_scale`` and
+    their bias is the identity rotation (0, 0, 0, 1)."""
+    rs = np.random.RandomState(seed)
+    sd = {}
+
+    def linear(name, out_f, in_f):
+        b = 1.0 / np.sqrt(in_f)
+        sd[name + '.weight'] = _f32(rs.uniform(-b, b, (out_f, in_f)))
+        sd[name + '.bias'] = _f32(rs.uniform(-b, b, (out_f,)))
+
+    def norm(name):
+        sd[name + '.weight'] = _f32(1.0 + 0.1 * rs.standard_normal(d))
+        sd[name + '.bias'] = _f32(0.1 * rs.standard_normal(d))
+
+    def mha(name):
+        b = np.sqrt(6.0 / (d + 3 * d))
+        sd[name + '.in_proj_weight'] = _f32(rs.uniform(-b, b, (3 * d, d)))
+        sd[name + '.in_proj_bias'] = _f32(0.02 * rs.standard_normal(3 * d))
+        linear(name + '.out_proj', d, d)
+
+    def stack(prefix, norms, cross):
+        for l in range(N_LAYERS):
+            p = '%s.layers.%d' % (prefix, l)
+            if l in QAN_LAYERS:
+                sd[p + '.queries'] = _f32(rs.normal(-1.0 / np.sqrt(d), 1.0 / np.sqrt(d), (n_queries, d)))
+                sd[p + '.wk'] = _f32(rs.normal(-1.0 / np.sqrt(n_queries), 1.0 / np.sqrt(n_queries), (n_queries, 1)))
+            else:
+                mha(p + '.self_attn')
+            if cross:
+                mha(p + '.multihead_attn')
+            linear(p + '.linear1', ff, d)
+            linear(p + '.linear2', d, ff)
+            for k in norms:
+                norm(p + '.norm%d' % k)
+
+    linear('bodyEmbedding', d, 3 * n_joints)
+    linear('shapeEmbedding', d, 3 * n_points)
+    linear('objEmbedding', d, 3 * n_points)
+    linear('embedTimeStep.time_embed.0', d, d)
+    linear('embedTimeStep.time_embed.2', d, d)
+    stack('encoder', (1, 2), False)
+    stack('decoder', (1, 2, 3), True)
+    linear('bodyFinalLinear', 3 * n_joints, d)
+    linear('objFinalLinear', 7, d)
+    sd['objFinalLinear.weight'][3:] *= np.float32(quat_scale)
+    sd['objFinalLinear.bias'][3:] = (0.0, 0.0, 0.0, 1.0)
+    return sd
+
+
+def make_skeleton_batch(seed=7400, B=3, T=20, n_joints=21, n_points=12):
+    """A skeleton-mode batch in the dataset's layout (data/dataset_skeleton.py; eval_skeleton.py:117-120): body [B,T,21,3], object
+    keypoints [B,T,12,3] = R(q_t) zero_pose + trans_t, pose [B,T,7] (translation | unit quaternion xyzw), zero_pose_obj [B,12,3]."""
+    rs = np.random.RandomState(seed)
+    body = 0.4 * rs.standard_normal((B, 1, n_joints, 3)) + np.cumsum(0.02 * rs.standard_normal((B, T, n_joints, 3)), axis=1)
+    zero = 0.3 * rs.standard_normal((B, n_points, 3))
+    trans = 0.3 * rs.standard_normal((B, 1, 3)) + np.cumsum(0.01 * rs.standard_normal((B, T, 3)), axis=1)
+    aa = 0.8 * rs.standard_normal((B, 1, 3)) + np.cumsum(0.03 * rs.standard_normal((B, T, 3)), axis=1)
+    R = aa_to_matrix(aa)                                                        # [B,T,3,3]
+    obj = np.einsum('btij,bkj->btki', R, zero) + trans[:, :, None]
+    th = np.linalg.norm(aa, axis=-1, keepdims=True)
+    quat = np.concatenate([aa / np.maximum(th, 1e-12) * np.sin(th / 2), np.cos(th / 2)], axis=-1)      # xyzw
+    return dict(body=_f32(body), obj=_f32(obj), pose=_f32(np.concatenate([trans, quat], axis=-1)), zero_pose_obj=_f32(zero))
+
+
 # shared-MLP channel plans of PointNet2Encoder(c_in=1, c_out=256, num_keypoints=1): +3 = use_xyz (model/layers.py:118-138)
 PC_MLPS = (((1 + 3, 16, 16, 32), (1 + 3, 32, 32, 64)), ((96 + 3, 64, 64, 128), (96 + 3, 64, 96, 128)))
 
