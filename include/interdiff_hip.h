@@ -566,6 +566,45 @@ int interdiff_debug_lds_sentinel(uint32_t *out, int32_t n_wg, int32_t spin, void
 int interdiff_debug_f16_aggressor(const float *src, size_t n_floats, float *sink, int32_t iters, int32_t grid, int32_t with_loads, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Checkpoint scoring (csrc/losses.hip): the forward, scoring side of interdiff/train_diffusion_smpl.py.  Forward only.
+ * Additive entries: no existing signature or struct layout changes, so interdiff_abi_version() stays what it was.
+ * Term order everywhere (the reference's dict order): index = 4 * kind + group,
+ *   kind  0 past, 1 v_past, 2 future, 3 v_future;   group 0 body_rot, 1 body_nonrot, 2 obj_rot, 3 obj_nonrot.
+ *
+ *  interdiff_q_sample           replaces GaussianDiffusion.q_sample (diffusion/gaussian_diffusion.py:233-250) with a per-clip timestep,
+ *      and the inpainting of x_t in training_losses (:1264-1268).  x_t, x0, noise, gt [B][per_clip], mask uint8 [B][per_clip], ts int64 [B]
+ *      (clamped into [0, n_steps)), sqrt_ac / sqrt_1mac f32 [n_steps]: the fp64 tables sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) cast to
+ *      fp32, as `_extract_into_tensor(...).float()` gives them.  x_t = sqrt_ac[t_b] * x0 + sqrt_1mac[t_b] * eps, both products rounded on
+ *      their own; then x_t = gt where mask (gt, mask NULL: no inpainting).  eps = noise when given; noise NULL: the library's Philox
+ *      generator (csrc/philox.h) at counter elem0 + e under the step index 0xFFFFFFFE, reserved for this entry (the sampler draws at its
+ *      loop indices 0 .. steps - 1 and x_T at 0xFFFFFFFF).  elem0 (a multiple of 4) as in interdiff_randn_at: a shard of a batch draws
+ *      the whole batch's noise.  x_t 16-byte aligned.
+ *  interdiff_denoising_losses   replaces the 16 per-clip terms of LitInteraction.forward_backward (train_diffusion_smpl.py:72-134, l2 :54-58)
+ *      on pred / target [B,1,144,T] in rot6d space, as the reference computes them, quirks included: the ground-truth velocity operand of the
+ *      first summand of every _v_ term is x_gt[a:b] - x_gt[a:b] (zero), the second summand is a second difference of the prediction alone.
+ *      out f32 [16][B].  One launch, one workgroup per clip, sums in a fixed order (no float atomics).  past_len >= 2, T >= past_len + 2.
+ *  interdiff_sample_losses      replaces the scoring of validation_step (variant IDF_LOSS_VAL, K = 1: _common_step :396-409 + calc_val_loss
+ *      :185-260) and of test_step (IDF_LOSS_TEST: :422-443 + calc_loss :262-379): rot6d -> matrix -> axis-angle per joint (the device
+ *      functions interdiff_rotation_6d_to_axis_angle uses), the 30 hand joints spliced in (prediction hand_pose[idx_pad[t]], ground truth
+ *      hand_pose[t]; hand_pose [T][B][90], NOT padded), axis-angle -> 3x3 (rotvec_to_rotmat, tools.py:88-90 -- human_body_prior's aa2matrot
+ *      is outside the reference tree: RESTATED, parity unpinned -- restatement defines the contract; csrc/rot_math.h), value / velocity
+ *      differences and reductions.  samples [K][B,1,144,T], gt [B,1,144,T].  out_terms f32 [32]: the 16 terms over all K samples, then
+ *      (TEST) the 16 best-of-K `_min` terms -- per clip the minimum over the samples, then the mean over clips -- (VAL: zeros).
+ *      out_per_clip f32 [K][16][B] (nullable: then `ws` holds it, interdiff_sample_losses_workspace_bytes(K, B) bytes): every clip's own
+ *      mean of every term.  The future-velocity frames differ between the variants exactly as upstream (VAL past_len .., TEST past_len + 1 ..).
+ *      Two launches whatever K is: one workgroup per (clip, sample), then one small workgroup for the means and minima; fixed order.
+ *      past_len >= 1, T >= past_len + 2.
+ * ---------------------------------------------------------------------------------- */
+enum { IDF_LOSS_VAL = 0, IDF_LOSS_TEST = 1 };
+int interdiff_q_sample(float *x_t, const float *x0, const float *noise, const int64_t *ts, const float *sqrt_ac, const float *sqrt_1mac,
+                       int32_t n_steps, const float *gt, const uint8_t *mask, int32_t B, int64_t per_clip, uint64_t seed, uint64_t elem0,
+                       void *stream);
+int interdiff_denoising_losses(const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, float *out, void *stream);
+size_t interdiff_sample_losses_workspace_bytes(int32_t K, int32_t B);
+int interdiff_sample_losses(const float *samples, const float *gt, const float *hand_pose, int32_t K, int32_t B, int32_t T, int32_t past_len,
+                            int32_t variant, float *out_terms, float *out_per_clip, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

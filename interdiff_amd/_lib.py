@@ -16,6 +16,7 @@ vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_ui
 MDM_LAYERS = 8
 FFN_SLICES = 5              # IDF_FFN_SLICES: partial output slabs of the fused feed-forward kernel
 STEP_EMBED_READY, STEP_EMBED_NEXT = 1, 2          # flags of interdiff_mdm_forward_step_ex (IDF_STEP_*)
+LOSS_VAL, LOSS_TEST = 0, 1                       # variant of interdiff_sample_losses (IDF_LOSS_*)
 TUNE = dict(ffn=3, ffn_math=4)      # indices into MdmWeights.tune (IDF_TUNE_*); the other six entries are reserved and must stay zero
 
 
@@ -138,6 +139,10 @@ _SIGS = {
     'interdiff_skeleton_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_encode_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_mdm_encode': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, i32, i32, vp, vp, sz, vp]),
+    'interdiff_q_sample': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i64, u64, u64, vp]),
+    'interdiff_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
+    'interdiff_sample_losses_workspace_bytes': (sz, [i32, i32]),
+    'interdiff_sample_losses': (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),

@@ -89,4 +89,24 @@ __device__ __forceinline__ void rodrigues_smpl(const float *a, float *m) {
     m[6] = 2 * xz - 2 * wy;    m[7] = 2 * wx + 2 * yz;    m[8] = w2 - x2 - y2 + z2;
 }
 
+// rotvec_to_rotmat (interdiff/tools.py:88-90) -> human_body_prior's aa2matrot -> angle_axis_to_rotation_matrix.  That package is not part of the
+// reference tree: this is a RESTATEMENT (parity unpinned -- restatement defines the contract) of the published algorithm: Rodrigues on
+// axis = aa / (theta + 1e-6) where theta^2 > 1e-6, else the first-order form I + [aa]x.
+__device__ __forceinline__ void aa2matrot(const float *a, float *m) {
+    const float rx = a[0], ry = a[1], rz = a[2];
+    const float th2 = rx * rx + ry * ry + rz * rz;
+    if (th2 > 1e-6f) {
+        const float th = sqrtf(th2), inv = 1.0f / (th + 1e-6f);
+        const float wx = rx * inv, wy = ry * inv, wz = rz * inv;
+        const float c = cosf(th), s = sinf(th), k = 1.0f - c;
+        m[0] = c + wx * wx * k;       m[1] = wx * wy * k - wz * s;  m[2] = wy * s + wx * wz * k;
+        m[3] = wz * s + wx * wy * k;  m[4] = c + wy * wy * k;       m[5] = -wx * s + wy * wz * k;
+        m[6] = -wy * s + wx * wz * k; m[7] = wx * s + wy * wz * k;  m[8] = c + wz * wz * k;
+    } else {
+        m[0] = 1.0f; m[1] = -rz;  m[2] = ry;
+        m[3] = rz;   m[4] = 1.0f; m[5] = -rx;
+        m[6] = -ry;  m[7] = rx;   m[8] = 1.0f;
+    }
+}
+
 }  // namespace rot

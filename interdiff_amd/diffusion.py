@@ -78,8 +78,12 @@ class GaussianDiffusion:
         self._c1 = self.posterior_mean_coef1.astype(np.float32)
         self._c2 = self.posterior_mean_coef2.astype(np.float32)
         self._sigma = np.exp(np.float32(0.5) * self.posterior_log_variance_clipped.astype(np.float32)).astype(np.float32)
+        # forward-diffusion tables (gaussian_diffusion.py:160-161), fp64; q_sample hands the kernel their fp32 casts
+        self.sqrt_alphas_cumprod = np.sqrt(self.alphas_cumprod)
+        self.sqrt_one_minus_alphas_cumprod = np.sqrt(1.0 - self.alphas_cumprod)
         self._t_cache = {}
         self._tables = {}
+        self._q_tables = {}
         self.fuse_plain_step = True          # plain steps of the graph route: posterior update inside the denoiser's last GEMM
         self.chain_plain_steps = os.environ.get('INTERDIFF_CHAIN_STEPS', '1') != '0'      # ... and, inside a captured run of plain steps, the next step's embedding in the same launch (csrc/tail_h2.h)
         self.split_chains = True             # ... and, for batches that do not fill the chip, as two independent half-batch chains
@@ -541,6 +545,68 @@ class GaussianDiffusion:
             if dump_steps is not None and it in dump_steps:
                 dump.append(img.clone())
         return dump if dump_steps is not None else img
+
+    # ------------------------------------------------------------------ forward diffusion / teacher-forced objective (forward only)
+    def sample_timesteps(self, B, device, generator=None):
+        """``UniformSampler.sample`` (diffusion/resample.py:61-77): ``t`` int64 [B] uniform over the schedule and the importance
+        weights, all one.  ``generator``: a torch generator (of any device) for a reproducible draw; default torch's global one."""
+        gdev = generator.device if generator is not None else device
+        t = torch.randint(0, self.num_timesteps, (B,), dtype=torch.int64, device=gdev, generator=generator).to(device)
+        return t, torch.ones(B, dtype=torch.float32, device=device)
+
+    def q_sample(self, x_start, t, noise=None, seed=None, inpainted_motion=None, inpainting_mask=None, elem0=0):
+        """``q_sample`` (gaussian_diffusion.py:233-250) with a per-clip timestep ``t`` int64 [B]: one launch of ``interdiff_q_sample``.
+        ``noise`` None: eps comes from the in-kernel Philox generator under ``seed`` (None: a fresh one, see ``fresh_seed``) at the
+        step index reserved for q_sample (include/interdiff_hip.h), element counter ``elem0`` + e -- a clip shard of a batch passes
+        first_clip * C * T and draws what the whole batch would.  ``inpainted_motion`` / ``inpainting_mask``: the inpainting of x_t
+        that ``training_losses`` applies when both keys are present (:1264-1268)."""
+        lib = _lib.load()
+        x0 = x_start.contiguous()
+        if x0.dtype != torch.float32:
+            raise ValueError('x_start must be float32')
+        B = x0.shape[0]
+        if tuple(t.shape) != (B,):
+            raise ValueError('t must be [B]')
+        if not t.is_cuda:
+            if int(t.min()) < 0 or int(t.max()) >= self.num_timesteps:
+                raise ValueError('t outside the schedule')
+            t = t.to(x0.device)
+        key = str(x0.device)
+        if key not in self._q_tables:
+            self._q_tables[key] = tuple(torch.from_numpy(v.astype(np.float32)).to(x0.device) for v in (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod))
+        sa, s1 = self._q_tables[key]
+        if (inpainted_motion is None) != (inpainting_mask is None):
+            raise ValueError('inpainted_motion and inpainting_mask go together')
+        mu8 = gc = None
+        if inpainting_mask is not None:
+            assert x0.shape == inpainting_mask.shape == inpainted_motion.shape
+            m = inpainting_mask
+            mu8, gc = (m if m.dtype == torch.uint8 else m.view(torch.uint8)).contiguous(), inpainted_motion.contiguous()
+        if noise is not None:
+            assert noise.shape == x0.shape
+            noise = noise.contiguous()
+        elif seed is None:
+            seed = fresh_seed()
+        x_t = torch.empty_like(x0)
+        _lib.check(lib.interdiff_q_sample(_lib.dptr(x_t), _lib.dptr(x0), _lib.dptr(noise, torch.float32, allow_none=True),
+                                          _lib.dptr(t.contiguous(), torch.int64), _lib.dptr(sa), _lib.dptr(s1), self.num_timesteps,
+                                          _lib.dptr(gc, torch.float32, allow_none=True), _lib.dptr(mu8, allow_none=True), B, x0.numel() // B,
+                                          int(seed or 0) & 0xFFFFFFFFFFFFFFFF, int(elem0), _lib.stream()), 'q_sample')
+        return x_t
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, seed=None):
+        """``training_losses`` (gaussian_diffusion.py:1233-1368) for the configuration this module implements (START_X, MSE): x_t by
+        ``q_sample`` (inpainted when model_kwargs['y'] carries both mask keys), ONE denoiser forward with the per-clip ``t``, and
+        ``(model_output, target)`` with target = x_start, as the reference returns them (:1368).  No backward pass."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        y = model_kwargs.get('y', {})
+        both = 'inpainting_mask' in y and 'inpainted_motion' in y
+        x_t = self.q_sample(x_start, t, noise=noise, seed=seed, inpainted_motion=y['inpainted_motion'] if both else None,
+                            inpainting_mask=y['inpainting_mask'] if both else None)
+        model_output = model(x_t, t.to(x_t.device), **model_kwargs)
+        assert model_output.shape == x_start.shape
+        return model_output, x_start
 
 
 class SpacedDiffusion(GaussianDiffusion):
