@@ -71,7 +71,7 @@ class HipCorrection:
         return x
 
     def _workspace(self, B, T):
-        """One workspace per STREAM the hook is called on: the sampler calls it for the two halves of a batch on two streams at once."""
+        """One workspace per STREAM the hook is called on: callers may run it on several streams at once."""
         need = self.lib.interdiff_correction_workspace_bytes(C.byref(self.ctx), B, T)
         key = torch.cuda.current_stream(self.device).cuda_stream
         ws = self._ws.pop(key, None)                  # (re-inserted below: the dict is kept in least-recently-used order)
@@ -84,15 +84,6 @@ class HipCorrection:
         return ws
 
     MAX_STREAM_WORKSPACES = 4
-
-    @staticmethod
-    def slice_kwargs(model_kwargs, sl):
-        """``model_kwargs`` of the clips ``sl`` of the batch (every entry of ``y`` the hook reads is per clip, eval_smpl_short.py:88-106):
-        what lets the sampler call the hook per half batch.  Contiguous copies, made once per sample."""
-        y = model_kwargs['y']
-        per_clip_dim = dict(inpainted_motion=0, inpainting_mask=0, obj_points=0, hand_pose=1, beta=1, cond=1)
-        ys = {k: (v[(slice(None),) * per_clip_dim[k] + (sl,)].contiguous() if k in per_clip_dim and isinstance(v, torch.Tensor) else v) for k, v in y.items()}
-        return dict(model_kwargs, y=ys)
 
     def apply(self, x, t0, y):
         """Run the correction unconditionally for timestep value t0 (host int); x [B,1,144,T] in place."""

@@ -634,7 +634,7 @@ class MDM:
     FFN16_MAX_ROWS, FFN64_MIN_ROWS = 800, 2800      # csrc/ffn.h
 
     def one_chain_max_rows(self):
-        """Up to how many token rows the sampler steps a batch as ONE kernel chain (diffusion.py _graph_loop).  Exact-fp32 feed-forward: 800 (the
+        """Up to how many token rows the sampler steps a batch as ONE kernel chain (graph_sampler.py).  Exact-fp32 feed-forward: 800 (the
         16-row grid's one round; above, two half-batch chains overlap each other's latency: round 3).  Split-f16 feed-forward: 1632 = 51 tiles
         of 32 rows x 5 slices = 255 workgroups, ONE round on 256 CUs -- the kernel owns its CUs (csrc/ffn_h2.h "exclusive CU"), so a second chain can
         no longer slip its small kernels beside it, and up to one round a single chain is ahead (same process, whole samples with correction,

@@ -474,6 +474,58 @@ def test_feed_forward_tile_is_picked_from_the_batch_rows():
     assert 'constexpr int FFN16_MAX_ROWS = %d, FFN64_MIN_ROWS = %d;' % (MDM.FFN16_MAX_ROWS, MDM.FFN64_MIN_ROWS) in src
 
 
+def test_step_planner_cuts_a_sample_into_graph_blocks(monkeypatch):
+    """graph_sampler.plan_steps (host logic, no GPU, no library): which captured graphs a sample is replayed from.  Pinned plans for the
+    correction gate (eval_smpl_short.py:85) over a whole sample and over the bench / test window, with the hook fused, eager and absent,
+    and with dump points; then the properties every plan must have, over a sweep of windows and dump sets."""
+    from interdiff_amd import diffusion, graph_sampler
+    plan = graph_sampler.plan_steps
+    gate = lambda t: t <= 500 and t % 50 == 0
+    never = lambda t: False
+    rle = lambda *runs: [op for op, n in runs for _ in range(n)]
+    P, H, E, D = (lambda k: ('plain', k)), (lambda k: ('hook', k)), ('eager_hook',), (lambda it: ('dump', it))
+
+    whole = plan(999, 1000, gate, None, True)
+    assert whole == rle((P(49), 10), (P(7), 1), (P(1), 1), (H(1), 1), (H(49), 10)) and len(whole) == 23
+    assert plan(560, 120, gate, None, True) == rle((P(49), 1), (P(7), 1), (P(1), 3), (H(1), 1), (H(49), 1), (P(7), 1), (P(1), 2))
+    assert plan(999, 1000, gate, None, False) == rle((P(49), 10), (P(7), 1), (P(1), 2)) + [E, P(49)] * 10 + [E]
+    assert plan(999, 1000, never, None, False) == rle((P(49), 20), (P(7), 2), (P(1), 6))
+    assert plan(560, 120, gate, {0, 59, 60, 119}, True) == [P(1), D(0), P(49), P(7), P(1), P(1), P(1), D(59), H(0), D(60), H(49), P(7), P(1), P(1), D(119)]
+
+    def check(t_start, todo, active, dumps, fuse):
+        ops = plan(t_start, todo, active, dumps, fuse)
+        want_dumps = sorted(d for d in (dumps or ()) if 0 <= d < todo)
+        i, it, seen, inside = t_start, 0, [], set(want_dumps)
+        for op in ops:
+            if op[0] == 'dump':
+                assert op[1] == it - 1 and op[1] in dumps, (op, it)
+                seen.append(op[1])
+                continue
+            assert op[0] in (('plain', 'hook') if fuse else ('plain', 'eager_hook')), op
+            k = op[1] if op[0] != 'eager_hook' else 0
+            assert k in diffusion.GRAPH_BLOCKS or (k == 0 and op[0] != 'plain'), op
+            for j in range(k):                               # the plain steps of the block: none active, no dump point before the block's end
+                assert not active(i - j), (op, i - j)
+                assert (it + j) not in inside or (j == k - 1 and op[0] == 'plain'), (op, it + j)
+            if op[0] != 'plain':
+                assert active(i - k), (op, i - k)
+                k += 1
+            i, it = i - k, it + k
+        assert (i, it) == (t_start - todo, todo), (i, it)      # every step once, in order, none beyond the window
+        assert seen == want_dumps
+        return ops
+
+    rs = np.random.RandomState(5)
+    for t_start, todo in [(999, 1000), (560, 120), (0, 1), (500, 1), (501, 2), (49, 50), (999, 0)] + [
+            (int(t), int(rs.randint(1, t + 2))) for t in rs.randint(0, 1000, 60)]:
+        for active in (gate, never, lambda t: t % 7 == 3):
+            for dumps in (None, set(), {todo - 1}, set(rs.randint(0, max(todo, 1), 5).tolist()), set(range(todo))):
+                for fuse in (True, False):
+                    check(t_start, todo, active, dumps, fuse)
+    monkeypatch.setattr(diffusion, 'GRAPH_BLOCKS', (12, 7, 1))      # read at call time (tools/block_ab.py rebinds it)
+    assert check(560, 120, gate, None, True) == rle((P(12), 4), (H(12), 1), (P(12), 4), (H(1), 1), (P(7), 1), (P(1), 2))
+
+
 def test_io_lightning_checkpoint_reproduces_the_committed_fixture(tmp_path):
     """interdiff_amd.io.load_lightning_state_dict on the reference's REAL checkpoints/correction.ckpt (a pytorch-lightning 1.7 file,
     ``LitInteraction.load_from_checkpoint``: eval_smpl_short.py:425-426, train_correction_smpl.py:24-40) must give, array for array and

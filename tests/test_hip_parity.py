@@ -1796,15 +1796,8 @@ def test_two_chain_plain_steps_equal_single_chain_and_eager(mdm, smpl):
                 two = run()
                 st = [v for k, v in mdm._graph_cache.items() if k[0] == diff._uid and k[1] == tuple(noise.shape)]
                 joined = lambda v: any((key[4] if key[0] == 'hook' else key[2]) for key in v.graphs if isinstance(key, tuple))                 # chains forked / joined inside every graph block
-                apart = lambda v: all(getattr(ch, 'graphs', None) for ch in v.chains)                         # chains on their own streams, own graphs
-                assert any(hasattr(v, 'chains') and (joined(v) or apart(v)) for v in st), 'split route not taken'
+                assert any(len(v.chains) == 2 and joined(v) for v in st), 'split route not taken'
                 assert torch.equal(two, run()), 'graph reuse'
-                if hook is not None and B % 2 == 0:  # the staggered per-chain loop (equal chains only) (option: hook called per half batch, chains on their own streams) against the default
-                    diff.stagger_steps = 7
-                    staggered = run()
-                    diff.stagger_steps = 0
-                    assert any(hasattr(v, 'chains') and apart(v) for v in st), 'staggered route not taken'
-                    assert torch.equal(two, staggered), 'staggered chains differ from joined chains: %g' % (two - staggered).abs().max()
                 diff.split_chains = False
                 one = run()
                 diff.split_chains = True
@@ -1874,7 +1867,7 @@ def test_timed_route_equals_eager_at_bench_shape(lib, mdm, smpl, B, T):
     timed = run(seed=seed)
     st = [v for k, v in mdm._graph_cache.items() if k[0] == diff._uid and k[1] == tuple(x_t.shape)]
     two = B * T > mdm.one_chain_max_rows() and B >= 4
-    assert len(st) == 1 and (hasattr(st[0], 'chains') and len(st[0].chains) == 2) == two, 'two-chain route %s' % ('not taken' if two else 'taken')
+    assert len(st) == 1 and (len(st[0].chains) == 2) == two, 'two-chain route %s' % ('not taken' if two else 'taken')
     flags = [(key[3], key[4]) if key[0] == 'hook' else (key[1], key[2]) for key in st[0].graphs if isinstance(key, tuple)]       # (fused, split) of plain-step and hook-step graphs
     assert all(f and sp == two for f, sp in flags), 'fused%s graphs expected: %r' % (' + split' if two else '', list(st[0].graphs))
     assert any(key[0] == 'hook' and key[2] == 49 for key in st[0].graphs if isinstance(key, tuple)), 'the 49 plain steps before a corrected step and the corrected step are ONE graph'
@@ -1883,10 +1876,6 @@ def test_timed_route_equals_eager_at_bench_shape(lib, mdm, smpl, B, T):
     eager = run(step_noise=_philox_step(lib, seed), use_graph=False)
     assert torch.equal(timed, eager), 'timed route differs from the eager injected-noise route at B=%d: %g' % (B, (timed - eager).abs().max())
     assert torch.equal(timed, run(seed=seed)), 'graph reuse'
-    if B % 2 == 0:
-        diff.stagger_steps = 7               # the optional staggered form (equal chains on their own streams, hook per half batch): same bits
-        assert torch.equal(timed, run(seed=seed)), 'staggered chains differ from the joined form (whole-batch hook steps)'
-        diff.stagger_steps = 0
     assert torch.isfinite(timed).all()
     fx.record_parity('timed_route_vs_eager_B%d_T%d_P2048_120steps_from_t560' % (B, T), bit_identical=1.0, corrected_steps_inside=2)
 
