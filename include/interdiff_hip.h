@@ -350,6 +350,14 @@ typedef struct {
 int interdiff_objprojector_sample(const idf_objproj *op, const float *obj_angles,
                                   const float *obj_trans, const float *markers,
                                   const int32_t *contact, int32_t B, float *out, void *stream);
+/* The teacher-forced call of the trainer: replaces the tail of ObjProjector.forward (model/correction_smpl.py:69-77; the axis-angle -> 6D conversion
+ * and the contact sum stay with the caller) = sample(..., initialize).  initialize == 0 is interdiff_objprojector_sample itself (same kernel, same
+ * bits; ws unused, contact required).  initialize != 0 replaces `results.mean(dim=2)` (:122-123), what validation uses while current_epoch < 10: the
+ * three stacks, then the mean over the P + 1 nodes taken in coefficient space (it commutes with the IDCT) and one IDCT; contact is not read (may be
+ * NULL); ws >= interdiff_objprojector_forward_workspace_bytes(B).  Additive (the ABI version does not move). */
+size_t interdiff_objprojector_forward_workspace_bytes(int32_t B);
+int interdiff_objprojector_forward(const idf_objproj *op, const float *obj_angles, const float *obj_trans, const float *markers,
+                                   const int32_t *contact, int32_t B, int32_t initialize, float *out, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * denoised_fn, fused   replaces eval_smpl_short.py:84-130 for one gated step.
@@ -603,6 +611,34 @@ int interdiff_denoising_losses(const float *pred, const float *target, int32_t B
 size_t interdiff_sample_losses_workspace_bytes(int32_t K, int32_t B);
 int interdiff_sample_losses(const float *samples, const float *gt, const float *hand_pose, int32_t K, int32_t B, int32_t T, int32_t past_len,
                             int32_t variant, float *out_terms, float *out_per_clip, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Scoring of a correction-predictor checkpoint (csrc/corr_losses.hip).  Forward only, additive.
+ *  interdiff_correction_losses  replaces LitInteraction.calc_loss_contact (interdiff/train_correction_smpl.py:103-185), calc_loss (:60-101) and the
+ *      skeleton trainer's calc_loss (train_correction_skeleton.py:85-126).
+ *      obj_pred, obj_gt f32 [T][B][rot_width + 3]: rot = the leading rot_width channels, nonrot = the trailing 3 (rot_width 6: rot6d | translation;
+ *      4: the skeleton trainer's pose [translation | quaternion xyzw], split as that trainer splits it).
+ *      out_terms f32 [10], the reference's dict order: penetration, contact, obj_rot_past, obj_nonrot_past, obj_rot_future, obj_nonrot_future,
+ *      obj_rot_v_past, obj_nonrot_v_past, obj_rot_v_future, obj_nonrot_v_future -- raw (unweighted) means.  The future velocity term pairs frame t
+ *      with t - 1 from t = past_len on (its first pair straddles the border), as upstream.
+ *      Geometry half (obj_points and human_verts given; rot_width must be 6): obj_points f32 [B][P][point_stride] canonical, xyz leading (stride 3, or
+ *      6 for the batch's points-with-normals), human_verts f32 [T][B][V][7] = position | normal | contact label, interleaved as the batch has it.
+ *      Per frame the points are posed with rotation_6d_to_matrix(obj_pred) and the predicted translation INSIDE the kernel and point2point_signed
+ *      (tools.py:11-76) runs in both directions with the contract of interdiff_nn_argmin (d2 = (dx*dx + dy*dy) + dz*dz, no FMA, lowest index wins):
+ *        contact      = mean over T*B*V of |h2o| [|h2o| > 0.02 and label > 0.5]
+ *        penetration  = mean over T*B*P of 20 |o2h| [o2h < 0], the sign from the body normal of the nearest vertex
+ *      (the reference's band 0 < o2h < 0.01 carries weight 0, :141-143: kept).  No per-pair / per-vertex / per-point array is written: only
+ *      (sum, count) per workgroup, into ws >= interdiff_correction_losses_workspace_bytes(T, B, V, P).  out_frames (nullable) f32 [T*B][4] =
+ *      per frame (penetration sum, contact sum, penetrating points, contact vertices).  T * B <= 65535.
+ *      Without the geometry half (both pointers NULL): terms 0 and 1 are 0, ws and out_frames must be NULL.
+ *      The per-frame matrices come from interdiff_rotation_6d_to_matrix itself (the rot6d columns are gathered into ws by one strided device copy), so
+ *      the entry poses the points from the bits that entry gives.  One copy + three launches (one launch without geometry) whatever T * B is; no float atomics, fixed summation order: two calls give the same bits, and a frame's
+ *      partial sums do not depend on which other clips are in the call.  past_len >= 1, T >= past_len + 1.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_correction_losses_workspace_bytes(int32_t T, int32_t B, int32_t V, int32_t P);
+int interdiff_correction_losses(const float *obj_pred, const float *obj_gt, const float *obj_points, int32_t point_stride, const float *human_verts,
+                                int32_t T, int32_t B, int32_t V, int32_t P, int32_t rot_width, int32_t past_len, float *out_terms, float *out_frames,
+                                void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).

@@ -123,6 +123,8 @@ _SIGS = {
     'interdiff_posterior_step_dev': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     'interdiff_sampler_advance': (C.c_int, [vp, vp, i32, vp]),
     'interdiff_objprojector_sample': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, vp, vp]),
+    'interdiff_objprojector_forward_workspace_bytes': (sz, [i32]),
+    'interdiff_objprojector_forward': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_correction_workspace_bytes': (sz, [C.POINTER(CorrectionCtx), i32, i32]),
     'interdiff_correction': (C.c_int, [C.POINTER(CorrectionCtx), vp, vp, vp, vp, vp, i32, i32, f32,
                                        vp, vp, vp, vp, vp, sz, vp]),
@@ -143,6 +145,8 @@ _SIGS = {
     'interdiff_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
     'interdiff_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_sample_losses': (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    'interdiff_correction_losses_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'interdiff_correction_losses': (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),

@@ -1,5 +1,6 @@
 """Corrector seam: ``ObjProjector.sample(obj_angles, obj_trans, human_verts, contact)``
-(model/correction_smpl.py:79-138, eval branch) on ``interdiff_objprojector_sample``.
+(model/correction_smpl.py:79-138, eval branch) on ``interdiff_objprojector_sample``, and the trainer's teacher-forced
+``ObjProjector.forward(data, initialize)`` (:69-77) on ``interdiff_objprojector_forward``.
 
 ``pack_objprojector`` takes the reference module's state_dict (``checkpoints/correction.ckpt`` keys with
 the ``model.`` prefix stripped) and folds, on the host in float64:
@@ -105,16 +106,43 @@ class ObjProjector:
     def eval(self):
         return self
 
+    def forward(self, data, initialize=False):
+        """``ObjProjector.forward`` (model/correction_smpl.py:69-77): ``data`` is the reference's dict-of-lists batch
+        (``frames[t]['objfit_params']['angle' | 'trans']`` [B,3], ``frames[t]['markers']`` [B,67,7]) or the stacked tensors
+        ``dict(obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7])``.  Axis-angle -> 6D on the rotation kernels, contact =
+        the future frames' marker labels summed, then ``sample``.  Returns (final_results [T,B,9], obj_gt [T,B,9])."""
+        from . import transforms
+        if 'frames' in data:
+            fr = data['frames']
+            aa = torch.stack([f['objfit_params']['angle'] for f in fr])
+            ot = torch.stack([f['objfit_params']['trans'] for f in fr])
+            mk = torch.stack([f['markers'] for f in fr])
+        else:
+            aa, ot, mk = data['obj_angle'], data['obj_trans'], data['markers']
+        aa, ot, mk = (a.to(self.device).float() for a in (aa, ot, mk))
+        if mk.dim() != 4 or mk.shape[-1] != 7:
+            raise ValueError('markers must be [T,B,67,7] (position | normal | contact label)')
+        d6 = transforms.matrix_to_rotation_6d(transforms.axis_angle_to_matrix(aa))
+        contact = mk[self.past_len:, :, :, 6].sum(dim=0)
+        return self.sample(d6, ot, mk, contact, initialize), torch.cat([d6, ot], dim=2)
+
+    __call__ = forward
+
     def sample(self, obj_angles, obj_trans, human_verts, contact, initialize=False):
-        if initialize:
-            raise NotImplementedError('initialize=True (mean over nodes) is a training-time option')
+        """``initialize=True``: the mean over the 68 output nodes (:122-123, what the trainer asks for while current_epoch < 10);
+        ``contact`` is then not read."""
         T, B = obj_angles.shape[:2]
         if T != self.T:
             raise ValueError('ObjProjector was packed for T=%d' % self.T)
         hv = human_verts[..., :3].contiguous().float()
         oa, ot = obj_angles.contiguous().float(), obj_trans.contiguous().float()
-        ct = contact.to(torch.int32).contiguous()
         out = torch.empty(T, B, 9, dtype=torch.float32, device=self.device)
+        if initialize:
+            ws = torch.empty(self.lib.interdiff_objprojector_forward_workspace_bytes(B), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.interdiff_objprojector_forward(C.byref(self.cop), _lib.dptr(oa), _lib.dptr(ot), _lib.dptr(hv), None, B, 1,
+                                                               _lib.dptr(out), _lib.dptr(ws), ws.numel(), _lib.stream()), 'objprojector_forward')
+            return out
+        ct = contact.to(torch.int32).contiguous()
         _lib.check(self.lib.interdiff_objprojector_sample(C.byref(self.cop), _lib.dptr(oa), _lib.dptr(ot), _lib.dptr(hv),
                                                           _lib.dptr(ct, torch.int32), B, _lib.dptr(out), _lib.stream()),
                    'objprojector_sample')

@@ -149,6 +149,38 @@ class SkeletonObjProjector:
         return q, tr
 
 
+    def forward(self, obj_angles, obj_trans, human_points):
+        """``ObjProjector.forward`` of the trainer (model/correction_skeleton.py:68-80) AS WRITTEN: it converts the xyzw quaternion to 6D
+        and hands the 6-vector to ``sample``, which converts again -- reading the 6-vector's trailing four values [r02, r10, r11, r12]
+        as a quaternion xyzw.  The checkpoint was trained and selected through this double conversion, so it is kept: the first
+        conversion runs here on the host side (elementwise torch on the device tensors), the rest is ``sample``.
+        Returns (obj_angles_p [T,B,4], obj_trans_p [T,B,3], obj_angles_gt, obj_trans_gt)."""
+        q = obj_angles.to(self.device).float()
+        i, j, k, r = q.unbind(-1)                                               # xyzw -> (r, i, j, k) = quat_correct (:74)
+        two_s = 2.0 / (q * q).sum(-1)                                           # quaternion_to_matrix, rows 0 and 1 = rotation 6D
+        d6_tail = torch.stack([two_s * (i * k + j * r), two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r)], dim=-1)
+        qp, tp = self.sample(d6_tail, obj_trans, human_points)
+        return qp, tp, obj_angles.clone(), obj_trans.clone()
+
+
+def skeleton_calc_loss(pose_pred, pose_gt, past_len=10, weights=None):
+    """``calc_loss`` of train_correction_skeleton.py:85-126 on pose [T,B,7] = translation | quaternion xyzw, split as that trainer splits
+    it: "rot" = the leading four channels, "nonrot" = the trailing three.  -> (loss, loss_dict, weighted_loss_dict)."""
+    from . import correction_losses as cl
+    return cl.calc_loss(pose_pred, pose_gt, past_len=past_len, weights=weights or cl.CorrectionLossWeights())
+
+
+def skeleton_validation_step(objprojector, batch, weights=None):
+    """``_common_step`` + ``validation_step`` of train_correction_skeleton.py:128-154, :191-196: ``batch`` = (body [B,T,21,3], object
+    keypoints [B,T,12,3], pose [B,T,7], zero_pose_obj [B,12,3]).  -> (val_loss, loss_dict, weighted_loss_dict).  The reference also
+    computes ``calc_obj_pred`` and ``calc_metric`` there and discards both (nothing logs them): neither is evaluated."""
+    dev = objprojector.device
+    body_gt, pose_gt = batch[0].transpose(0, 1).float().to(dev), batch[2].transpose(0, 1).float().to(dev)
+    obj_trans, obj_angles = torch.split(pose_gt, [3, 4], dim=2)
+    qp, tp, _, _ = objprojector.forward(obj_angles, obj_trans, body_gt)
+    return skeleton_calc_loss(torch.cat([tp, qp], dim=2), pose_gt, objprojector.past_len, weights)
+
+
 class HipSkeletonCorrection:
     """Drop-in ``denoised_fn(x, t, model_kwargs)`` of eval_skeleton.py:82-111 on ``interdiff_skeleton_correction``.
 
