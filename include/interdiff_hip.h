@@ -641,6 +641,32 @@ int interdiff_correction_losses(const float *obj_pred, const float *obj_gt, cons
                                 void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Contact-label generation (csrc/contact_labels.hip): the per-frame work of interdiff/data/prepare_behave.py:32-52 (get_contact_labels).  Additive.
+ *  interdiff_contact_labels     replaces igl.signed_distance(points, smpl.vertices, smpl.faces) (:42, winding-number sign), `dist < thres` (:45) and
+ *      the body vertices within thres of a labelled point (:48-51), for N frames in three launches.  igl is not available: RESTATED, the restatement
+ *      defines the contract:
+ *        d = min over faces of the exact point-triangle distance (a zero-area face counts through its edges and corners; never NaN),
+ *        w = (1 / 4 pi) sum over faces of the signed solid angle (van Oosterom-Strackee atan2 form; a zero-area face contributes 0),
+ *        S = (1 - 2 w) d,   obj_label = S < thres,   human_label[v] = exists p: obj_label[p] and |p - v| < thres   (both comparisons strict).
+ *      verts f32 [N][V][3]; faces int32 [F][3] in the mesh's own orientation, every index in [0, V) -- validated by the caller, the kernels only clamp;
+ *      their order changes no result, only how many (lane, 256-face chunk) pairs the bounding-box test skips (sort them along a space-filling curve).
+ *      points f32: point_frame_stride 0 = one cloud [P][3] shared by all frames, 3 * P = per-frame points [N][P][3].  objR f32 [N][9] row-major and
+ *      objT f32 [N][3], both or neither: the kernels use p R^T + t (products and sums rounded one by one, left to right); NULL = points as given.
+ *      obj_label uint8 [N][P], human_label uint8 [N][V] (all V vertices, unreferenced ones included), signed_dist (nullable) f32 [N][P] = S: w is
+ *      computed for every point (the solid angle shares the face loop of the distance), so there is no point that gets +d instead.
+ *      ws >= interdiff_contact_labels_workspace_bytes(N, V, F, P): the chunk bounding boxes.  fp32, no float atomics, no reduction across
+ *      workgroups: two calls give the same bits.  IDF_E_INVAL: null pointer, non-positive size or thres, a stride that is neither 0 nor 3 * P, one of
+ *      objR / objT without the other; IDF_E_NOMEM: short workspace.
+ *  interdiff_debug_point_triangle   HOST-side instance of the per-pair device inline: tri [n][9] = a | b | c, p [n][3] -> out [n][2] = squared distance,
+ *      signed solid angle; lets the CPU test suite check the region logic without a GPU.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_contact_labels_workspace_bytes(int64_t N, int32_t V, int32_t F, int32_t P);
+int interdiff_contact_labels(const float *verts, int64_t N, int32_t V, const int32_t *faces, int32_t F, const float *points, int32_t P,
+                             int64_t point_frame_stride, const float *objR, const float *objT, float thres, uint8_t *obj_label /*[N,P]*/,
+                             uint8_t *human_label /*[N,V]*/, float *signed_dist /*[N,P] or NULL*/, void *ws, size_t ws_bytes, void *stream);
+int interdiff_debug_point_triangle(const float *tri, const float *p, float *out, int32_t n);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

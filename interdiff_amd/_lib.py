@@ -147,6 +147,9 @@ _SIGS = {
     'interdiff_sample_losses': (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_correction_losses_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'interdiff_correction_losses': (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    'interdiff_contact_labels_workspace_bytes': (sz, [i64, i32, i32, i32]),
+    'interdiff_contact_labels': (C.c_int, [vp, i64, i32, vp, i32, vp, i32, i64, vp, vp, f32, vp, vp, vp, vp, sz, vp]),
+    'interdiff_debug_point_triangle': (C.c_int, [vp, vp, vp, i32]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),

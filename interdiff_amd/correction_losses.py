@@ -10,8 +10,8 @@
 The batch is the DataLoader's dict of lists (``frames[t]['human_verts']`` [B,V,7] = position | normal | contact label,
 ``obj_points`` [B,P,6]) or the stacked tensors (``human_verts`` [T,B,V,7]).  All arithmetic runs in libinterdiff_hip.so
 (csrc/corr_losses.hip): a launch count that does not depend on T * B (the rotation entry, the fused geometry pass, the reduction);
-torch only applies the ten weights.  The contact labels are an input: the
-label generator (prepare_behave.py) is outside this package.
+torch only applies the ten weights.  The contact labels are an input; ``contact_labels.generate_contact``
+(prepare_behave.py) writes them.
 """
 from dataclasses import dataclass
 import torch
@@ -126,7 +126,7 @@ def body_records(smpl_layer, pose, betas, trans, contact_labels, markers_idx=Non
     """The two per-frame body records of a batch (data/dataset_smpl.py) from a body model, on the HIP SMPL forward and
     ``vertex_normals``: ``human_verts`` [T,B,V,7] = vertex | normal | contact label and ``markers`` [T,B,67,7] = its rows
     ``markerset_ssm67_smplh``.  ``pose`` [T,B,3J] axis-angle, ``betas`` [T,B,nb], ``trans`` [T,B,3], ``contact_labels`` [T,B,V]
-    (an input: the label generator is outside this package).  ``topology``: a ``geometry.MeshTopology`` to reuse."""
+    (``data.clip_labels`` of a ``contact.npz`` that ``contact_labels.generate_contact`` wrote).  ``topology``: a ``geometry.MeshTopology`` to reuse."""
     from .correction import MARKERS67
     from .geometry import vertex_normals
     T, B = pose.shape[:2]

@@ -8,8 +8,9 @@ origin at the first pelvis, yaw of the first global orientation removed).  Host-
 dataset plumbing, not the hot path); the one heavy step, the per-frame pelvis = SMPL joint 0 over the whole sequence
 (:57,68), runs on the GPU through ``SMPL_Layer``.  The contact-side records of a clip -- the object cloud of every frame with
 normals and contact labels, foot-ground labels, human contact labels (:48-50,152-180; read by the reference's training code, never
-by the sampler, the hook or the metrics) -- come from ``clip_labels`` when the sequence has a ``contact.npz``; the per-vertex
-``human_verts`` records and rendering inputs are not produced."""
+by the sampler, the hook or the metrics) -- come from ``clip_labels`` when the sequence has a ``contact.npz`` (written by ``contact_labels.generate_contact`` /
+``write_contact_npz`` from the fits and an object mesh read by ``load_obj_mesh`` / ``load_ply_mesh``); the per-vertex ``human_verts`` records come
+from ``correction_losses.body_records``; rendering inputs are not produced."""
 import os
 import numpy as np
 import torch
@@ -95,6 +96,94 @@ def load_ply_vertices(path):
             rec = np.frombuffer(f.read(nv * dt.itemsize), dtype=dt, count=nv)
             v = np.stack([rec['x'], rec['y'], rec['z']], axis=1).astype(np.float64)
     return v - v.mean(0)
+
+
+_PLY_TYPES = {'float': '<f4', 'float32': '<f4', 'double': '<f8', 'float64': '<f8', 'uchar': 'u1', 'uint8': 'u1', 'char': 'i1', 'int8': 'i1',
+              'short': '<i2', 'int16': '<i2', 'ushort': '<u2', 'uint16': '<u2', 'int': '<i4', 'int32': '<i4', 'uint': '<u4', 'uint32': '<u4'}
+
+
+def _fan(polys):
+    """Polygons (index lists) -> triangles, as a fan around the first corner."""
+    return np.array([[q[0], q[k], q[k + 1]] for q in polys for k in range(1, len(q) - 1)], dtype=np.int64).reshape(-1, 3)
+
+
+def load_ply_mesh(path):
+    """(vertices [V,3] float64, faces [F,3] int64) of an ASCII or binary-little-endian PLY, as stored -- NOT centred (``load_ply_vertices``
+    centres; ``contact_labels.generate_contact`` does its own centring).  Polygons with more than three corners become triangle fans; elements
+    other than ``vertex`` and ``face`` are skipped."""
+    with open(path, 'rb') as f:
+        fmt, elements = None, []                                    # elements: [name, count, [(kind, type[, count type], name)]]
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError('%s: no end_header' % path)
+            w = line.decode('ascii', 'ignore').split()
+            if not w:
+                continue
+            if w[0] == 'format':
+                fmt = w[1]
+            elif w[0] == 'element':
+                elements.append([w[1], int(w[2]), []])
+            elif w[0] == 'property':
+                elements[-1][2].append(('list', w[2], w[3], w[4]) if w[1] == 'list' else ('scalar', w[1], w[2]))
+            elif w[0] == 'end_header':
+                break
+        if fmt not in ('ascii', 'binary_little_endian'):
+            raise ValueError('%s: unsupported PLY format %r' % (path, fmt))
+        verts, faces = None, np.zeros((0, 3), np.int64)
+        for name, count, props in elements:
+            has_list = any(p[0] == 'list' for p in props)
+            if fmt == 'ascii':
+                rows = [f.readline().split() for _ in range(count)]
+                if name == 'vertex':
+                    col = [p[-1] for p in props]
+                    ix = [col.index(k) for k in 'xyz']
+                    verts = np.array([[float(r[i]) for i in ix] for r in rows], dtype=np.float64).reshape(-1, 3)
+                elif name == 'face':
+                    polys, at = [], [p[0] for p in props].index('list')          # scalar properties in front of the list take one token each
+                    for r in rows:
+                        k = int(r[at])
+                        polys.append([int(x) for x in r[at + 1:at + 1 + k]])
+                    faces = _fan(polys)
+            elif not has_list:
+                dt = np.dtype([(p[2], _PLY_TYPES[p[1]]) for p in props])
+                rec = np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
+                if name == 'vertex':
+                    verts = np.stack([rec['x'], rec['y'], rec['z']], axis=1).astype(np.float64)
+            else:
+                polys = []
+                for _ in range(count):
+                    for p in props:
+                        if p[0] == 'scalar':
+                            f.read(np.dtype(_PLY_TYPES[p[1]]).itemsize)
+                        else:
+                            k = int(np.frombuffer(f.read(np.dtype(_PLY_TYPES[p[1]]).itemsize), dtype=_PLY_TYPES[p[1]])[0])
+                            idx = np.frombuffer(f.read(k * np.dtype(_PLY_TYPES[p[2]]).itemsize), dtype=_PLY_TYPES[p[2]])
+                            if name == 'face' and p[3] in ('vertex_indices', 'vertex_index'):
+                                polys.append([int(x) for x in idx])
+                if name == 'face':
+                    faces = _fan(polys)
+    if verts is None:
+        raise ValueError('%s: no vertex element' % path)
+    return verts, faces
+
+
+def load_obj_mesh(path):
+    """(vertices [V,3] float64, faces [F,3] int64, 0-based) of a Wavefront OBJ: ``v x y z`` and ``f`` lines, corners written ``a``, ``a/b``,
+    ``a//c`` or ``a/b/c`` (the vertex index is the first field; negative indices count from the end, as the format allows).  Polygons become
+    triangle fans.  What psbody's ``Mesh.load_from_obj`` gives prepare_behave.py:76-88 as ``.v`` and ``.f``."""
+    verts, polys = [], []
+    with open(path) as f:
+        for line in f:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == 'v':
+                verts.append([float(x) for x in w[1:4]])
+            elif w[0] == 'f':
+                idx = [int(c.split('/')[0]) for c in w[1:]]
+                polys.append([i - 1 if i > 0 else len(verts) + i for i in idx])
+    return np.array(verts, dtype=np.float64).reshape(-1, 3), _fan(polys)
 
 
 def sample_points(vertices, n, seed=0):
