@@ -613,6 +613,35 @@ int interdiff_sample_losses(const float *samples, const float *gt, const float *
                             int32_t variant, float *out_terms, float *out_per_clip, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Scoring of a skeleton diffusion checkpoint (csrc/skeleton_losses.hip): the forward, scoring side of interdiff/train_diffusion_skeleton.py.
+ * Forward only, additive.  Tokens [B,1,C,T] with C = n_body + 3 * n_points + 7 (63 + 36 + 7 = 106): body | object keypoints | object
+ * translation 3 | object quaternion xyzw 4.  The keypoint channels are the prediction's own (the denoiser's keypoint head wrote them): nothing is
+ * re-posed.  Term order everywhere (the reference's dict order, :129-143 / :215-229):
+ *   0 body_past, 1 body_future, 2 obj_past, 3 obj_future, 4 loss_obj_nonrot_past, 5 loss_obj_nonrot_future, 6 loss_obj_rot_past,
+ *   7 loss_obj_rot_future, 8 quaternion_reg_loss, 9 loss_obj_rot_v, 10 loss_obj_nonrot_v, 11 loss_body_v, 12 loss_obj_v
+ * -- raw (unweighted) means of squares; the four velocity terms over all T - 1 frame differences, (x[t] - x[t-1]) - (g[t] - g[t-1]);
+ * quaternion_reg_loss = mean over frames of (q.q - 1)^2 of the prediction.
+ *
+ *  interdiff_skeleton_sample_losses     replaces the split of _common_step (:280-283) and calc_val_loss (:190-229).  pred f32 [K][B,1,C,T]: K
+ *      samples of one batch (K = 1 is the reference's case; no best-of-K terms, the skeleton trainer has none), gt f32 [B,1,C,T].
+ *      out_terms f32 [K][13]: per sample the mean over its B clips.  out_per_clip f32 [K][13][B] (nullable: then `ws` holds it,
+ *      interdiff_skeleton_sample_losses_workspace_bytes(K, B) bytes): every clip's own mean of every term -- it depends on that clip's floats
+ *      alone, whatever else is in the call.  Two launches whatever K and B are: one workgroup per (sample, clip), then one small workgroup
+ *      for the means over clips; fp32, no float atomics, fixed order: two calls give the same bits.
+ *      IDF_E_INVAL unless past_len >= 1, T >= past_len + 1 and C == n_body + 3 * n_points + 7; IDF_E_NOMEM for a short workspace; nothing is
+ *      launched in either case.
+ *  interdiff_skeleton_denoising_losses  replaces the 13 terms of forward_backward (:100-127) in their per-clip form: pred (the model output) and
+ *      target f32 [B,1,C,T] with C = n_body + 3 * n_points + 7, out f32 [13][B].  One launch (the first of the two above); the means over the batch
+ *      and the weighted sum (:145-161, :168) are the caller's.  Same argument checks.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_skeleton_sample_losses_workspace_bytes(int32_t K, int32_t B);
+int interdiff_skeleton_sample_losses(const float *pred, const float *gt, int32_t K, int32_t B, int32_t C, int32_t T, int32_t past_len,
+                                     int32_t n_body, int32_t n_points, float *out_terms, float *out_per_clip, void *ws, size_t ws_bytes,
+                                     void *stream);
+int interdiff_skeleton_denoising_losses(const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, int32_t n_body,
+                                        int32_t n_points, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Scoring of a correction-predictor checkpoint (csrc/corr_losses.hip).  Forward only, additive.
  *  interdiff_correction_losses  replaces LitInteraction.calc_loss_contact (interdiff/train_correction_smpl.py:103-185), calc_loss (:60-101) and the
  *      skeleton trainer's calc_loss (train_correction_skeleton.py:85-126).

@@ -145,6 +145,9 @@ _SIGS = {
     'interdiff_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, vp, vp]),
     'interdiff_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_sample_losses': (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_sample_losses_workspace_bytes': (sz, [i32, i32]),
+    'interdiff_skeleton_sample_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     'interdiff_correction_losses_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'interdiff_correction_losses': (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_contact_labels_workspace_bytes': (sz, [i64, i32, i32, i32]),
