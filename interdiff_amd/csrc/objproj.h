@@ -10,17 +10,14 @@
 //   - the idx_pad frame repetition (future frames = last past frame) is folded into a
 //     [n_pre x past_len] DCT matrix, so only the past markers enter the relative branch,
 //   - the IDCT is evaluated only for the node that the contact rule selects.
-// Layer block layout in the arena (floats), for a layer with cin/cout channels over `nodes` nodes
-// (cinp/coutp = channels rounded up to 16, zero padded):
-//   version 0 (stacks 0,1):  Tm[n_pre][n_pre] (+12 pad)
-//   version 2 (stack 2):     Tm[nodes][n_pre][n_pre], AT[n_pre][80][80]  (A transposed: [t][w][v], zero padded)
-//   then Wt[coutp][cinp], bt[coutp], Wr[coutp][cinp], br[coutp], prelu[1]
+// The ST-GCN layer's arena block and its three products (1x1 convolution tile, temporal mix, adjacency product): csrc/stgcn.h.
 // (Device code in a header since round 6: the correction hook runs PART 1 as sixteen leading workgroups of its contact-scan launch, csrc/correction.hip.)
 #pragma once
-#include "common.h"
+#include "stgcn.h"
 
 namespace idf_objproj_dev {
 
+using namespace idf_stgcn;
 
 constexpr int NP = 10;                     // n_pre (DCT coefficients)
 constexpr int MAXN = 68;                   // nodes: 67 markers + the object itself
@@ -28,55 +25,17 @@ constexpr int VP = 80;                     // nodes padded to 5 MFMA tiles (adja
 constexpr int CH = 9;
 constexpr int PLANE = NP * MAXN;           // one channel of the big buffers
 constexpr int POOL_CH = 48;                // max(cin + cout) over the 9->32->16->32->9 stacks
-constexpr int NTHR = 1024, NWAVE = NTHR / 64;
-
-__device__ __forceinline__ int pad16(int x) { return (x + 15) & ~15; }
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
-struct LayerP {
-    const float *Tm, *AT, *Wt, *bt, *Wr, *br;
-    float prelu;
-};
-
-// arena block of one layer (pack_objprojector): Tm | (AT) | Wt[coutp][cinp] | bt[coutp] | Wr[coutp][cinp] | br[coutp] | prelu
-__device__ __forceinline__ LayerP layer_params(const float *blk, int cin, int cout, int nodes, bool v2) {
-    const int cinp = pad16(cin), coutp = pad16(cout);
-    LayerP p;
-    p.Tm = blk;
-    blk += v2 ? nodes * NP * NP : NP * NP + 12;         // shared 10x10 block is padded to 112 floats
-    p.AT = v2 ? blk : nullptr;
-    if (v2) blk += NP * VP * VP;
-    p.Wt = blk; blk += coutp * cinp;
-    p.bt = blk; blk += coutp;
-    p.Wr = blk; blk += coutp * cinp;
-    p.br = blk; blk += coutp;
-    p.prelu = blk[0];
-    return p;
-}
 
 // 1x1 convolution over channel-major planes on the fp32 MFMA:
 //   out[o][pos] = bias[o] + sum_c W[o][c] in[c][pos]      (ACC: += what is there, then PReLU)
-// M = positions (16 per tile), N = output channels, K = input channels (zero-padded weights).
 template <bool ACC>
 __device__ __forceinline__ void conv1x1(const float *in, float *out, const float *W, const float *bias, int cin, int cout,
                                         int npos, float slope) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, kq = lane >> 4;
-    const int cinp = pad16(cin), NT = pad16(cout) >> 4, MT = (npos + 15) >> 4;
+    const int NT = pad16(cout) >> 4, MT = (npos + 15) >> 4;
     for (int item = wave; item < MT * NT; item += NWAVE) {
         const int mt = item / NT, nt = item - mt * NT;
-        const int pos = min(mt * 16 + li, npos - 1);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        for (int c0 = 4 * kq; c0 < cinp; c0 += 16) {
-            const float4 w = ld4(W + (nt * 16 + li) * cinp + c0);
-            const float a0 = c0 + 0 < cin ? in[(c0 + 0) * npos + pos] : 0.f;
-            const float a1 = c0 + 1 < cin ? in[(c0 + 1) * npos + pos] : 0.f;
-            const float a2 = c0 + 2 < cin ? in[(c0 + 2) * npos + pos] : 0.f;
-            const float a3 = c0 + 3 < cin ? in[(c0 + 3) * npos + pos] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, w.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, w.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, w.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, w.w, acc, 0, 0, 0);
-        }
+        const f32x4 acc = conv_tile(in, W, cin, npos, mt, nt);
         const int o = nt * 16 + li;
         if (o < cout) {
             const float bv = bias[o];
@@ -98,71 +57,13 @@ __device__ __forceinline__ void conv1x1(const float *in, float *out, const float
 
 // one ST-GCN layer on channel-major planes [c][k][node] with row stride `nodes`
 __device__ inline void st_gcn_layer(float *in, float *out, const LayerP &p, int cin, int cout, int nodes, bool v2) {
-    const int npos = NP * nodes, stride = npos;
+    const int npos = NP * nodes;
     conv1x1<false>(in, out, p.Wr, p.br, cin, cout, npos, 0.f);      // residual branch (BN folded)
     __syncthreads();
-    // temporal mixing, in place: y[q] = sum_t x[t] Tm[(v)][t][q]
-    for (int i = threadIdx.x; i < cin * nodes; i += NTHR) {
-        const int c = i / nodes, v = i - c * nodes;
-        float *col = in + c * stride + v;
-        const float *Tm = p.Tm + (v2 ? v * NP * NP : 0);
-        float x[NP], y[NP];
-#pragma unroll
-        for (int t = 0; t < NP; ++t) { x[t] = col[t * nodes]; y[t] = 0.f; }
-#pragma unroll
-        for (int t = 0; t < NP; ++t)
-#pragma unroll
-            for (int q = 0; q < NP; q += 2) {
-                const float2 tm = *reinterpret_cast<const float2 *>(Tm + t * NP + q);
-                y[q] += x[t] * tm.x;
-                y[q + 1] += x[t] * tm.y;
-            }
-#pragma unroll
-        for (int q = 0; q < NP; ++q) col[q * nodes] = y[q];
-    }
+    temporal_mix<NP>(in, p.Tm, cin, nodes, v2);
     __syncthreads();
     if (v2) {
-        // spatial mixing on the MFMA, in place: per coefficient t, Y[c][w] = sum_v X[c][t][v] A[t][v][w].
-        // One wave owns the whole row block (16 channels, one t): it pulls its X fragments into registers first,
-        // so writing the result back over the same rows is safe without a barrier.  (nodes % 4 == 0 here.)
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, kq = lane >> 4;
-        const int MT = pad16(cin) >> 4;
-        for (int item = wave; item < MT * NP; item += NWAVE) {
-            const int mt = item / NP, t = item - mt * NP, c = mt * 16 + li;
-            float4 a[VP / 16];
-#pragma unroll
-            for (int s4 = 0; s4 < VP / 16; ++s4) {
-                const int v0 = 16 * s4 + 4 * kq;
-                a[s4] = (c < cin && v0 < nodes) ? ld4(in + (c * NP + t) * nodes + v0) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            f32x4 acc[VP / 16];
-#pragma unroll
-            for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float *At = p.AT + (size_t)t * VP * VP;
-#pragma unroll
-            for (int s4 = 0; s4 < VP / 16; ++s4) {
-                float4 bw[VP / 16];
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) bw[wt] = ld4(At + (wt * 16 + li) * VP + 16 * s4 + 4 * kq);
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4].x, bw[wt].x, acc[wt], 0, 0, 0);
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4].y, bw[wt].y, acc[wt], 0, 0, 0);
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4].z, bw[wt].z, acc[wt], 0, 0, 0);
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4].w, bw[wt].w, acc[wt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int wt = 0; wt < VP / 16; ++wt) {
-                const int w = wt * 16 + li;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int cc = mt * 16 + kq * 4 + r;
-                    if (cc < cin && w < nodes) in[(cc * NP + t) * nodes + w] = acc[wt][r];
-                }
-            }
-        }
+        spatial_mix<NP, VP>(in, p.AT, cin, nodes);
         __syncthreads();
     }
     conv1x1<true>(in, out, p.Wt, p.bt, cin, cout, npos, p.prelu);   // tcn (BN folded) + res, PReLU
@@ -171,17 +72,15 @@ __device__ inline void st_gcn_layer(float *in, float *out, const LayerP &p, int 
 
 // run one 4-layer stack; input (9 ch) must already sit at pool[0 ..); returns pointer to the 9-ch output
 __device__ inline float *run_stack(float *pool, const idf_objproj &op, const float *arena, int stack, int nodes) {
-    const int plane = NP * nodes;
     float *start = pool, *end = pool + (POOL_CH - 32) * PLANE;   // 32-channel tensors live at the END
     float *cur = start;
     for (int l = 0; l < 4; ++l) {
         const int li = stack * 4 + l, cin = op.cin[li], cout = op.cout[li];
         float *nxt = (cur == start) ? end : start;
-        const LayerP p = layer_params(arena + op.layer[li], cin, cout, nodes, stack == 2);
+        const LayerP p = layer_params<NP, VP>(arena + op.layer[li], cin, cout, nodes, stack == 2);
         st_gcn_layer(cur, nxt, p, cin, cout, nodes, stack == 2);
         cur = nxt;
     }
-    (void)plane;
     return cur;
 }
 

@@ -16,16 +16,14 @@
 // temporal mix on the VALU.  The idx_pad repetition of the last past frame is folded into dct_pad [n_pre][past_len] (only the past
 // pose rows and the past body frames enter the relative and object branches), and the IDCT is evaluated for node 0 only
 // (correction_skeleton.py:130 reads nothing else).
-//
-// Arena layer block (pack_skeleton_objprojector), cinp/coutp = channels rounded up to 16 (zero padded):
-//   version 0 (stacks 0, 1): Tm[n_pre][n_pre]
-//   version 2 (stack 2):     Tm[nodes][n_pre][n_pre], AT[n_pre][32][32]  (A transposed: [t][w][v], zero padded)
-//   then Wt[coutp][cinp], bt[coutp], Wr[coutp][cinp], br[coutp], prelu[1]
+// The ST-GCN layer's arena block and its three products (1x1 convolution tile, temporal mix, adjacency product): csrc/stgcn.h.
 #pragma once
-#include "common.h"
+#include "stgcn.h"
 #include "rot_math.h"
 
 namespace idf_skel_dev {
+
+using namespace idf_stgcn;
 
 constexpr int NP = 20;                     // n_pre = T = past_len + future_len
 constexpr int J = 21;                      // body joints
@@ -35,56 +33,11 @@ constexpr int CH = 9;                      // 6D rotation | translation
 constexpr int MAXC = 64;                   // widest layer
 constexpr int C_TOK = 106;                 // token channels: body 63 | object keypoints 36 | pose 7
 constexpr int N_OBJ = 12;                  // object keypoints
-constexpr int NTHR = 1024, NWAVE = NTHR / 64;
 constexpr int SK_MAXT = 7;                 // 16x16 output tiles per wave: ceil(440 / 16) x 64 / 16 = 112 = 7 x 16
 constexpr int BUF = MAXC * NP * NJ;        // the in-place layer buffer
 constexpr int KEEP = CH * NP * NJ;         // [9][n_pre][22]: node 0 = object, 1.. = joints
 constexpr int SMALL = 512;
 constexpr size_t SKEL_LDS = (size_t)(BUF + KEEP + SMALL) * sizeof(float);
-
-__device__ __forceinline__ int pad16(int x) { return (x + 15) & ~15; }
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
-struct LayerP {
-    const float *Tm, *AT, *Wt, *bt, *Wr, *br;
-    float prelu;
-};
-
-__device__ __forceinline__ LayerP layer_params(const float *blk, int cin, int cout, int nodes, bool v2) {
-    const int cinp = pad16(cin), coutp = pad16(cout);
-    LayerP p;
-    p.Tm = blk;
-    blk += v2 ? nodes * NP * NP : NP * NP;
-    p.AT = v2 ? blk : nullptr;
-    if (v2) blk += NP * VP * VP;
-    p.Wt = blk; blk += coutp * cinp;
-    p.bt = blk; blk += coutp;
-    p.Wr = blk; blk += coutp * cinp;
-    p.br = blk; blk += coutp;
-    p.prelu = blk[0];
-    return p;
-}
-
-// one 16x16 tile of a 1x1 convolution over channel-major planes: out[o][pos] = sum_c W[o][c] in[c][pos] (no bias)
-// M = positions mt*16.., N = output channels nt*16.., K = input channels (zero-padded weights); lane (li, kq) gets
-// rows mt*16 + kq*4 + r, column nt*16 + li.
-__device__ __forceinline__ f32x4 conv_tile(const float *in, const float *W, int cin, int npos, int mt, int nt) {
-    const int lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
-    const int cinp = pad16(cin), pos = min(mt * 16 + li, npos - 1);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 4 * kq; c0 < cinp; c0 += 16) {
-        const float4 w = ld4(W + (nt * 16 + li) * cinp + c0);
-        const float a0 = c0 + 0 < cin ? in[(c0 + 0) * npos + pos] : 0.f;
-        const float a1 = c0 + 1 < cin ? in[(c0 + 1) * npos + pos] : 0.f;
-        const float a2 = c0 + 2 < cin ? in[(c0 + 2) * npos + pos] : 0.f;
-        const float a3 = c0 + 3 < cin ? in[(c0 + 3) * npos + pos] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, w.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, w.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, w.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, w.w, acc, 0, 0, 0);
-    }
-    return acc;
-}
 
 // one ST-GCN layer in place on buf = channel-major planes [c][k][node] (plane = NP * nodes floats): cin planes in, cout planes out
 template <bool V2>
@@ -106,71 +59,11 @@ __device__ inline void st_gcn_layer(float *buf, const LayerP &p, int cin, int co
         }
     }
     __syncthreads();
-    // 2a. temporal mixing, in place: y[q] = sum_t x[t] Tm[(v)][t][q]
-    for (int i = threadIdx.x; i < cin * nodes; i += NTHR) {
-        const int c = i / nodes, v = i - c * nodes;
-        float *col = buf + c * npos + v;
-        const float *Tm = p.Tm + (v2 ? v * NP * NP : 0);
-        float y[NP];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) y[q] = 0.f;
-#pragma unroll 2
-        for (int t = 0; t < NP; ++t) {          // (x[t] read as it is needed: the residual tiles are live here, 28 registers)
-            const float xt = col[t * nodes];
-#pragma unroll
-            for (int q = 0; q < NP; q += 4) {
-                const float4 tm = ld4(Tm + t * NP + q);
-                y[q] += xt * tm.x;
-                y[q + 1] += xt * tm.y;
-                y[q + 2] += xt * tm.z;
-                y[q + 3] += xt * tm.w;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NP; ++q) col[q * nodes] = y[q];
-    }
+    // 2. temporal and (version 2) spatial mixing overwrite the input planes in place
+    temporal_mix<NP>(buf, p.Tm, cin, nodes, v2);
     __syncthreads();
     if (v2) {
-        // 2b. spatial mixing on the MFMA, in place: per coefficient t, Y[c][w] = sum_v X[c][t][v] A[t][v][w].  One wave owns the
-        // rows (16 channels, one t) it writes and holds their X fragments in registers before it writes: no barrier inside.
-        const int MT = pad16(cin) >> 4;
-        for (int item = wave; item < MT * NP; item += NWAVE) {
-            const int mt = item / NP, t = item - mt * NP, c = mt * 16 + li;
-            float a[VP / 16][4];
-#pragma unroll
-            for (int s4 = 0; s4 < VP / 16; ++s4)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int v = 16 * s4 + 4 * kq + e;
-                    a[s4][e] = (c < cin && v < nodes) ? buf[(c * NP + t) * nodes + v] : 0.f;
-                }
-            f32x4 acc[VP / 16];
-#pragma unroll
-            for (int wt = 0; wt < VP / 16; ++wt) acc[wt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float *At = p.AT + (size_t)t * VP * VP;
-#pragma unroll
-            for (int s4 = 0; s4 < VP / 16; ++s4) {
-                float4 bw[VP / 16];
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) bw[wt] = ld4(At + (wt * 16 + li) * VP + 16 * s4 + 4 * kq);
-#pragma unroll
-                for (int wt = 0; wt < VP / 16; ++wt) {
-                    acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4][0], bw[wt].x, acc[wt], 0, 0, 0);
-                    acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4][1], bw[wt].y, acc[wt], 0, 0, 0);
-                    acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4][2], bw[wt].z, acc[wt], 0, 0, 0);
-                    acc[wt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4][3], bw[wt].w, acc[wt], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int wt = 0; wt < VP / 16; ++wt) {
-                const int w = wt * 16 + li;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int cc = mt * 16 + kq * 4 + q;
-                    if (cc < cin && w < nodes) buf[(cc * NP + t) * nodes + w] = acc[wt][q];
-                }
-            }
-        }
+        spatial_mix<NP, VP>(buf, p.AT, cin, nodes);
         __syncthreads();
     }
     // 3. tcn (BN folded) + bias + residual, PReLU -- in registers
@@ -214,7 +107,7 @@ __device__ inline void run_stack(float *buf, const idf_skel_objproj &op, int sta
 #pragma unroll 1
     for (int l = 0; l < 4; ++l) {
         const int li = stack * 4 + l;
-        const LayerP p = layer_params(op.arena + op.layer[li], op.cin[li], op.cout[li], nodes, stack == 2);
+        const LayerP p = layer_params<NP, VP>(op.arena + op.layer[li], op.cin[li], op.cout[li], nodes, stack == 2);
         if (stack == 2) st_gcn_layer<true>(buf, p, op.cin[li], op.cout[li], nodes);
         else st_gcn_layer<false>(buf, p, op.cin[li], op.cout[li], nodes);
     }

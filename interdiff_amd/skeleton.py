@@ -7,12 +7,7 @@ the sampling glue ``sample_once_proj`` (eval_skeleton.py:114-142), the correctio
 Tokens are C = 106 channels: body 21 x 3 | object keypoints 12 x 3 | pose [translation 3, quaternion xyzw 4].
 
 ``pack_skeleton_objprojector`` takes the skeleton checkpoint's state_dict (``checkpoints/obj_skeleton.ckpt``, with or without
-the ``model.`` prefix) and folds, on the host in float64:
-  * eval-mode BatchNorm into the preceding 1x1 convolution (tcn.0/tcn.1 and residual.0/residual.1);
-  * the idx_pad frame repetition into ``dct_pad`` [n_pre, past_len];
-  * DCT / IDCT matrices as get_dct_matrix builds them (fp64, inverse by numpy) -> fp32.
-Arena layer block (csrc/skeleton.h): Tm | (A^T padded to 32 x 32 per coefficient, joint stack) | Wt bt Wr br (zero-padded to
-multiples of 16 channels: MFMA operands) | prelu.
+the ``model.`` prefix); what it folds and the arena it writes: ``stgcn_pack.py``, csrc/stgcn.h.
 """
 import ctypes as C
 import itertools
@@ -20,10 +15,9 @@ import numpy as np
 import torch
 from . import _lib
 from .correction import correction_gate
-from .objprojector import dct_matrices, _fold, _np
+from .stgcn_pack import ArenaBuilder, pack_dct, pack_stgcn_layers, unpack_stgcn_layers, to_f64
 from . import mdm as _mdm
 
-STACKS = ('st_gcnns_relative', 'st_gcnns', 'st_gcnns_all')
 N_PRE, N_JOINTS, N_OBJ = 20, 21, 12
 C_TOKENS = 3 * N_JOINTS + 3 * N_OBJ + 7          # 106
 VP = 32                                          # joint-stack nodes (22) padded to 2 MFMA tiles (csrc/skeleton.h)
@@ -49,77 +43,18 @@ def pack_skeleton_objprojector(state_dict, past_len=10, future_len=10):
     T = past_len + future_len
     if T != N_PRE:
         raise ValueError('the skeleton predictor keeps all %d DCT coefficients: past_len + future_len must be %d' % (N_PRE, N_PRE))
-    parts, n = [], [0]
-
-    def add(a):
-        a = np.ascontiguousarray(a, dtype=np.float32).ravel()
-        off = n[0]
-        pad = (-a.size) % 16
-        parts.append(a)
-        if pad:
-            parts.append(np.zeros(pad, np.float32))
-        n[0] += a.size + pad
-        return off
+    ab = ArenaBuilder()
     op = _lib.SkelObjProj()
     op.T, op.past_len, op.J, op.n_pre = T, past_len, N_JOINTS, N_PRE
-    dct, idct = dct_matrices(T)
-    d = dct[:N_PRE]
-    dpad = d[:, :past_len].copy()
-    dpad[:, past_len - 1] = d[:, past_len - 1:].sum(axis=1)
-    op.dct_pad, op.dct, op.idct = add(dpad), add(d), add(idct[:, :N_PRE])
-    for s, name in enumerate(STACKS):
-        for l in range(4):
-            p = '%s.%d' % (name, l)
-            Wt, bt = _fold(sd, p + '.tcn.0', p + '.tcn.1')
-            Wr, br = _fold(sd, p + '.residual.0', p + '.residual.1')
-            cout, cin = Wt.shape
-            cinp, coutp = -(-cin // 16) * 16, -(-cout // 16) * 16
-
-            def padw(W):
-                out = np.zeros((coutp, cinp))
-                out[:cout, :cin] = W
-                return out.ravel()
-
-            def padb(b):
-                out = np.zeros(coutp)
-                out[:cout] = b
-                return out
-            blk = [_np(sd[p + '.gcn.T']).ravel()]
-            if s == 2:
-                A = _np(sd[p + '.gcn.A'])                                  # [n_pre, nodes, nodes] : y[w] = sum_v x[v] A[t][v][w]
-                AT = np.zeros((N_PRE, VP, VP))
-                AT[:, :A.shape[2], :A.shape[1]] = A.transpose(0, 2, 1)     # [t][w][v], zero padded to 32 x 32
-                blk.append(AT.ravel())
-            blk += [padw(Wt), padb(bt), padw(Wr), padb(br), _np(sd[p + '.prelu.weight']).ravel()]
-            op.layer[s * 4 + l] = add(np.concatenate(blk))
-            op.cout[s * 4 + l], op.cin[s * 4 + l] = cout, cin
-    return op, np.concatenate(parts)
+    op.dct_pad, op.dct, op.idct = pack_dct(ab, T, N_PRE, past_len)
+    pack_stgcn_layers(ab, sd, op, N_PRE, VP)
+    return op, ab.arena()
 
 
 def packed_layers(op, arena):
-    """The 12 folded layers back out of a packed arena (numpy, float32), as dicts Tm, A (joint stack), Wt, bt, Wr, br, prelu --
-    what the CPU restatement (tests/skeleton_oracle.py) evaluates to check the packer."""
-    out = []
-    for li in range(12):
-        s, cin, cout = li // 4, op.cin[li], op.cout[li]
-        cinp, coutp = -(-cin // 16) * 16, -(-cout // 16) * 16
-        nodes = N_JOINTS + 1
-        o = op.layer[li]
-        L = {}
-        nT = nodes * N_PRE * N_PRE if s == 2 else N_PRE * N_PRE
-        L['Tm'] = arena[o:o + nT].reshape((nodes, N_PRE, N_PRE) if s == 2 else (N_PRE, N_PRE))
-        o += nT
-        if s == 2:
-            AT = arena[o:o + N_PRE * VP * VP].reshape(N_PRE, VP, VP)
-            L['A'] = AT[:, :nodes, :nodes].transpose(0, 2, 1)
-            o += N_PRE * VP * VP
-        L['Wt'] = arena[o:o + coutp * cinp].reshape(coutp, cinp)[:cout, :cin]; o += coutp * cinp
-        L['bt'] = arena[o:o + cout]; o += coutp
-        L['Wr'] = arena[o:o + coutp * cinp].reshape(coutp, cinp)[:cout, :cin]; o += coutp * cinp
-        L['br'] = arena[o:o + cout]; o += coutp
-        L['prelu'] = arena[o]
-        out.append(L)
-    return out
+    """The 12 folded layers back out of a packed arena (numpy, float32): what the CPU restatement (tests/skeleton_oracle.py)
+    evaluates to check the packer."""
+    return unpack_stgcn_layers(op, arena, N_PRE, VP, N_JOINTS + 1)
 
 
 class SkeletonObjProjector:
@@ -290,7 +225,7 @@ def skeleton_state_dict_for_pack(state_dict):
     """The skeleton model's state_dict in the shape ``mdm.pack_mdm_weights`` packs: feed-forward blocks zero-padded to width 1024
     (``pad_ffn_width``), objEmbedding with 7 zero columns for the pose channels the model does not embed (diffusion_skeleton.py:236-238).
     The two head matrices stay as they are (their packed form is ``pack_skeleton_head``).  Returns (dict, ff_size)."""
-    sd = {k: _np(v).astype(np.float32) for k, v in _strip(state_dict).items() if not k.endswith('.pe')}
+    sd = {k: to_f64(v).astype(np.float32) for k, v in _strip(state_dict).items() if not k.endswith('.pe')}
     ff = sd['decoder.layers.0.linear1.weight'].shape[0]
     for k in [k for k in sd if k.endswith('.linear1.weight')]:
         p = k[:-len('linear1.weight')]

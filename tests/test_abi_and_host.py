@@ -96,6 +96,25 @@ def test_pack_objprojector_folds():
     assert list(op.cin) == [9, 32, 16, 32] * 3 and list(op.cout) == [32, 16, 32, 9] * 3
 
 
+def test_pack_objprojector_layers_read_back():
+    """Every layer block of the SMPL arena, read back by the layout csrc/stgcn.h describes, holds the state dict's folded layer in fp32."""
+    from interdiff_amd.objprojector import pack_objprojector, VP
+    from interdiff_amd.stgcn_pack import STACKS, fold_bn, unpack_stgcn_layers
+    sd = fx.objproj_weights()
+    op, arena = pack_objprojector(sd, T=35, past_len=10, device='cpu')
+    layers = unpack_stgcn_layers(op, arena.numpy(), 10, VP, 68)
+    assert len(layers) == 12
+    for li, L in enumerate(layers):
+        p = '%s.%d' % (STACKS[li // 4], li % 4)
+        for (W, b), kw, kb in ((fold_bn(sd, p + '.tcn.0', p + '.tcn.1'), 'Wt', 'bt'), (fold_bn(sd, p + '.residual.0', p + '.residual.1'), 'Wr', 'br')):
+            assert np.array_equal(L[kw], W.astype(np.float32)) and np.array_equal(L[kb], b.astype(np.float32)), (p, kw)
+        assert L['Tm'].shape == ((68, 10, 10) if li >= 8 else (10, 10)) and np.array_equal(L['Tm'], sd[p + '.gcn.T'].numpy().reshape(L['Tm'].shape)), p
+        assert ('A' in L) == (li >= 8)
+        if li >= 8:
+            assert L['A'].shape == (10, 68, 68) and np.array_equal(L['A'], sd[p + '.gcn.A'].numpy()), p
+        assert L['prelu'] == sd[p + '.prelu.weight'].numpy().ravel()[0]
+
+
 def test_gloo_sharding_world2():
     """N>1 path on CPU: clips are sharded over ranks, metrics all-gathered (gloo stands in for RCCL)."""
     import torch.multiprocessing as mp
