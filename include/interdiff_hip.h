@@ -461,6 +461,49 @@ int interdiff_skeleton_metrics(const float *body_pred, const float *body_gt, con
                                const float *obj_gt, const float *pose_pred, const float *pose_gt,
                                int32_t T, int32_t B, int32_t from_frame, float *out4, void *stream);
 
+/* ---- FINE-TUNING of the skeleton predictor with FROZEN normalisation statistics (the reference module in eval() with autograd on: BatchNorm
+ * uses its running statistics and never writes them, dropout is off; train-mode BatchNorm and dropout are NOT built).  Device code:
+ * csrc/skeleton_train.h, launchers csrc/skeleton_train.hip.  Additive entries: interdiff_abi_version() stays what it was.
+ *
+ * PARAMETER TABLE.  `params`, `grads`, `exp_avg`, `exp_avg_sq` are flat fp32 vectors of n_param = 96 110 floats in the order of
+ * ObjProjector.named_parameters(): the stacks st_gcnns_relative, st_gcnns, st_gcnns_all, four layers each, and per layer
+ *     [gcn.A [20][nodes][nodes]  (st_gcnns_all only, nodes = 22)]
+ *     gcn.T [20][20]  (st_gcnns_all: [nodes][20][20])
+ *     tcn.0.weight [cout][cin], tcn.0.bias [cout], tcn.1.weight [cout], tcn.1.bias [cout],
+ *     residual.0.weight [cout][cin], residual.0.bias [cout], residual.1.weight [cout], residual.1.bias [cout], prelu.weight [1].
+ * `bn` is the flat vector of the BatchNorm buffers (n_bn floats, read only -- no entry writes it), per layer
+ *     tcn.1.running_mean, tcn.1.running_var, residual.1.running_mean, residual.1.running_var, [cout] each.
+ * interdiff_skeleton_finetune_param_table writes table[12][16] = per layer the offsets {A (-1 when absent), T, tcn.0.weight, tcn.0.bias,
+ * tcn.1.weight, tcn.1.bias, residual.0.weight, residual.0.bias, residual.1.weight, residual.1.bias, prelu.weight}, then {cin, cout, nodes,
+ * joint-stack flag, offset in bn}; only op's cin / cout are read.  interdiff_amd/skeleton_finetune.py builds the same table from the
+ * state_dict and the tests compare the two.
+ *
+ * interdiff_skeleton_finetune_grads   replaces loss.backward() on LitObjInteraction._common_step (train_correction_skeleton.py:128-154:
+ *      ObjProjector.forward, model/correction_skeleton.py:68-137, then calc_loss :85-126).  op->arena must be the fold of `params` / `bn`
+ *      (interdiff_skeleton_finetune_step keeps it so).  obj_angles [T,B,4], obj_trans [T,B,3], human_points [T,B,21,3] are what
+ *      interdiff_skeleton_objprojector_sample takes (ObjProjector.forward's first quaternion conversion is the caller's, as in
+ *      SkeletonObjProjector.forward); pose_gt [T,B,7] = translation | quaternion xyzw.  weights8: HOST pointer, the 8 loss weights in the order
+ *      rot_past, nonrot_past, rot_future, nonrot_future, rot_v_past, nonrot_v_past, rot_v_future, nonrot_v_future.  -> out9 (device) = loss, the
+ *      8 unweighted terms; grads (device) [n_param] in the reference layout.  One 1024-thread workgroup per clip (forward with saves, loss
+ *      gradient, backward, per-clip partials by plain stores), then the fold over clips in ascending order and the conversion from the folded
+ *      convolutions: no atomics, two calls give the same bits.  IDF_E_INVAL: null pointer, B < 1, T != op->T, short workspace.
+ *      PRECISION: the layers run in fp32 on the VALU with compensated sums (not the MFMA forward of interdiff_skeleton_objprojector_sample); the head
+ *      of 20 threads per clip (pose from the network output, pose error, loss gradient, backward of matrix_to_quaternion and rotation_6d_to_matrix)
+ *      and the input quaternion -> 6D conversion run in DOUBLE, rounded once -- a departure from fp32-throughout taken to keep every gradient tensor
+ *      within 4x the reference's own fp32 error of the fp64 gradient.  The loss therefore agrees with the inference kernels' to ~1e-7 relative, not in bits.
+ * interdiff_skeleton_finetune_step    replaces optimizer.step() of torch.optim.Adam(lr, betas, eps, weight_decay) (:41-47), torch's order of
+ *      operations, weight decay added to the gradient; `step` = 1 for the first step.  Updates params / exp_avg / exp_avg_sq in place and re-folds
+ *      params into `arena` (the float arena op->layer[] indexes; folded in double without contraction, like the host packer).
+ * ---------------------------------------------------------------------------------- */
+int interdiff_skeleton_finetune_param_table(const idf_skel_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn);
+size_t interdiff_skeleton_finetune_workspace_bytes(const idf_skel_objproj *op, int32_t B);
+int interdiff_skeleton_finetune_grads(const idf_skel_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                      const float *obj_trans, const float *human_points, const float *pose_gt, int32_t B, int32_t T,
+                                      const float *weights8, float *out9, float *grads, void *ws, size_t ws_bytes, void *stream);
+int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, float *arena, float *params, const float *bn, const float *grads,
+                                     float *exp_avg, float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps,
+                                     double weight_decay, void *stream);
+
 /* ---- the skeleton DENOISER (model/diffusion_skeleton.py MDM): the decoder / encoder of idf_mdm_weights with token width
  * C = n_body + 3 n_points + 7 = 106 (W_in = [bodyEmbedding | objEmbedding | 7 zero columns], feed-forward width <= 1024 zero-padded
  * into the 1024-wide streams) and a KEYPOINT HEAD instead of two plain linears: bodyFinalLinear gives the n_body body channels,

@@ -137,6 +137,11 @@ _SIGS = {
     'interdiff_skeleton_objprojector_sample': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, vp, vp, vp]),
     'interdiff_skeleton_correction': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, i32, i32, f32, vp, vp]),
     'interdiff_skeleton_metrics': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    'interdiff_skeleton_finetune_param_table': (C.c_int, [C.POINTER(SkelObjProj), vp, C.POINTER(i32), C.POINTER(i32)]),
+    'interdiff_skeleton_finetune_workspace_bytes': (sz, [C.POINTER(SkelObjProj), i32]),
+    'interdiff_skeleton_finetune_grads': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(f32), vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_finetune_step': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                   C.c_double, vp]),
     'interdiff_skeleton_mdm_forward': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_encode_workspace_bytes': (sz, [i32, i32]),

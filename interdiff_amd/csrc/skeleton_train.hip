@@ -1,0 +1,258 @@
+// Fine-tuning of the skeleton correction predictor with frozen normalisation statistics: launchers of the clip kernel (csrc/skeleton_train.h) and the
+// kernels around it -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients to the reference
+// parameters, Adam (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference kernels read.
+#include <math.h>
+#include "skeleton_train.h"
+
+namespace {
+using namespace idf_skel_train;
+
+constexpr int FT_THR = 256;
+constexpr float BN_EPS = 1e-5f;
+
+__global__ __launch_bounds__(NTHR) void skel_ft_clip_kernel(const idf_skel_objproj op, const Src s, const FtPlan plan, const FtArgs a, int B) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    ft_clip_body(sm, op, s, plan, a, B, blockIdx.x);
+}
+
+// gsum[i] = sum_b partials[b][i], b ascending; block 0 also folds the loss: out9 = loss, the 8 terms
+struct LossK {
+    float w[8], inv_n[8];      // the 8 weights, 1 / (frames * B * width) of each mean
+};
+__global__ __launch_bounds__(FT_THR) void skel_ft_fold_kernel(const float *__restrict__ partials, const float *__restrict__ loss_part, int B, int n_param,
+                                                             const LossK lk, float *__restrict__ gsum, float *__restrict__ out9) {
+    const int i = blockIdx.x * FT_THR + threadIdx.x;
+    if (i < n_param) {
+        Acc2 a;
+        for (int b = 0; b < B; ++b) a.add(partials[(size_t)b * n_param + i]);
+        gsum[i] = a.value();
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float loss = 0.f;
+        for (int k = 0; k < 8; ++k) {
+            float a = 0.f;
+            for (int b = 0; b < B; ++b) a += loss_part[(size_t)b * 8 + k];
+            a *= lk.inv_n[k];
+            out9[1 + k] = a;
+            loss += lk.w[k] * a;
+        }
+        out9[0] = loss;
+    }
+}
+
+// one block per layer: gradients of the folded (W s, (b - mu) s + beta), s = gamma / sqrt(var + eps), back to conv weight / bias and BN gamma / beta;
+// T, A and the PReLU slope pass through
+__global__ __launch_bounds__(FT_THR) void skel_ft_convert_kernel(const FtPlan plan, const float *__restrict__ gsum, const float *__restrict__ params,
+                                                                const float *__restrict__ bn, float *__restrict__ grads) {
+    const FtLayer &L = plan.L[blockIdx.x];
+    const int tid = threadIdx.x, cin = L.cin, cout = L.cout;
+    const int nT = (L.v2 ? L.nodes : 1) * NP * NP;
+    if (L.v2)
+        for (int i = tid; i < NP * L.nodes * L.nodes; i += FT_THR) grads[L.A + i] = gsum[L.A + i];
+    for (int i = tid; i < nT; i += FT_THR) grads[L.T + i] = gsum[L.T + i];
+    if (tid == 0) grads[L.pr] = gsum[L.pr];
+    for (int br = 0; br < 2; ++br) {
+        const int W = br ? L.Wr : L.Wt, bb = br ? L.br : L.bt, ga = br ? L.gr : L.gt, be = br ? L.ber : L.bet;
+        const float *mu = bn + L.bn + 2 * br * cout, *var = mu + cout;
+        for (int i = tid; i < cout * cin; i += FT_THR) {
+            const int o = i / cin;
+            const float s = params[ga + o] / sqrtf(var[o] + BN_EPS);
+            grads[W + i] = gsum[W + i] * s;
+        }
+        for (int o = tid; o < cout; o += FT_THR) {
+            const float r = 1.0f / sqrtf(var[o] + BN_EPS), db = gsum[bb + o];
+            Acc2 a;
+            for (int c = 0; c < cin; ++c) a.mac(gsum[W + o * cin + c], params[W + o * cin + c]);
+            a.mac(db, params[bb + o] - mu[o]);
+            grads[bb + o] = db * (params[ga + o] * r);
+            grads[be + o] = db;
+            grads[ga + o] = r * a.value();
+        }
+    }
+}
+
+// torch.optim.Adam (torch/optim/adam.py _single_tensor_adam): grad += wd * p; exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) grad^2;
+// denom = sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps; p += -(lr / (1 - beta1^step)) * exp_avg / denom
+struct AdamK {
+    float w1, beta2, w2, step_size, bc2_sqrt, eps, wd;
+    int use_wd;
+};
+__global__ __launch_bounds__(FT_THR) void skel_ft_adam_kernel(float *__restrict__ p, const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v, int n,
+                                                             const AdamK k) {
+    const int i = blockIdx.x * FT_THR + threadIdx.x;
+    if (i >= n) return;
+    float g = grad[i];
+    const float pi = p[i];
+    if (k.use_wd) g = g + k.wd * pi;
+    float mi = m[i], vi = v[i];
+    mi = mi + k.w1 * (g - mi);
+    vi = vi * k.beta2 + k.w2 * g * g;
+    const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi + (-k.step_size) * (mi / denom);
+}
+
+// one block per layer: the arena layer block (csrc/stgcn.h) from the master parameters, folded in double exactly as stgcn_pack.fold_bn does on the host
+// (no contraction: W * s and (b - mu) * s + beta round once per operation); padding stays what the host packer wrote (zero)
+__device__ __forceinline__ double ft_scale(float gamma, float var) {
+#pragma clang fp contract(off)
+    return (double)gamma / sqrt((double)var + 1e-5);
+}
+__device__ __forceinline__ float ft_fold_w(float w, double s) {
+#pragma clang fp contract(off)
+    return (float)((double)w * s);
+}
+__device__ __forceinline__ float ft_fold_b(float b, float mu, double s, float beta) {
+#pragma clang fp contract(off)
+    const double t = ((double)b - (double)mu) * s;
+    return (float)(t + (double)beta);
+}
+__global__ __launch_bounds__(FT_THR) void skel_ft_refold_kernel(const idf_skel_objproj op, const FtPlan plan, const float *__restrict__ params,
+                                                               const float *__restrict__ bn, float *__restrict__ arena) {
+    const int li = blockIdx.x;
+    const FtLayer &L = plan.L[li];
+    const int tid = threadIdx.x, cin = L.cin, cout = L.cout, nodes = L.nodes, cinp = pad16(cin), coutp = pad16(cout);
+    const int nT = (L.v2 ? nodes : 1) * NP * NP;
+    float *blk = arena + op.layer[li];
+    for (int i = tid; i < nT; i += FT_THR) blk[i] = params[L.T + i];
+    blk += pad16(nT);
+    if (L.v2) {
+        for (int i = tid; i < NP * nodes * nodes; i += FT_THR) {
+            const int t = i / (nodes * nodes), r = i - t * nodes * nodes, v = r / nodes, w = r - v * nodes;
+            blk[(t * VP + w) * VP + v] = params[L.A + i];
+        }
+        blk += NP * VP * VP;
+    }
+    for (int br = 0; br < 2; ++br) {
+        const int W = br ? L.Wr : L.Wt, bb = br ? L.br : L.bt, ga = br ? L.gr : L.gt, be = br ? L.ber : L.bet;
+        const float *mu = bn + L.bn + 2 * br * cout, *var = mu + cout;
+        for (int i = tid; i < cout * cin; i += FT_THR) {
+            const int o = i / cin, c = i - o * cin;
+            blk[o * cinp + c] = ft_fold_w(params[W + i], ft_scale(params[ga + o], var[o]));
+        }
+        blk += coutp * cinp;
+        for (int o = tid; o < cout; o += FT_THR) blk[o] = ft_fold_b(params[bb + o], mu[o], ft_scale(params[ga + o], var[o]), params[be + o]);
+        blk += coutp;
+    }
+    if (tid == 0) blk[0] = params[L.pr];
+}
+
+// the channel widths the kernels were built for (all the parameter table needs)
+int ft_check_widths(const idf_skel_objproj *op) {
+    if (!op || op->n_pre != NP || op->T != NP || op->J != J) return IDF_E_INVAL;
+    for (int st = 0; st < 3; ++st) {
+        if (op->cin[st * 4] != CH || op->cout[st * 4 + 3] != CH) return IDF_E_INVAL;
+        for (int l = 0; l < 4; ++l) {
+            const int li = st * 4 + l;
+            if (op->cin[li] < 1 || op->cin[li] > MAXC || op->cout[li] < 1 || op->cout[li] > MAXC) return IDF_E_INVAL;
+            if (l < 3 && op->cout[li] != op->cin[li + 1]) return IDF_E_INVAL;
+        }
+    }
+    return IDF_OK;
+}
+
+int ft_check(const idf_skel_objproj *op, int B) {
+    if (ft_check_widths(op) != IDF_OK || !op->arena || B < 1 || op->past_len < 1 || op->past_len > 10) return IDF_E_INVAL;
+    for (int li = 0; li < 12; ++li)
+        if (op->layer[li] < 0) return IDF_E_INVAL;
+    return IDF_OK;
+}
+
+// workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]
+struct FtWs {
+    size_t partials, loss_part, gsum, clips, total;
+};
+FtWs ft_ws(const FtPlan &P, int B) {
+    FtWs w{};
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
+    w.partials = take((size_t)B * P.n_param);
+    w.loss_part = take((size_t)B * 8);
+    w.gsum = take((size_t)P.n_param);
+    w.clips = take((size_t)B * P.ws_clip);
+    w.total = o;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int interdiff_skeleton_finetune_param_table(const idf_skel_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn) {
+    if (!table || !n_param || !n_bn || ft_check_widths(op) != IDF_OK) return IDF_E_INVAL;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    for (int li = 0; li < 12; ++li) {
+        const int32_t *src = reinterpret_cast<const int32_t *>(&P.L[li]);
+        for (int k = 0; k < FT_TABLE_COLS; ++k) table[li * FT_TABLE_COLS + k] = src[k];
+    }
+    *n_param = P.n_param;
+    *n_bn = P.n_bn;
+    return IDF_OK;
+}
+
+extern "C" size_t interdiff_skeleton_finetune_workspace_bytes(const idf_skel_objproj *op, int32_t B) {
+    if (!op || B < 1) return 0;
+    return ft_ws(ft_plan(op->cin, op->cout), B).total * sizeof(float);
+}
+
+extern "C" int interdiff_skeleton_finetune_grads(const idf_skel_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                                 const float *obj_trans, const float *human_points, const float *pose_gt, int32_t B, int32_t T,
+                                                 const float *weights8, float *out9, float *grads, void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !bn || !obj_angles || !obj_trans || !human_points || !pose_gt || !weights8 || !out9 || !grads || !ws) return IDF_E_INVAL;
+    if (ft_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    const FtWs W = ft_ws(P, B);
+    if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
+    float *base = static_cast<float *>(ws);
+    hipStream_t st = idf_stream(stream);
+    const int past = op->past_len, fut = T - past;
+    LossK lk;
+    FtArgs a{};
+    for (int k = 0; k < 8; ++k) {
+        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 4;
+        const double n = frames * (double)B * width;
+        lk.w[k] = weights8[k];
+        lk.inv_n[k] = (float)(1.0 / n);
+        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
+    }
+    a.pose_gt = pose_gt;
+    a.partials = base + W.partials;
+    a.loss_part = base + W.loss_part;
+    a.ws_clips = base + W.clips;
+    Src s{};
+    s.angles = obj_angles; s.trans = obj_trans; s.human = human_points;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (idf_opt_in_lds(reinterpret_cast<const void *>(skel_ft_clip_kernel), (int)FT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(skel_ft_clip_kernel, dim3(B), dim3(NTHR), FT_LDS, st, *op, s, P, a, B);
+    hipLaunchKernelGGL(skel_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+                       lk, base + W.gsum, out9);
+    hipLaunchKernelGGL(skel_ft_convert_kernel, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+extern "C" int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, float *arena, float *params, const float *bn, const float *grads, float *exp_avg,
+                                                float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                                void *stream) {
+    if (!arena || !params || !bn || !grads || !exp_avg || !exp_avg_sq || step < 1 || ft_check(op, 1) != IDF_OK) return IDF_E_INVAL;
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return IDF_E_INVAL;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    hipStream_t st = idf_stream(stream);
+    AdamK k;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    k.w1 = (float)(1.0 - beta1);
+    k.beta2 = (float)beta2;
+    k.w2 = (float)(1.0 - beta2);
+    k.step_size = (float)(lr / bc1);
+    k.bc2_sqrt = (float)sqrt(bc2);
+    k.eps = (float)eps;
+    k.wd = (float)weight_decay;
+    k.use_wd = weight_decay != 0.0;
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(skel_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
+    hipLaunchKernelGGL(skel_ft_refold_kernel, dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
