@@ -739,6 +739,63 @@ int interdiff_contact_labels(const float *verts, int64_t N, int32_t V, const int
 int interdiff_debug_point_triangle(const float *tri, const float *p, float *out, int32_t n);
 
 /* ------------------------------------------------------------------------------------
+ * Mesh rendering (csrc/render.hip, csrc/render.h): the pictures of interdiff/render/mesh_viz.py (visualize_body_obj) without pyrender / EGL -- a tiled
+ * software rasteriser whose integer stage is exact by construction.  Additive.  The contract (sub-pixel grid, fill rule, depth key, bit widths) is the
+ * head comment of csrc/render.h; tests/render_oracle.py restates it in numpy.
+ *  idf_render_scene   off: subtracted after the negation of a moving mesh's coordinates (scene = -p - off); cam_t, cam_cos, cam_sin: camera position and
+ *      downward pitch (pose = translate(cam_t) . rotate_x(-pitch)); znear; focal = 1 / tan(yfov / 2); light [3][3]: unit vectors TOWARDS the three
+ *      directional lights; shade = min(1, ambient + light_gain * sum max(0, n . L)); bg: background colour in [0, 1].
+ *  idf_render_mesh    verts, normals f32 [frames][V][3] (frames = 1: shared by all frames, or N); faces int32 [F][3], every index in [0, V);
+ *      rgb f32 [N][3] base colour per frame, or [V][3] per vertex with IDF_RMESH_VERTEX_RGB; R f32 [N][9] row-major and t f32 [N][3], both or
+ *      neither: verts and normals are posed per frame inside the setup stage (p R^T + t, rounded left to right as interdiff_contact_labels does).
+ *      IDF_RMESH_SCENE_SPACE: the mesh is given in scene coordinates and does not turn with the views (the ground).
+ *  interdiff_render_frames   N frames x `views` images (view v turns the moving meshes v quarter turns about +y), H x W pixels each.
+ *      out_rgb uint8 [N][views][H][W][3]; out_id (nullable) int32 [N][views][H][W] = the winning slot, -1 background (slot = 2 * source triangle (+ 1),
+ *      source triangles numbered through the meshes in the order given); out_depth (nullable) int32, 0x7fffffff background; out_setup (nullable)
+ *      int32 [N][views][2 * sum F][20], the setup records.  dropped (HOST, nullable): slots whose snapped coordinates left the guard band -- counted,
+ *      never clamped, the rest of the scene is drawn.  stage_ms (HOST, nullable) f32 [3]: setup + count, scan + fill, tile + resolve, hip events
+ *      (tile and resolve are ONE kernel -- the resolve reads the tile's keys out of LDS -- so they cannot be timed apart).
+ *      ws >= interdiff_render_frames_workspace_bytes(1, ...): images are rendered in as many chunks as the workspace asks for, with identical bits.
+ *      Integer atomics only (LDS 64-bit min, global 32-bit add); nothing depends on their order: two calls give the same bits.  The call
+ *      synchronises the stream (face check up front, counter at the end).
+ *      IDF_E_INVAL: null pointer, a data pointer that is not 4-byte aligned or a ws that is not 256-byte aligned (hipMalloc's and torch's are), N / views / H / W out of range (views 1..4, H, W 1..IDF_RENDER_MAX_DIM), no mesh or more
+ *      than IDF_RENDER_MAX_MESHES, V or F non-positive, frames neither 1 nor N, one of R / t without the other, a face index outside [0, V);
+ *      IDF_E_NOMEM: a workspace that does not hold one image.  Nothing is written in either case.
+ *  interdiff_debug_render_setup_vertex / _pixel   HOST-side instances of the setup stage's per-vertex function and of the per-pixel coverage / depth /
+ *      colour function.  vertex: pos, nrm, rgb f32 [n][3] -> out_f f32 [n][6] = xc, yc, d, r, g, b and out_i int32 [n][7] = in front of the near
+ *      plane, X, Y, Z, R, G, B (0 when behind).  pixel: rec int32 [n][20], ij int32 [n][2] -> out int32 [n][5] = covered, depth, r, g, b.
+ * ---------------------------------------------------------------------------------- */
+#define IDF_RENDER_SUBPIX 16
+#define IDF_RENDER_GUARD 32768
+#define IDF_RENDER_MAX_DIM 2048
+#define IDF_RENDER_ZONE (1 << 28)
+#define IDF_RENDER_REC_INTS 20
+#define IDF_RENDER_TILE 16
+#define IDF_RENDER_MAX_MESHES 8
+enum { IDF_RMESH_SCENE_SPACE = 1, IDF_RMESH_VERTEX_RGB = 2 };
+typedef struct {
+    float off[3], cam_t[3];
+    float cam_cos, cam_sin, znear, focal;
+    float light[9];
+    float light_gain, ambient;
+    float bg[3];
+    float reserved;
+} idf_render_scene;
+typedef struct {
+    const float *verts, *normals;
+    const int32_t *faces;
+    const float *rgb, *R, *t;
+    int32_t V, F, frames, flags;
+} idf_render_mesh;
+size_t interdiff_render_frames_workspace_bytes(int64_t n_images, int64_t n_triangles, int32_t H, int32_t W);
+int interdiff_render_frames(const idf_render_scene *scene, const idf_render_mesh *meshes, int32_t n_meshes, int64_t N, int32_t views, int32_t H,
+                            int32_t W, uint8_t *out_rgb, int32_t *out_id, int32_t *out_depth, int32_t *out_setup, int64_t *dropped, float *stage_ms,
+                            void *ws, size_t ws_bytes, void *stream);
+int interdiff_debug_render_setup_vertex(const idf_render_scene *scene, int32_t view, int32_t scene_space, int32_t H, int32_t W, const float *pos,
+                                        const float *nrm, const float *rgb, float *out_f, int32_t *out_i, int32_t n);
+int interdiff_debug_render_pixel(const int32_t *rec, const int32_t *ij, int32_t *out, int32_t n);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

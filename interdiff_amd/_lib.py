@@ -88,6 +88,19 @@ class OptState(C.Structure):
     _fields_ = [('B', i32), ('T', i32), ('P', i32), ('max_iters', i32)] + [(k, vp) for k in _OPT_PTRS] + [('smpl_ws_bytes', sz), ('porder', vp), ('psort', vp), ('pbox', vp)]
 
 
+class RenderScene(C.Structure):
+    _fields_ = [('off', f32 * 3), ('cam_t', f32 * 3), ('cam_cos', f32), ('cam_sin', f32), ('znear', f32), ('focal', f32),
+                ('light', f32 * 9), ('light_gain', f32), ('ambient', f32), ('bg', f32 * 3), ('reserved', f32)]
+
+
+class RenderMesh(C.Structure):
+    _fields_ = [('verts', vp), ('normals', vp), ('faces', vp), ('rgb', vp), ('R', vp), ('t', vp),
+                ('V', i32), ('F', i32), ('frames', i32), ('flags', i32)]
+
+
+RMESH_SCENE_SPACE, RMESH_VERTEX_RGB = 1, 2                 # idf_render_mesh.flags (IDF_RMESH_*)
+RENDER_SUBPIX, RENDER_GUARD, RENDER_MAX_DIM, RENDER_ZONE, RENDER_REC_INTS, RENDER_TILE = 16, 32768, 2048, 1 << 28, 20, 16
+
 _SIGS = {
     'interdiff_abi_version': (C.c_int, []),
     'interdiff_build_info': (C.c_char_p, []),
@@ -158,6 +171,11 @@ _SIGS = {
     'interdiff_contact_labels_workspace_bytes': (sz, [i64, i32, i32, i32]),
     'interdiff_contact_labels': (C.c_int, [vp, i64, i32, vp, i32, vp, i32, i64, vp, vp, f32, vp, vp, vp, vp, sz, vp]),
     'interdiff_debug_point_triangle': (C.c_int, [vp, vp, vp, i32]),
+    'interdiff_render_frames_workspace_bytes': (sz, [i64, i64, i32, i32]),
+    'interdiff_render_frames': (C.c_int, [C.POINTER(RenderScene), C.POINTER(RenderMesh), i32, i64, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f32),
+                                          vp, sz, vp]),
+    'interdiff_debug_render_setup_vertex': (C.c_int, [C.POINTER(RenderScene), i32, i32, i32, i32, vp, vp, vp, vp, vp, i32]),
+    'interdiff_debug_render_pixel': (C.c_int, [vp, vp, vp, i32]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),

@@ -12,6 +12,7 @@ elementwise adds outside it: the rendering-only ``smooth`` and the translation r
 ``sample_long``.
 """
 import ctypes as C
+import os
 import torch
 from . import _lib, dist, io, transforms as tr
 from .dist import METRIC_KEYS
@@ -301,3 +302,25 @@ def sample_long_sharded(model, diffusion, correction, raw, windows, past_len=10,
     sl = dist.shard_slice(B, rank, world)
     local = dist.shard_batch(raw, rank, world, RAW_DIMS)
     return sl, sample_long(model, diffusion, correction, local, windows, past_len, mode, seed=seed, shard=(sl.start, B), **kw)
+
+
+def visualize(batch, j, obj, verts, faces, obj_mesh, name, save_dir, past_len, sample_rate=1, h=512, w=512):
+    """eval_smpl_short.py:305-331 ``visualize``: the GIF of one sample.  obj [T,6] = axis-angle | translation per frame, verts [T,V,3] body vertices,
+    faces [F,3]; obj_mesh = (vertices [Vo,3], faces [Fo,3]) of the clip's object (the reference loads it from its object directory by
+    batch['obj_name']; here the caller hands it in).  The object mesh is centred on its vertex mean and posed per frame INSIDE the render kernel from
+    axis_angle_to_matrix(obj[t, :3]) and obj[t, 3:].  Written to save_dir/render/s{start_frame}_l{T}_r{sample_rate}_{j}_{name}.gif; returns
+    (path, video uint8 [T,3,h,4w])."""
+    from . import render
+    dev = verts.device
+    ov = torch.as_tensor(obj_mesh[0]).to(device=dev, dtype=torch.float32)
+    ov = ov - ov.mean(dim=0, keepdim=True)
+    obj = obj.detach().to(device=dev, dtype=torch.float32)
+    R = tr.axis_angle_to_matrix(obj[:, :3].contiguous())
+    out_dir = os.path.join(str(save_dir), 'render')
+    os.makedirs(out_dir, exist_ok=True)
+    start = batch['start_frame'][0]
+    start = int(start) if isinstance(start, torch.Tensor) else start
+    path = os.path.join(out_dir, 's{}_l{}_r{}_{}_{}.gif'.format(start, obj.shape[0], sample_rate, j, name))
+    video = render.visualize_body_obj(verts.detach(), faces, ov, obj_mesh[1], past_len=past_len, save_path=path, sample_rate=sample_rate, h=h, w=w,
+                                      obj_R=R, obj_t=obj[:, 3:].contiguous())
+    return path, video
