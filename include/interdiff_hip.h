@@ -291,6 +291,17 @@ int interdiff_randn_at(float *out, int64_t n, uint64_t seed, uint64_t step_index
 int interdiff_posterior_step_dev(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
                                  const float *table, int64_t *state, int64_t *ts, int32_t B, void *stream);
 int interdiff_sampler_advance(int64_t *state, int64_t *ts, int32_t B, void *stream);
+/* Respaced schedules (diffusion/respace.py:64-129: SpacedDiffusion keeps a subset of the base process's timesteps and
+ * _WrappedModel.__call__, :124-126, hands the MODEL map_tensor[ts] while everything else -- coefficient tables, denoised_fn, the
+ * loop -- counts spaced steps).  tmap int64[steps] = timestep_map: the model's timestep of every loop-side step.  The _map entries are
+ * the un-suffixed ones with one change: where those write ts[b] = max(t - 1, 0), these write ts[b] = tmap[max(t - 1, 0)].  state[0],
+ * the table row, the parked {t, loop index} (state[4..5]) and the Philox step index stay LOOP-side values; ts holds MODEL timesteps
+ * (the caller starts a sample with ts[b] = tmap[t_start]).  tmap == NULL is the identity: the un-suffixed entries call these with
+ * NULL and keep their results bit for bit.  A DDIM sampler (gaussian_diffusion.py:738-788, ddim_sample) needs no entry of its own:
+ * for an x0-predicting model its update is linear in (x0, x_t, noise), so its rows go into the same table {c1, c2, sigma, t/1000}. */
+int interdiff_posterior_step_dev_map(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
+                                     const float *table, const int64_t *tmap, int64_t *state, int64_t *ts, int32_t B, void *stream);
+int interdiff_sampler_advance_map(int64_t *state, int64_t *ts, const int64_t *tmap, int32_t B, void *stream);
 /* One PLAIN reverse step (no denoised_fn hook) = interdiff_mdm_forward + interdiff_posterior_step_dev(ts != NULL) with the x0
  * prediction consumed inside the denoiser's last GEMM: x [B,1,C,T] is the sampler state, updated in place; ts, table, gt, mask as
  * above; state is int64[8] here: [0..3] as above, [4..5] scratch (this step's {t, loop index}, parked by one thread of layer 0's
@@ -317,6 +328,12 @@ int interdiff_mdm_forward_step(const idf_mdm_weights *w, const float *memctx, fl
 int interdiff_mdm_forward_step_ex(const idf_mdm_weights *w, const float *memctx, float *x, int64_t *ts, int32_t B, int32_t T,
                                   const float *gt, const uint8_t *mask, const float *table, int64_t *state, void *ws,
                                   size_t ws_bytes, int32_t flags, void *stream);
+/* interdiff_mdm_forward_step_ex under a respaced schedule: tmap as for interdiff_posterior_step_dev_map (NULL = identity = the entry above); layer 0's QKV
+ * kernel writes ts[b] = tmap[max(t - 1, 0)], which the next step's embedding -- a chained one (IDF_STEP_EMBED_NEXT) included -- looks up unchanged.
+ * Replaces respace.py:124-126 around gaussian_diffusion.py:425-461 (p_sample) / :738-788 (ddim_sample). */
+int interdiff_mdm_forward_step_map(const idf_mdm_weights *w, const float *memctx, float *x, int64_t *ts, int32_t B, int32_t T,
+                                   const float *gt, const uint8_t *mask, const float *table, const int64_t *tmap, int64_t *state,
+                                   void *ws, size_t ws_bytes, int32_t flags, void *stream);
 int interdiff_mdm_step_chaining(const idf_mdm_weights *w);
 /* Every kernel of the library that issues the f16 MFMA claims its CU for itself (all 160 KiB of LDS, the whole register file: DESIGN.md "exclusive CU");
  * since round 5 each launcher VERIFIES that on the device it launches on -- occupancy query == 1, static + dynamic LDS == 160 KiB, >= 256 registers
@@ -529,6 +546,11 @@ int interdiff_skeleton_mdm_forward_step(const idf_mdm_weights *w, const idf_skel
                                         int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
                                         const uint8_t *mask, const float *table, int64_t *state, void *ws, size_t ws_bytes,
                                         void *stream);
+/* ... under a respaced schedule (tmap as for interdiff_posterior_step_dev_map; NULL = the entry above); replaces respace.py:124-126 around it */
+int interdiff_skeleton_mdm_forward_step_map(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
+                                            int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
+                                            const uint8_t *mask, const float *table, const int64_t *tmap, int64_t *state, void *ws,
+                                            size_t ws_bytes, void *stream);
 /* replaces MDM._get_embeddings (diffusion_skeleton.py:194-215): the per-clip additive feature of interdiff_mdm_encode is
  * shapeEmbedding(zero_pose_obj.view(B, 3 n_points)) (one fp32-MFMA GEMM into the workspace), x_past [B,1,C,Tp] holds the past
  * frames (the pose channels meet zero columns of W_in) -> cond [Tp,B,256]. */

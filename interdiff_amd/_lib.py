@@ -127,6 +127,7 @@ _SIGS = {
     'interdiff_mdm_forward': (C.c_int, [C.POINTER(MdmWeights), vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_mdm_forward_step_ex': (C.c_int, [C.POINTER(MdmWeights), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, i32, vp]),
+    'interdiff_mdm_forward_step_map': (C.c_int, [C.POINTER(MdmWeights), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, i32, vp]),
     'interdiff_mdm_step_chaining': (C.c_int, [C.POINTER(MdmWeights)]),
     'interdiff_inpaint': (C.c_int, [vp, vp, vp, i64, vp]),
     'interdiff_posterior_step': (C.c_int, [vp, vp, vp, i64, f32, f32, f32, u64, u64, vp]),
@@ -135,6 +136,8 @@ _SIGS = {
     'interdiff_randn_at': (C.c_int, [vp, i64, u64, u64, u64, vp]),
     'interdiff_posterior_step_dev': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     'interdiff_sampler_advance': (C.c_int, [vp, vp, i32, vp]),
+    'interdiff_posterior_step_dev_map': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp]),
+    'interdiff_sampler_advance_map': (C.c_int, [vp, vp, vp, i32, vp]),
     'interdiff_objprojector_sample': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, vp, vp]),
     'interdiff_objprojector_forward_workspace_bytes': (sz, [i32]),
     'interdiff_objprojector_forward': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
@@ -157,6 +160,7 @@ _SIGS = {
                                                    C.c_double, vp]),
     'interdiff_skeleton_mdm_forward': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_mdm_forward_step_map': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_encode_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_mdm_encode': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_q_sample': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i64, u64, u64, vp]),

@@ -1594,22 +1594,22 @@ void run_skel_heads(hipStream_t s, const Args &g, bool post) {
 // planes / scales != null (with pack_h2): the output leaves as the self-attention's f16 plane pairs + per-row scales instead of fp32 rows (ffn_h2.h ln_linear_h2_kernel<.., PLANES>);
 // the caller has checked (qkv_planes_ok) that this kernel and the attention kernel that reads the planes both run here -- there is no fp32 fallback behind a planes launch
 int run_qkv(hipStream_t s, const Args &g, const float *pack, int np, int64_t *step_state = nullptr, int64_t *step_ts = nullptr,
-            int step_B = 0, const float *pack_h2 = nullptr, float *planes = nullptr, float *scales = nullptr) {
+            int step_B = 0, const float *pack_h2 = nullptr, float *planes = nullptr, float *scales = nullptr, const int64_t *step_tmap = nullptr) {
     if (planes) {
         if (!pack_h2) return IDF_E_INVAL;
-        const int rc = np == NSL ? idf_ffn_h2::launch_ln_linear_h2<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, planes, scales)
-                                 : idf_ffn_h2::launch_ln_linear_h2<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, planes, scales);
+        const int rc = np == NSL ? idf_ffn_h2::launch_ln_linear_h2<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, planes, scales, step_tmap)
+                                 : idf_ffn_h2::launch_ln_linear_h2<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, planes, scales, step_tmap);
         return idf_public_rc(rc);
     }
     if (pack_h2) {
-        const int rc = np == NSL ? idf_ffn_h2::launch_ln_linear_h2<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B)
-                                 : idf_ffn_h2::launch_ln_linear_h2<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B);
+        const int rc = np == NSL ? idf_ffn_h2::launch_ln_linear_h2<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, nullptr, nullptr, step_tmap)
+                                 : idf_ffn_h2::launch_ln_linear_h2<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack_h2, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, nullptr, nullptr, step_tmap);
         if (rc != IDF_NOT_EXCLUSIVE) return rc;        // (not exclusive on this device: the fp32 kernel below)
     }
     if (np == NSL)
-        idf_ffn::launch_ln_linear<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B);
+        idf_ffn::launch_ln_linear<NSL>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, step_tmap);
     else
-        idf_ffn::launch_ln_linear<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B);
+        idf_ffn::launch_ln_linear<1>(s, g.A, g.a_pstride, g.lnw, g.lnb, g.M, g.N, pack, g.bias, g.C, g.ldc, g.xn_out, step_state, step_ts, step_B, step_tmap);
     return IDF_OK;
 }
 
@@ -1637,9 +1637,9 @@ template __global__ void rowblock8_kernel<true, NSL, MEM, 8>(const float *, int,
 template __global__ void idf_attn_h2::self_attn_h2_kernel<0, true>(const float *, int, int, const float *, float *, size_t, const float *);
 template __global__ void idf_ffn_h2::ffn_h2_kernel<2, 4, 0, 8>(const float *, int, int, const float *, const float *, const float *, float *, int);
 template __global__ void idf_ffn_h2::ln_linear_h2_kernel<1, true>(const float *, size_t, int, int, const float *, const float *, const float *, int, int, const float *, float *, int, int, float *,
-                                                                  int64_t *, int64_t *, float *, float *);
+                                                                  int64_t *, int64_t *, float *, float *, const int64_t *);
 template __global__ void idf_ffn_h2::ln_linear_h2_kernel<IDF_FFN_SLICES, true>(const float *, size_t, int, int, const float *, const float *, const float *, int, int, const float *, float *, int,
-                                                                               int, float *, int64_t *, int64_t *, float *, float *);
+                                                                               int, float *, int64_t *, int64_t *, float *, float *, const int64_t *);
 template __global__ void idf_tail_h2::step_tail_h2_kernel<3, false>(const float *, size_t, const float *, int, int, int, int, const idf_tail_h2::TailArgs);
 
 extern "C" int interdiff_mdm_ffn(const idf_mdm_weights *w, int32_t layer, int32_t encoder, const float *x2, int32_t M, float *parts,
@@ -1852,6 +1852,7 @@ struct StepPost {
     const uint8_t *mask;
     const float *table;
     int64_t *state, *ts;
+    const int64_t *tmap;          // respaced schedule: the model's timestep of every loop-side step (philox.h); null = identity
 };
 // the skeleton model's head (interdiff_skeleton_mdm_*): null h = the two plain linears of idf_mdm_weights
 struct SkelHead {
@@ -1950,7 +1951,7 @@ int mdm_forward_impl_t(const idf_mdm_weights *w, const float *memctx, const floa
             const bool planes = attn_h2 && qkv_h2 && ly.qkv_bounds_ok != 0 && qkv_planes_ok(u_np, B, T);
             const bool step0 = post.x && l == 0;
             if (const int rc = run_qkv(s, g, ar + ly.sa_in_pack, u_np, step0 ? post.state : nullptr, step0 ? post.ts : nullptr, step0 ? B : 0, qkv_h2, planes ? k.qkv : nullptr,
-                                       planes ? k.ctx : nullptr); rc != IDF_OK) return rc;
+                                       planes ? k.ctx : nullptr, step0 ? post.tmap : nullptr); rc != IDF_OK) return rc;
             idf_prof_mark(IDF_K_SELF_ATTN, s);
             // u1 = xn + ctx.Wo^T + bo with the product taken per head inside the attention kernel: H partial slabs in the FFN's
             // slab buffer (its previous contents were consumed by the QKV kernel), summed with xn + bo by the row block
@@ -2053,19 +2054,25 @@ extern "C" int interdiff_mdm_forward_step(const idf_mdm_weights *w, const float 
     if (!(T & 3) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 15 || (reinterpret_cast<uintptr_t>(mask) & 3))) return IDF_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 3) return IDF_E_INVAL;
     if (!w || w->layer[0].is_qan) return IDF_E_INVAL;         // the step bookkeeping rides on layer 0's QKV kernel
-    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts});
+    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts, nullptr});
 }
 
 // The same with flags that chain CONSECUTIVE plain steps on one workspace (include/interdiff_hip.h IDF_STEP_*): a step's last launch then also computes
 // the next step's embedding from the token rows it has just updated (tail_h2.h), and the next call starts at its QKV projection.
-extern "C" int interdiff_mdm_forward_step_ex(const idf_mdm_weights *w, const float *memctx, float *x, int64_t *ts, int32_t B, int32_t T,
-                                             const float *gt, const uint8_t *mask, const float *table, int64_t *state, void *ws,
-                                             size_t ws_bytes, int32_t flags, void *stream) {
+extern "C" int interdiff_mdm_forward_step_map(const idf_mdm_weights *w, const float *memctx, float *x, int64_t *ts, int32_t B, int32_t T,
+                                              const float *gt, const uint8_t *mask, const float *table, const int64_t *tmap, int64_t *state,
+                                              void *ws, size_t ws_bytes, int32_t flags, void *stream) {
     if (!x || !ts || !table || !state || (mask && !gt) || T <= 0 || (flags & ~(IDF_STEP_EMBED_READY | IDF_STEP_EMBED_NEXT))) return IDF_E_INVAL;
     if (!(T & 3) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 15 || (reinterpret_cast<uintptr_t>(mask) & 3))) return IDF_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 3) return IDF_E_INVAL;
     if (!w || w->layer[0].is_qan) return IDF_E_INVAL;
-    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts}, flags);
+    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts, tmap}, flags);
+}
+
+extern "C" int interdiff_mdm_forward_step_ex(const idf_mdm_weights *w, const float *memctx, float *x, int64_t *ts, int32_t B, int32_t T,
+                                             const float *gt, const uint8_t *mask, const float *table, int64_t *state, void *ws,
+                                             size_t ws_bytes, int32_t flags, void *stream) {
+    return interdiff_mdm_forward_step_map(w, memctx, x, ts, B, T, gt, mask, table, nullptr, state, ws, ws_bytes, flags, stream);
 }
 
 // The skeleton denoiser (model/diffusion_skeleton.py MDM.forward): the forward above with the keypoint head (skel_head.h) in the last GEMM's epilogue
@@ -2078,15 +2085,22 @@ extern "C" int interdiff_skeleton_mdm_forward(const idf_mdm_weights *w, const id
 }
 
 // ... and its fused plain step: the update covers all C channels of x, the derived keypoint channels included
-extern "C" int interdiff_skeleton_mdm_forward_step(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
-                                                   int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
-                                                   const uint8_t *mask, const float *table, int64_t *state, void *ws, size_t ws_bytes,
-                                                   void *stream) {
+extern "C" int interdiff_skeleton_mdm_forward_step_map(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
+                                                       int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
+                                                       const uint8_t *mask, const float *table, const int64_t *tmap, int64_t *state, void *ws,
+                                                       size_t ws_bytes, void *stream) {
     if (!x || !ts || !table || !state || (mask && !gt) || T <= 0 || !skel_head_ok(w, head, zero_pose_obj)) return IDF_E_INVAL;
     if (!(T & 3) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 15 || (reinterpret_cast<uintptr_t>(mask) & 3))) return IDF_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gt)) & 3) return IDF_E_INVAL;
     if (w->layer[0].is_qan) return IDF_E_INVAL;
-    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts}, 0, SkelHead{head, zero_pose_obj});
+    return mdm_forward_impl(w, memctx, x, ts, B, T, nullptr, ws, ws_bytes, stream, StepPost{x, gt, mask, table, state, ts, tmap}, 0, SkelHead{head, zero_pose_obj});
+}
+
+extern "C" int interdiff_skeleton_mdm_forward_step(const idf_mdm_weights *w, const idf_skel_head *head, const float *memctx, float *x,
+                                                   int64_t *ts, const float *zero_pose_obj, int32_t B, int32_t T, const float *gt,
+                                                   const uint8_t *mask, const float *table, int64_t *state, void *ws, size_t ws_bytes,
+                                                   void *stream) {
+    return interdiff_skeleton_mdm_forward_step_map(w, head, memctx, x, ts, zero_pose_obj, B, T, gt, mask, table, nullptr, state, ws, ws_bytes, stream);
 }
 
 // Encoder side of the skeleton model (MDM._get_embeddings): pc[b] = shapeEmbedding(zero_pose_obj[b]) by the register-staged fp32-MFMA GEMM

@@ -744,11 +744,12 @@ __global__ __launch_bounds__(NT) void ln_linear_kernel(const float *__restrict__
                                                         const float *__restrict__ lnb, int M, const float *__restrict__ pack,
                                                         const float *__restrict__ bias, float *__restrict__ C, int ldc, int N,
                                                         float *__restrict__ xn_out, int64_t *__restrict__ step_state,
-                                                        int64_t *__restrict__ step_ts, int step_B, int nsl_grid) {
+                                                        int64_t *__restrict__ step_ts, int step_B, int nsl_grid,
+                                                        const int64_t *__restrict__ step_tmap) {
     __shared__ __attribute__((aligned(1024))) float smem[XS + 3 * LPSLOT];
     idf_args_now(A, a_pstride, lnw, lnb, M, pack, bias, C, ldc, N, xn_out, step_state, step_ts, step_B, nsl_grid, gridDim.x);
     // sampler bookkeeping of a fused plain step (philox.h): nobody else touches these words while this kernel runs
-    if (step_state && blockIdx.x == 0 && threadIdx.x == 0) sampler_prepare_step(step_state, step_ts, step_B);
+    if (step_state && blockIdx.x == 0 && threadIdx.x == 0) sampler_prepare_step(step_state, step_ts, step_B, step_tmap);
     float *Xs = smem, *ring = smem + XS;
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -863,10 +864,10 @@ __global__ __launch_bounds__(NT) void ln_linear_kernel(const float *__restrict__
 template <int NP>
 inline void launch_ln_linear(hipStream_t s, const float *A, size_t a_pstride, const float *lnw, const float *lnb, int M, int N,
                              const float *pack, const float *bias, float *C, int ldc, float *xn_out, int64_t *step_state = nullptr,
-                             int64_t *step_ts = nullptr, int step_B = 0) {
+                             int64_t *step_ts = nullptr, int step_B = 0, const int64_t *step_tmap = nullptr) {
     const int nsl = (int)idf_cdiv(N, LHS);
     hipLaunchKernelGGL(ln_linear_kernel<NP>, dim3((unsigned)(idf_cdiv(M, BM) * nsl)), dim3(NT), 0, s, A, a_pstride, lnw, lnb,
-                       M, pack, bias, C, ldc, N, xn_out, step_state, step_ts, step_B, nsl);
+                       M, pack, bias, C, ldc, N, xn_out, step_state, step_ts, step_B, nsl, step_tmap);
 }
 
 // rows: 16 / 32 / 64 = the M tile to use; 0 = choose by THIS launch's rows (ffn_tile_for_rows).  The kernels differ in the rounding of one

@@ -564,7 +564,8 @@ __global__ __launch_bounds__(NT) void ln_linear_h2_kernel(const float *__restric
                                                            const float *__restrict__ lnw, const float *__restrict__ lnb, int nsl_grid, int step_B,
                                                            const float *__restrict__ bias, float *__restrict__ C, int ldc, int N,
                                                            float *__restrict__ xn_out, int64_t *__restrict__ step_state,
-                                                           int64_t *__restrict__ step_ts, float *__restrict__ planes_out, float *__restrict__ scales_out) {
+                                                           int64_t *__restrict__ step_ts, float *__restrict__ planes_out, float *__restrict__ scales_out,
+                                                           const int64_t *__restrict__ step_tmap) {
     // (argument order: the first 14 dwords -- what the weight stream and the row requests need -- arrive preloaded in SGPRs: build.py)
     extern __shared__ __attribute__((aligned(1024))) float smem[];
     asm volatile("" ::: "v255");            // exclusive CU, like the feed-forward kernel (see launch_h2_tt)
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(NT) void ln_linear_h2_kernel(const float *__restric
 #pragma unroll
         for (int i = 0; i < QBM / NW; ++i) v[i] = ld4_sum<NP>(A + (size_t)min(m0 + wave + NW * i, M - 1) * D + lane * 4, a_pstride);
         idf_args_now(bias, C, ldc, N, xn_out, step_state, step_ts);      // the rest of the argument segment, behind the requests
-        if (step_state && blockIdx.x == 0 && threadIdx.x == 0) sampler_prepare_step(step_state, step_ts, step_B);
+        if (step_state && blockIdx.x == 0 && threadIdx.x == 0) sampler_prepare_step(step_state, step_ts, step_B, step_tmap);
 #pragma unroll
         for (int i = 0; i < QBM / NW; ++i) {
             const int row = wave + NW * i;
@@ -768,7 +769,8 @@ __global__ __launch_bounds__(NT) void ln_linear_h2_kernel(const float *__restric
 template <int NP>
 inline int launch_ln_linear_h2(hipStream_t s, const float *A, size_t a_pstride, const float *lnw, const float *lnb, int M, int N,
                                const float *pack, const float *bias, float *C, int ldc, float *xn_out, int64_t *step_state = nullptr,
-                               int64_t *step_ts = nullptr, int step_B = 0, float *planes_out = nullptr, float *scales_out = nullptr) {
+                               int64_t *step_ts = nullptr, int step_B = 0, float *planes_out = nullptr, float *scales_out = nullptr,
+                               const int64_t *step_tmap = nullptr) {
     static idf_excl_cache excl, excl_p;
     if (planes_out) {                                  // the plane-pair output of the QKV projection (N = 768, the bounds behind the stream): see the kernel
         const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, true>), NP == 1 ? "ln_linear_h2_kernel<1 slab, planes out>" : "ln_linear_h2_kernel<5 slabs, planes out>", NT, excl_p);
@@ -776,14 +778,14 @@ inline int launch_ln_linear_h2(hipStream_t s, const float *A, size_t a_pstride, 
         if (!A) return IDF_OK;                         // (availability query: nothing to launch)
         const int nsl = (int)idf_cdiv(N, QHS);
         hipLaunchKernelGGL((ln_linear_h2_kernel<NP, true>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NT), LDS_REQUEST, s, A, a_pstride, M,
-                           (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, planes_out, scales_out);
+                           (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, planes_out, scales_out, step_tmap);
         return IDF_OK;
     }
     const int dyn = idf_exclusive_cu(reinterpret_cast<const void *>(&ln_linear_h2_kernel<NP, false>), NP == 1 ? "ln_linear_h2_kernel<1 slab>" : "ln_linear_h2_kernel<5 slabs>", NT, excl);
     if (dyn != LDS_REQUEST) return IDF_NOT_EXCLUSIVE;
     const int nsl = (int)idf_cdiv(N, QHS);
     hipLaunchKernelGGL((ln_linear_h2_kernel<NP, false>), dim3((unsigned)(idf_cdiv(M, QBM) * nsl)), dim3(NT), LDS_REQUEST, s, A, a_pstride, M,
-                       (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, (float *)nullptr, (float *)nullptr);
+                       (int)(idf_cdiv(M, QBM) * nsl), pack, lnw, lnb, nsl, step_B, bias, C, ldc, N, xn_out, step_state, step_ts, (float *)nullptr, (float *)nullptr, step_tmap);
     return IDF_OK;
 }
 }  // namespace idf_ffn_h2

@@ -47,8 +47,14 @@ __device__ __forceinline__ float4 posterior4(float c1, float c2, float sigma, co
 // sampler state {t, loop index, seed, arrival counter}: the LAST workgroup of a launch to arrive advances it (t -= 1, loop index
 // += 1, ts[b] = max(t, 0)).  Every workgroup reads the state before it adds itself to the counter, so the update cannot race
 // with a reader of the same launch.  Call with all threads of the workgroup.
+// tmap (respaced schedules, respace.py:124-126; null = identity): int64 [steps], the MODEL's timestep of every loop-side step.  t, the
+// table row, the parked {t, loop index} and the Philox step index stay loop-side; only what the embedding looks up, ts[b], is mapped.
+__device__ __forceinline__ int64_t sampler_model_timestep(const int64_t *__restrict__ tmap, int64_t tn) {
+    const int64_t tc = tn < 0 ? 0 : tn;
+    return tmap ? tmap[tc] : tc;
+}
 __device__ __forceinline__ void sampler_advance_last(int64_t *__restrict__ state, int64_t *__restrict__ ts, int B, unsigned n_wg, int64_t t,
-                                                     uint64_t it) {
+                                                     uint64_t it, const int64_t *__restrict__ tmap = nullptr) {
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned *arrived = reinterpret_cast<unsigned *>(state + 3);          // (no fence: __syncthreads drained every load of the state,
@@ -58,7 +64,8 @@ __device__ __forceinline__ void sampler_advance_last(int64_t *__restrict__ state
             const int64_t tn = t - 1;
             state[0] = tn;
             state[1] = (int64_t)it + 1;
-            for (int b = 0; b < B; ++b) ts[b] = tn < 0 ? 0 : tn;
+            const int64_t tm = sampler_model_timestep(tmap, tn);
+            for (int b = 0; b < B; ++b) ts[b] = tm;
         }
     }
 }
@@ -68,11 +75,13 @@ __device__ __forceinline__ void sampler_advance_last(int64_t *__restrict__ state
 // after the embedding has read ts, before the last GEMM reads the state -- does the bookkeeping for the whole step: it parks the
 // current {t, loop index} in state[4..5] for the last GEMM, sets ts to the NEXT step's timestep and advances state[0..1].  Nothing
 // else reads or writes these words while that kernel runs, so there is no counter and no fence.
-__device__ __forceinline__ void sampler_prepare_step(int64_t *__restrict__ state, int64_t *__restrict__ ts, int B) {
+__device__ __forceinline__ void sampler_prepare_step(int64_t *__restrict__ state, int64_t *__restrict__ ts, int B,
+                                                     const int64_t *__restrict__ tmap = nullptr) {
     const int64_t t = state[0], it = state[1], tn = t - 1;
     state[4] = t;
     state[5] = it;
     state[0] = tn;
     state[1] = it + 1;
-    for (int b = 0; b < B; ++b) ts[b] = tn < 0 ? 0 : tn;
+    const int64_t tm = sampler_model_timestep(tmap, tn);
+    for (int b = 0; b < B; ++b) ts[b] = tm;
 }

@@ -55,7 +55,8 @@ __global__ __launch_bounds__(256) void randn_kernel(float *__restrict__ out, int
 __global__ __launch_bounds__(256) void posterior_dev_kernel(float *__restrict__ x, const float *__restrict__ x0,
                                                             const float *__restrict__ gt, const uint8_t *__restrict__ mask,
                                                             int64_t n, const float *__restrict__ table,
-                                                            int64_t *__restrict__ state, int64_t *__restrict__ ts, int B) {
+                                                            int64_t *__restrict__ state, int64_t *__restrict__ ts, int B,
+                                                            const int64_t *__restrict__ tmap) {
     const int64_t t = state[0];
     const uint64_t it = (uint64_t)state[1], seed = (uint64_t)state[2], g0 = (uint64_t)state[6] >> 2;
     const float c1 = table[t * 4], c2 = table[t * 4 + 1], sigma = table[t * 4 + 2];
@@ -80,14 +81,16 @@ __global__ __launch_bounds__(256) void posterior_dev_kernel(float *__restrict__ 
             }
         }
     }
-    // advance (t -= 1, loop index += 1, ts[b] = max(t, 0)) by the LAST workgroup to arrive (philox.h)
-    if (ts) sampler_advance_last(state, ts, B, gridDim.x, t, it);
+    // advance (t -= 1, loop index += 1, ts[b] = tmap[max(t, 0)]) by the LAST workgroup to arrive (philox.h)
+    if (ts) sampler_advance_last(state, ts, B, gridDim.x, t, it, tmap);
 }
 
-__global__ __launch_bounds__(256) void advance_kernel(int64_t *__restrict__ state, int64_t *__restrict__ ts, int B) {
+__global__ __launch_bounds__(256) void advance_kernel(int64_t *__restrict__ state, int64_t *__restrict__ ts, int B,
+                                                      const int64_t *__restrict__ tmap) {
     const int64_t t = state[0] - 1;
     __syncthreads();                                        // every thread has read the old value (single workgroup)
-    for (int b = threadIdx.x; b < B; b += 256) ts[b] = t < 0 ? 0 : t;
+    const int64_t tm = sampler_model_timestep(tmap, t);
+    for (int b = threadIdx.x; b < B; b += 256) ts[b] = tm;
     if (threadIdx.x == 0) { state[0] = t; state[1] += 1; }
 }
 
@@ -134,25 +137,34 @@ extern "C" int interdiff_posterior_step(float *x, const float *x0, const float *
     return interdiff_posterior_step_at(x, x0, noise, n, c1, c2, sigma, seed, step_index, 0, stream);
 }
 
-extern "C" int interdiff_posterior_step_dev(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
-                                            const float *table, int64_t *state, int64_t *ts, int32_t B, void *stream) {
+extern "C" int interdiff_posterior_step_dev_map(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
+                                                const float *table, const int64_t *tmap, int64_t *state, int64_t *ts, int32_t B, void *stream) {
     if (!x || !x0 || !table || !state || n < 0 || (mask && !gt) || (ts && B <= 0)) return IDF_E_INVAL;   // (state[6] & 3 cannot be checked here without a sync: the host mirror asserts it)
     if (n == 0) return IDF_OK;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(gt)) & 15) return IDF_E_INVAL;
     if (reinterpret_cast<uintptr_t>(mask) & 3) return IDF_E_INVAL;
     idf_prof_mark(IDF_K_POSTERIOR, idf_stream(stream));
     hipLaunchKernelGGL(posterior_dev_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, idf_stream(stream), x, x0, gt, mask, n, table,
-                       state, ts, B);
+                       state, ts, B, tmap);
     idf_prof_mark(-1, idf_stream(stream));
     IDF_CHECK_LAUNCH();
     return IDF_OK;
 }
 
-extern "C" int interdiff_sampler_advance(int64_t *state, int64_t *ts, int32_t B, void *stream) {
+extern "C" int interdiff_posterior_step_dev(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
+                                            const float *table, int64_t *state, int64_t *ts, int32_t B, void *stream) {
+    return interdiff_posterior_step_dev_map(x, x0, gt, mask, n, table, nullptr, state, ts, B, stream);
+}
+
+extern "C" int interdiff_sampler_advance_map(int64_t *state, int64_t *ts, const int64_t *tmap, int32_t B, void *stream) {
     if (!state || !ts || B <= 0) return IDF_E_INVAL;
-    hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(256), 0, idf_stream(stream), state, ts, B);
+    hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(256), 0, idf_stream(stream), state, ts, B, tmap);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
+}
+
+extern "C" int interdiff_sampler_advance(int64_t *state, int64_t *ts, int32_t B, void *stream) {
+    return interdiff_sampler_advance_map(state, ts, nullptr, B, stream);
 }
 
 extern "C" int interdiff_randn_at(float *out, int64_t n, uint64_t seed, uint64_t step_index, uint64_t elem0, void *stream) {

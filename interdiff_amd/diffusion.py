@@ -22,8 +22,15 @@ larger batch that other ranks (or other calls) hold the rest of.  The in-kernel 
 counters (element offset first * C * T: the reference fills one ``randn_like`` tensor for the whole batch, :532) and the
 feed-forward tile is picked from the whole batch's token rows, so the shard's result is bit-identical to the same clips of an
 unsharded run -- whatever the route (eager, graph, chains).
-Only the configuration the eval path uses is implemented (ModelMeanType.START_X, ModelVarType.FIXED_SMALL,
-clip_denoised=False, identity timestep map); anything else raises NotImplementedError.
+Respacing and DDIM: ``space_timesteps`` / ``SpacedDiffusion`` (diffusion/respace.py) keep a subset of the base
+process's timesteps; ``ddim_sample_loop`` (gaussian_diffusion.py:738-788, :885-1000) is the same loop on other table rows -- for an
+x0-predicting model the DDIM update is linear in (x0, x_t, noise), so it is folded on the host, in fp64, into the three per-step
+scalars {c1, c2, sigma} the kernels already take.  Two indices then exist per step: the loop-side (spaced) index i -- table row,
+Philox step counter, what ``denoised_fn`` is told and what its gate and blend weight act on -- and the model's timestep
+``timestep_map[i]``, which only the denoiser's embedding sees (respace.py:124-126); on the device, ``state[0]`` holds the former and
+``ts`` the latter (``_tmap``).
+Only the configuration the eval path uses is implemented (ModelMeanType.START_X, ModelVarType.FIXED_SMALL, clip_denoised=False,
+rescale_timesteps=False); anything else raises NotImplementedError.
 """
 import itertools
 import math
@@ -79,6 +86,50 @@ def seeded_state(t_start, seed, elem0):
     return torch.tensor([t_start, 0, int(seed) & 0x7FFFFFFFFFFFFFFF, 0, 0, 0, elem0, 0], dtype=torch.int64)
 
 
+def space_timesteps(num_timesteps, section_counts):
+    """respace.py:8-61: the set of base timesteps to keep.  ``section_counts``: a list of ints or a comma string -- that many evenly
+    strided steps from each of len(section_counts) equal portions of the base process -- or 'ddimN': the fixed integer stride of the
+    DDIM paper that yields exactly N steps.  ValueError when no integer stride does, or a portion has fewer steps than asked of it."""
+    if isinstance(section_counts, str):
+        if section_counts.startswith('ddim'):
+            want = int(section_counts[len('ddim'):])
+            for stride in range(1, num_timesteps):
+                if len(range(0, num_timesteps, stride)) == want:
+                    return set(range(0, num_timesteps, stride))
+            raise ValueError('cannot create exactly %d steps with an integer stride' % num_timesteps)
+        section_counts = [int(c) for c in section_counts.split(',')]
+    size_per, extra = divmod(num_timesteps, len(section_counts))
+    start, kept = 0, []
+    for k, count in enumerate(section_counts):
+        size = size_per + (1 if k < extra else 0)
+        if size < count:
+            raise ValueError('cannot divide section of %d steps into %d' % (size, count))
+        stride = 1 if count <= 1 else (size - 1) / (count - 1)
+        kept += [start + round(cur) for cur in _strided(stride, count)]
+        start += size
+    return set(kept)
+
+
+def _strided(stride, count):
+    """0, stride, 2 stride, ... accumulated the way the reference does (repeated addition: the rounding of the sum is part of the result)."""
+    cur = 0.0
+    for _ in range(count):
+        yield cur
+        cur += stride
+
+
+def ddim_coefficients(alphas_cumprod, alphas_cumprod_prev, eta):
+    """The DDIM step of an x0-predicting model (gaussian_diffusion.py:769-787) as x_prev = c1 x0 + c2 x_t + sigma noise, fp64 [steps] each:
+        eps    = (sqrt(1/ab) x - x0) / sqrt(1/ab - 1)
+        sigma  = eta sqrt((1 - ab_prev) / (1 - ab)) sqrt(1 - ab / ab_prev)
+        x_prev = x0 sqrt(ab_prev) + sqrt(1 - ab_prev - sigma^2) eps + sigma noise
+    so with k = sqrt(1 - ab_prev - sigma^2) / sqrt(1/ab - 1):  c1 = sqrt(ab_prev) - k,  c2 = k sqrt(1/ab)."""
+    ab, abp = np.asarray(alphas_cumprod, np.float64), np.asarray(alphas_cumprod_prev, np.float64)
+    sigma = float(eta) * np.sqrt((1.0 - abp) / (1.0 - ab)) * np.sqrt(1.0 - ab / abp)
+    k = np.sqrt(np.maximum(1.0 - abp - sigma ** 2, 0.0)) / np.sqrt(1.0 / ab - 1.0)     # (eta = 1: 1 - ab_prev - sigma^2 is >= 0 up to rounding)
+    return np.sqrt(abp) - k, k * np.sqrt(1.0 / ab), sigma
+
+
 class GaussianDiffusion:
     """START_X / FIXED_SMALL diffusion (the reference's create_gaussian_diffusion configuration)."""
 
@@ -101,8 +152,13 @@ class GaussianDiffusion:
         # forward-diffusion tables (gaussian_diffusion.py:160-161), fp64; q_sample hands the kernel their fp32 casts
         self.sqrt_alphas_cumprod = np.sqrt(self.alphas_cumprod)
         self.sqrt_one_minus_alphas_cumprod = np.sqrt(1.0 - self.alphas_cumprod)
+        self.timestep_map = list(range(self.num_timesteps))       # a SpacedDiffusion overwrites both (respace.py:75-76)
+        self.original_num_steps = self.num_timesteps
+        self.identity_tmap_is_null = True    # an identity timestep map goes to the kernels as NULL (the route of the un-suffixed C entries); False: as an array, for the A/B test of the _map entries
         self._t_cache = {}
         self._tables = {}
+        self._rows_cache = {}
+        self._tmaps = {}
         self._q_tables = {}
         self.fuse_plain_step = True          # plain steps of the graph route: posterior update inside the denoiser's last GEMM
         self.chain_plain_steps = os.environ.get('INTERDIFF_CHAIN_STEPS', '1') != '0'      # ... and, inside a captured run of plain steps, the next step's embedding in the same launch (csrc/tail_h2.h)
@@ -111,23 +167,52 @@ class GaussianDiffusion:
         self._uid = next(_UID)               # names this schedule in the per-denoiser graph cache (never reused, unlike id())
 
     # ------------------------------------------------------------------ helpers
-    def _timesteps(self, B, device):
-        key = (B, str(device))
+    @property
+    def is_respaced(self):
+        return self.timestep_map != list(range(self.num_timesteps))
+
+    def _timesteps(self, B, device, loop_side=False):
+        """int64 [steps, B]: row i is the ``t`` of loop-side step i -- the MODEL's timestep ``timestep_map[i]`` (respace.py:124-126), or with
+        ``loop_side`` the spaced index i itself, which is what ``denoised_fn`` is handed (gaussian_diffusion.py:356 passes the unmapped t).
+        The same tensor when the map is the identity."""
+        key = (B, str(device), bool(loop_side) and self.is_respaced)
         if key not in self._t_cache:
-            self._t_cache[key] = torch.arange(self.num_timesteps, device=device, dtype=torch.int64)[:, None].repeat(1, B).contiguous()
+            vals = torch.tensor(self.timestep_map, dtype=torch.int64) if not key[2] and self.is_respaced else torch.arange(self.num_timesteps, dtype=torch.int64)
+            self._t_cache[key] = vals.to(device)[:, None].repeat(1, B).contiguous()
         return self._t_cache[key]
 
-    def _table(self, device):
-        """[steps,4] fp32 rows {c1, c2, sigma (0 at t=0), t/1000} for the device-parameterised step kernels."""
+    def _tmap(self, device):
+        """The device array the step kernels map ``ts`` through (int64 [steps] = timestep_map), None for the identity."""
+        if not self.is_respaced and self.identity_tmap_is_null:
+            return None
         key = str(device)
-        if key not in self._tables:
-            sig = self._sigma.copy()
+        if key not in self._tmaps:
+            self._tmaps[key] = torch.tensor(self.timestep_map, dtype=torch.int64).to(device)
+        return self._tmaps[key]
+
+    def _rows(self, sampler=('ddpm',)):
+        """Host [steps,4] fp32 rows {c1, c2, sigma (0 at step 0), step/1000} of a sampler: ('ddpm',) -- posterior mean coefficients and
+        exp(.5 logvar) -- or ('ddim', eta) -- ``ddim_coefficients``.  ``step`` is the loop-side index: the blend weight of the correction
+        hook acts on it (module docstring)."""
+        if sampler not in self._rows_cache:
+            if sampler[0] == 'ddpm':
+                c1, c2, sig = self._c1, self._c2, self._sigma.copy()
+            else:
+                c1, c2, sig = (v.astype(np.float32) for v in ddim_coefficients(self.alphas_cumprod, self.alphas_cumprod_prev, sampler[1]))
             sig[0] = 0.0
             blend = (np.arange(self.num_timesteps, dtype=np.float32) / np.float32(1000)).astype(np.float32)
-            self._tables[key] = torch.from_numpy(np.stack([self._c1, self._c2, sig, blend], axis=1).astype(np.float32)).contiguous().to(device)
+            self._rows_cache[sampler] = np.ascontiguousarray(np.stack([c1, c2, sig, blend], axis=1).astype(np.float32))
+        return self._rows_cache[sampler]
+
+    def _table(self, device, sampler=('ddpm',)):
+        """``_rows`` on the device, for the device-parameterised step kernels."""
+        key = (str(device), sampler)
+        if key not in self._tables:
+            self._tables[key] = torch.from_numpy(self._rows(sampler)).to(device)
         return self._tables[key]
 
-    def _step(self, model, img, x0_buf, i, it, t, model_kwargs, denoised_fn, noise_i, seed, elem0=0, rows_kw={}):
+    def _step(self, model, img, x0_buf, i, it, t, model_kwargs, denoised_fn, noise_i, seed, elem0=0, rows_kw={}, t_hook=None, rows=None):
+        """``t``: what the model is called with; ``t_hook`` (default ``t``): what ``denoised_fn`` is; ``rows``: the sampler's ``_rows``."""
         lib = _lib.load()
         y = model_kwargs.get('y', {})
         x0 = model(img, t, **model_kwargs, **rows_kw)
@@ -135,11 +220,11 @@ class GaussianDiffusion:
         if mu8 is not None:
             inpaint(x0, gc, mu8)
         if denoised_fn is not None:
-            x0 = denoised_fn(x0, t, model_kwargs)
-        sigma = 0.0 if i == 0 else float(self._sigma[i])
+            x0 = denoised_fn(x0, t if t_hook is None else t_hook, model_kwargs)
+        c1, c2, sigma = (float(v) for v in (self._rows() if rows is None else rows)[i, :3])
         _lib.check(lib.interdiff_posterior_step_at(_lib.dptr(img, torch.float32), _lib.dptr(x0, torch.float32),
                                                    _lib.dptr(noise_i, torch.float32, allow_none=True), img.numel(),
-                                                   float(self._c1[i]), float(self._c2[i]), sigma, seed, it, elem0, _lib.stream()),
+                                                   c1, c2, sigma, seed, it, elem0, _lib.stream()),
                    'posterior_step')
         return x0
 
@@ -155,7 +240,26 @@ class GaussianDiffusion:
         to force the eager route, ``first_t`` to enter the schedule at that timestep with ``noise`` taken as x_{first_t}
         (a window of the loop for measurements; default T-1), ``shard=(first_clip, total_clips)``: the batch is clips
         [first, first + B) of a larger one -- noise counters and the feed-forward tile are the larger batch's (module docstring);
-        ``noise`` / ``step_noise`` tensors, when given, are this shard's slices."""
+        ``noise`` / ``step_noise`` tensors, when given, are this shard's slices.  On a respaced schedule ``first_t``, ``n_steps`` and
+        ``dump_steps`` count spaced steps."""
+        return self._sample_loop(('ddpm',), model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
+                                 init_image, randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed, n_steps, use_graph,
+                                 first_t, shard)
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None, randomize_class=False,
+                         cond_fn_with_grad=False, dump_steps=None, const_noise=False, step_noise=None, seed=None, n_steps=None,
+                         use_graph=True, first_t=None, shard=None):
+        """``ddim_sample_loop`` (gaussian_diffusion.py:885-1000): ``p_sample_loop``'s keyword surface and extras, plus ``eta``.  The same
+        loop on the table rows of ``ddim_coefficients``; inpainting and ``denoised_fn`` act on x0 before the update, and x_T drawn here
+        (``noise=None``) is NOT inpainted (:960-963, unlike :695-699).  With ``eta = 0`` every sigma is 0: the noise is still drawn and
+        multiplied, so that the eager and the graph route stay one arithmetic (the result does not depend on ``seed``)."""
+        return self._sample_loop(('ddim', float(eta)), model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                                 skip_timesteps, init_image, randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed,
+                                 n_steps, use_graph, first_t, shard)
+
+    def _sample_loop(self, sampler, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps, init_image,
+                     randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed, n_steps, use_graph, first_t, shard):
         if clip_denoised:
             raise NotImplementedError('clip_denoised=True is not used on the eval path (eval_smpl_short.py:153)')
         if cond_fn is not None or skip_timesteps or init_image is not None or randomize_class or cond_fn_with_grad or const_noise:
@@ -182,7 +286,7 @@ class GaussianDiffusion:
             img = torch.empty(*shape, dtype=torch.float32, device=device)
             _lib.check(_lib.load().interdiff_randn_at(_lib.dptr(img), img.numel(), seed, 0xFFFFFFFF, elem0, _lib.stream()), 'randn')
             y = model_kwargs.get('y', {})
-            mu8, gc = mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), img)
+            mu8, gc = mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), img) if sampler[0] == 'ddpm' else (None, None)
             if mu8 is not None:
                 inpaint(img, gc, mu8)
         t_first = self.num_timesteps - 1 if first_t is None else int(first_t)
@@ -191,23 +295,23 @@ class GaussianDiffusion:
         todo = t_first + 1 if n_steps is None else min(int(n_steps), t_first + 1)
         if (step_noise is None and use_graph and getattr(model, 'graph_safe', False) and img.is_cuda
                 and 'cond' in model_kwargs.get('y', {}) and os.environ.get('INTERDIFF_NO_GRAPH') != '1'):
-            return graph_sampler.sample(self, model, img, model_kwargs, denoised_fn, seed, todo, dump_steps, t_first, shard)
+            return graph_sampler.sample(self, model, img, model_kwargs, denoised_fn, seed, todo, dump_steps, t_first, shard, sampler)
         rows_kw = {'batch_rows': total * shape[-1]} if shard is not None and getattr(model, 'accepts_batch_rows', False) else {}
-        ts = self._timesteps(shape[0], device)
+        ts, ts_hook, rows = self._timesteps(shape[0], device), self._timesteps(shape[0], device, loop_side=True), self._rows(sampler)
         dump = []
         cond = model_kwargs.get('y', {}).get('cond') if isinstance(model_kwargs.get('y', None), dict) else None
         if cond is not None and hasattr(model, 'prepare_memory'):
             model.prepare_memory(cond)                  # once per sample, like the graph route (never trust a cached fold across samples)
         for it, i in enumerate(range(t_first, t_first - todo, -1)):
-            t = ts[i]
-            t.host_value = i
+            t, th = ts[i], ts_hook[i]
+            t.host_value = th.host_value = i
             if step_noise is None:
                 nz = None
             elif callable(step_noise):
                 nz = step_noise(it, img).contiguous()
             else:
                 nz = step_noise[it]
-            self._step(model, img, None, i, it, t, model_kwargs, denoised_fn, nz, seed, elem0, rows_kw)
+            self._step(model, img, None, i, it, t, model_kwargs, denoised_fn, nz, seed, elem0, rows_kw, th, rows)
             if dump_steps is not None and it in dump_steps:
                 dump.append(img.clone())
         return dump if dump_steps is not None else img
@@ -266,30 +370,48 @@ class GaussianDiffusion:
         both = 'inpainting_mask' in y and 'inpainted_motion' in y
         x_t = self.q_sample(x_start, t, noise=noise, seed=seed, inpainted_motion=y['inpainted_motion'] if both else None,
                             inpainting_mask=y['inpainting_mask'] if both else None)
-        model_output = model(x_t, t.to(x_t.device), **model_kwargs)
+        t = t.to(x_t.device)
+        if self.is_respaced:                   # the model is told the base process's timestep (respace.py:94-97, :124-126)
+            t = torch.tensor(self.timestep_map, dtype=torch.int64, device=x_t.device)[t]
+        model_output = model(x_t, t, **model_kwargs)
         assert model_output.shape == x_start.shape
         return model_output, x_start
 
 
-class SpacedDiffusion(GaussianDiffusion):
-    """respace.py:64-114.  Betas are re-derived from the kept alphas_cumprod; the timestep map is the
-    identity when every step is kept (the only configuration the eval path builds)."""
+def sample_loop(diffusion, model, shape, sampler='ddpm', eta=0.0, **kw):
+    """``diffusion.p_sample_loop`` (sampler='ddpm', the default everywhere) or ``diffusion.ddim_sample_loop`` (sampler='ddim', with ``eta``): what the
+    eval and scoring entry points call, so that their ``loop_kw`` can choose the sampler."""
+    if sampler == 'ddpm':
+        return diffusion.p_sample_loop(model, shape, **kw)
+    if sampler == 'ddim':
+        return diffusion.ddim_sample_loop(model, shape, eta=eta, **kw)
+    raise ValueError("sampler must be 'ddpm' or 'ddim'")
 
-    def __init__(self, use_timesteps, betas):
+
+class SpacedDiffusion(GaussianDiffusion):
+    """respace.py:64-114: the steps ``use_timesteps`` of the base process ``betas``.  The betas are re-derived (fp64) from the kept
+    alphas_cumprod, so every table of ``GaussianDiffusion`` is the spaced process's; ``timestep_map[i]`` is the base timestep of spaced
+    step i -- what the model is called with -- and ``original_num_steps`` the base length.  ``rescale_timesteps=True`` is not built."""
+
+    def __init__(self, use_timesteps, betas, rescale_timesteps=False):
+        if rescale_timesteps:
+            raise NotImplementedError('rescale_timesteps=True is not built (the reference configuration is False: model/diffusion_smpl.py:258)')
         base = GaussianDiffusion(betas)
-        use = set(use_timesteps)
-        last, new_betas, self.timestep_map = 1.0, [], []
+        self.use_timesteps = set(use_timesteps)
+        last, new_betas, tmap = 1.0, [], []
         for i, ac in enumerate(base.alphas_cumprod):
-            if i in use:
+            if i in self.use_timesteps:
                 new_betas.append(1 - ac / last)
                 last = ac
-                self.timestep_map.append(i)
-        if self.timestep_map != list(range(len(betas))):
-            raise NotImplementedError('timestep respacing is not used by the reference eval path')
+                tmap.append(i)
         super().__init__(np.array(new_betas))
+        self.timestep_map, self.original_num_steps, self.rescale_timesteps = tmap, len(base.betas), False
 
 
-def create_gaussian_diffusion(noise_schedule='cosine', diffusion_steps=1000):
-    """model/diffusion_smpl.py:251-284 with its fixed defaults (predict x_start, sigma_small, no respacing)."""
+def create_gaussian_diffusion(noise_schedule='cosine', diffusion_steps=1000, timestep_respacing=''):
+    """model/diffusion_smpl.py:251-284 with its fixed defaults (predict x_start, sigma_small); ``timestep_respacing``: '' (every step, the
+    reference's setting) or what ``space_timesteps`` takes -- '100', [4, 3, 2], 'ddim50'."""
     betas = get_named_beta_schedule(noise_schedule, diffusion_steps, 1.)
-    return SpacedDiffusion(range(diffusion_steps), betas)
+    if not timestep_respacing:
+        timestep_respacing = [diffusion_steps]
+    return SpacedDiffusion(space_timesteps(diffusion_steps, timestep_respacing), betas)

@@ -16,6 +16,7 @@ import os
 import torch
 from . import _lib, dist, io, transforms as tr
 from .dist import METRIC_KEYS
+from .diffusion import sample_loop
 
 SMPL_DIM = 132          # 22 joints x rot6d (eval_smpl_short.py:416)
 
@@ -86,13 +87,14 @@ def as_clip_batch(model, batch, past_len=10):
 
 def sample_once_proj(model, diffusion, correction, batch, past_len=10, noise=None, **loop_kw):
     """Full InterDiff: diffusion + correction hook.  Returns (obj_pred [T,B,6], body_pred [T,B,159], verts [T,B,V,3],
-    jtr [T,B,J,3], pelvis [T,B,3]) like the reference (:177).  ``noise`` / ``step_noise`` / ``seed`` make it deterministic.
+    jtr [T,B,J,3], pelvis [T,B,3]) like the reference (:177).  ``noise`` / ``step_noise`` / ``seed`` make it deterministic;
+    ``sampler='ddim'`` (+ ``eta=``) in ``loop_kw`` takes ``ddim_sample_loop`` instead of ``p_sample_loop`` (``diffusion.sample_loop``), here and in ``sample_once``.
     ``batch``: a clip batch (module docstring) or the DataLoader's dict-of-lists batch, as the reference passes it."""
     batch = as_clip_batch(model, batch, past_len)
     gt = batch['gt']
     if noise is None:
         noise = _x_T(gt, loop_kw.get('seed'), loop_kw.get('shard'))
-    sample = diffusion.p_sample_loop(model, tuple(gt.shape), clip_denoised=False, noise=noise,
+    sample = sample_loop(diffusion, model, tuple(gt.shape), clip_denoised=False, noise=noise,
                                      model_kwargs={'y': model_kwargs_for(batch, past_len)}, denoised_fn=correction, **loop_kw)
     return finalize(sample, batch, correction.smpl if correction is not None else loop_kw['smpl'], past_len)
 
@@ -104,7 +106,7 @@ def sample_once(model, diffusion, smpl, batch, past_len=10, noise=None, **loop_k
     if noise is None:
         noise = _x_T(gt, loop_kw.get('seed'), loop_kw.get('shard'))
     y = model_kwargs_for(batch, past_len)
-    sample = diffusion.p_sample_loop(model, tuple(gt.shape), clip_denoised=False, noise=noise, model_kwargs={'y': y}, **loop_kw)
+    sample = sample_loop(diffusion, model, tuple(gt.shape), clip_denoised=False, noise=noise, model_kwargs={'y': y}, **loop_kw)
     return finalize(sample, batch, smpl, past_len)
 
 

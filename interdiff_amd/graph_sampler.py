@@ -57,10 +57,12 @@ def capture(enqueue, *args):
     return g
 
 
-def posterior_update(x, x0, gt, mask, table, state, ts):
-    """x_t -> x_{t-1} from x0 (inpainted first when gt / mask are given), every per-step scalar read from ``table[state[0]]``; advances ``state`` and ``ts``."""
-    _lib.check(_lib.load().interdiff_posterior_step_dev(_lib.dptr(x), _lib.dptr(x0), _lib.dptr(gt, allow_none=True), _lib.dptr(mask, allow_none=True),
-                                                        x.numel(), _lib.dptr(table), _lib.dptr(state), _lib.dptr(ts), ts.numel(), _lib.stream()),
+def posterior_update(x, x0, gt, mask, table, state, ts, tmap=None):
+    """x_t -> x_{t-1} from x0 (inpainted first when gt / mask are given), every per-step scalar read from ``table[state[0]]``; advances ``state`` and
+    ``ts`` (to ``tmap[state[0]]``, the model's timestep under a respaced schedule; None: the identity)."""
+    _lib.check(_lib.load().interdiff_posterior_step_dev_map(_lib.dptr(x), _lib.dptr(x0), _lib.dptr(gt, allow_none=True), _lib.dptr(mask, allow_none=True),
+                                                            x.numel(), _lib.dptr(table), _lib.dptr(tmap, torch.int64, allow_none=True), _lib.dptr(state),
+                                                            _lib.dptr(ts), ts.numel(), _lib.stream()),
                'posterior_step_dev')
 
 
@@ -146,19 +148,20 @@ class Entry:
             self.gt.copy_(gt)
             self.mask.copy_(mask)
 
-    def warm_up(self, model, table, rows):
+    def warm_up(self, model, table, rows, tmap=None):
         """First launches of everything a plain step can consist of, outside a capture (where a launch error cannot be reported): the
         forward (workspaces, kernel attributes), the fused step's own instantiations (last GEMM with the update in its epilogue, QKV kernel
         with the sampler bookkeeping) and the chained forms of the step tail (csrc/tail_h2.h).  The steps run on copies of x / ts."""
         model(self.x, self.ts, out=self.x0, **self.kwargs, batch_rows=rows)
         if model.supports_forward_step:
-            x, ts, state = self.x.clone(), self.ts.clone(), diffusion.seeded_state(2, 1, 0).to(self.x.device)
-            model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, **self.kwargs, batch_rows=rows)
+            t0 = min(2, table.shape[0] - 1)              # (a row every schedule has: respaced ones can be shorter than three steps)
+            x, ts, state = self.x.clone(), self.ts.clone(), diffusion.seeded_state(t0, 1, 0).to(self.x.device)
+            model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, tmap=tmap, **self.kwargs, batch_rows=rows)
             if model.step_chaining:
-                state.copy_(diffusion.seeded_state(2, 1, 0))
+                state.copy_(diffusion.seeded_state(t0, 1, 0))
                 ts.copy_(self.ts)
-                model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, embed_next=True, **self.kwargs, batch_rows=rows)
-                model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, embed_ready=True, **self.kwargs, batch_rows=rows)
+                model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, tmap=tmap, embed_next=True, **self.kwargs, batch_rows=rows)
+                model.forward_step(x, ts, table, state, gt=self.gt, mask=self.mask, tmap=tmap, embed_ready=True, **self.kwargs, batch_rows=rows)
         torch.cuda.synchronize(self.x.device)
 
     def split_into_chains(self, model, n):
@@ -206,8 +209,8 @@ class Run:
     """One sample on ``entry``.  ``fused``: the plain step's update runs in the epilogue of the denoiser's last GEMM; ``split``: the
     plain steps run as the entry's chains; ``hook`` / ``hk``: the hook and, when whole hook steps are captured, its buffers."""
 
-    def __init__(self, model, entry, table, rows, fused, split, hook, hk):
-        self.model, self.entry, self.table, self.rows = model, entry, table, rows
+    def __init__(self, model, entry, table, rows, fused, split, hook, hk, tmap=None):
+        self.model, self.entry, self.table, self.rows, self.tmap = model, entry, table, rows, tmap
         self.fused, self.split, self.hook, self.hk = fused, split, hook, hk
 
     def enqueue_forward(self):
@@ -226,21 +229,21 @@ class Run:
                 ch.stream.wait_stream(cur)
                 with torch.cuda.stream(ch.stream):
                     for link in links:
-                        model.forward_step(ch.x, ch.ts, self.table, ch.state, gt=ch.gt, mask=ch.mask, memctx=ch.memctx, ws=ch.ws, batch_rows=self.rows, **link, **ch.kwargs)
+                        model.forward_step(ch.x, ch.ts, self.table, ch.state, gt=ch.gt, mask=ch.mask, tmap=self.tmap, memctx=ch.memctx, ws=ch.ws, batch_rows=self.rows, **link, **ch.kwargs)
             for ch in st.chains:
                 cur.wait_stream(ch.stream)
         elif self.fused:
             for link in links:
-                model.forward_step(st.x, st.ts, self.table, st.state, gt=st.gt, mask=st.mask, **link, **st.kwargs, batch_rows=self.rows)
+                model.forward_step(st.x, st.ts, self.table, st.state, gt=st.gt, mask=st.mask, tmap=self.tmap, **link, **st.kwargs, batch_rows=self.rows)
         else:
             for _ in links:
                 self.enqueue_forward()
-                posterior_update(st.x, st.x0, st.gt, st.mask, self.table, st.state, st.ts)
+                posterior_update(st.x, st.x0, st.gt, st.mask, self.table, st.state, st.ts, self.tmap)
 
     def finish_hook_step(self, x0):
         """The whole-batch update from the hook's x0; it advanced chain 0's state, the others follow."""
         st = self.entry
-        posterior_update(st.x, x0, None, None, self.table, st.state, st.ts)
+        posterior_update(st.x, x0, None, None, self.table, st.state, st.ts, self.tmap)
         if self.split:
             for ch in st.chains[1:]:
                 ch.state[:6].copy_(st.state[:6])
@@ -279,7 +282,7 @@ class Run:
         self.finish_hook_step(self.hook(st.x0, t, model_kwargs).contiguous())
 
     def play(self, plan, t_start, ts_all, model_kwargs):
-        """One replay or eager hook step per op; the dumps."""
+        """One replay or eager hook step per op; the dumps.  ``ts_all``: the LOOP-side timesteps, what an eager hook is handed."""
         st, dump, i = self.entry, [], t_start
         for op in plan:
             if op[0] == 'plain':
@@ -298,19 +301,22 @@ class Run:
         return dump
 
 
-def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start, shard=None):
+def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start, shard=None, sampler=('ddpm',)):
     """``todo`` reverse steps from x_{t_start} = ``img`` on captured graphs: the plain step [denoiser forward -> inpaint + posterior ->
-    advance] with its per-step scalars (c1, c2, sigma, t, loop index, seed) in HBM, and whole hook steps when the hook allows it."""
+    advance] with its per-step scalars (c1, c2, sigma, t, loop index, seed) in HBM, and whole hook steps when the hook allows it.
+    ``sampler``: whose table rows (``GaussianDiffusion._rows``).  The captured launches bake the table's and the timestep map's addresses
+    in, so the graphs are kept per (schedule, sampler).  ``t_start``, the plan and the hook gate count loop-side (spaced) steps; ``ts``
+    holds the model's timesteps (``diff._tmap``)."""
     y = model_kwargs.get('y', {})
     B, T, dev = img.shape[0], img.shape[-1], img.device
     first, total = (0, B) if shard is None else shard
     per_clip = img.numel() // B
     elem0 = first * per_clip                    # position of this batch's x[0] inside the whole (possibly sharded) batch: the Philox counter base (p_sample_loop checked it)
     rows = total * T                            # the WHOLE batch's token rows: what every launch's feed-forward tile is picked by (MDM._pick_ffn_tile)
-    table = diff._table(dev)
+    table, tmap = diff._table(dev, sampler), diff._tmap(dev)
     mask, gt = diffusion.mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), img)
     cond, zpo = y['cond'], model_kwargs.get('zero_pose_obj')
-    key = (diff._uid, tuple(img.shape), mask is not None, tuple(cond.shape), model.ffn_graph_key(rows))    # the captured launches bake the feed-forward kernel choice in
+    key = (diff._uid, tuple(img.shape), mask is not None, tuple(cond.shape), model.ffn_graph_key(rows)) + (() if sampler == ('ddpm',) and tmap is None else (sampler, tmap is not None))    # the captured launches bake the feed-forward kernel choice in
     if zpo is not None:
         key += (tuple(zpo.shape),)
     st, fresh = Entry.of(model, key, img, cond, mask is not None, zpo)
@@ -318,7 +324,7 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
     pools_before = model.shape_buffer_keys() if fresh else None      # (taken before the first fold of this shape allocates its memory context)
     model.prepare_memory(st.cond)                   # once per sample, on the current stream (inside the caller's clock)
     if fresh:
-        st.warm_up(model, table, rows)
+        st.warm_up(model, table, rows, tmap)
         st.pool_keys = model.shape_buffer_keys() - pools_before      # what this entry made the denoiser allocate: released with the entry
 
     fused = diff.fuse_plain_step and model.supports_forward_step
@@ -343,13 +349,13 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
         st.graphs.clear()
         st.chain_steps = chain_steps
     fuse_hook = hook_capturable(hook, y)
-    run = Run(model, st, table, rows, fused, split, hook, st.hook_buffers(hook, y, table) if fuse_hook else None)
+    run = Run(model, st, table, rows, fused, split, hook, st.hook_buffers(hook, y, table) if fuse_hook else None, tmap)
 
     st.x.copy_(img)
     st.state.copy_(diffusion.seeded_state(t_start, seed, elem0))
     if split:                                       # the other chains' states: the same schedule position, their x starts where their clips do
         for ch in st.chains[1:]:                    # (an odd offset when T % 4 != 0: the per-row form of the fused update takes any)
             ch.state.copy_(diffusion.seeded_state(t_start, seed, elem0 + ch.sl.start * per_clip))
-    st.ts.fill_(t_start)
-    dump = run.play(plan_steps(t_start, todo, hook_gate(hook), dump_steps, fuse_hook), t_start, diff._timesteps(B, dev), model_kwargs)
+    st.ts.fill_(diff.timestep_map[t_start])
+    dump = run.play(plan_steps(t_start, todo, hook_gate(hook), dump_steps, fuse_hook), t_start, diff._timesteps(B, dev, loop_side=True), model_kwargs)
     return dump if dump_steps is not None else st.x.clone()

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 from . import _lib
 from .eval import as_clip_batch
+from .diffusion import sample_loop
 
 _KINDS, _GROUPS = ('past', 'v_past', 'future', 'v_future'), ('body_rot', 'body_nonrot', 'obj_rot', 'obj_nonrot')
 LOSS_KEYS = tuple('%s_%s' % (g, k) for k in _KINDS for g in _GROUPS)        # the reference's dict order (:117-134); kernel index = 4 * kind + group
@@ -128,9 +129,9 @@ def sample_seeds(seed, K):
 
 def validation_step(model, diffusion, batch, past_len=10, seed=None, weights=LossWeights(), **loop_kw):
     """``validation_step``: one full sample (x_T drawn in-kernel and inpainted: ``p_sample_loop`` with ``noise=None``), scored by
-    ``calc_val_loss``.  ``loop_kw`` goes to ``p_sample_loop`` (n_steps=, use_graph=, ...)."""
+    ``calc_val_loss``.  ``loop_kw`` goes to ``p_sample_loop`` (n_steps=, use_graph=, ...), or with ``sampler='ddim'`` (+ ``eta=``) to ``ddim_sample_loop``."""
     batch = as_clip_batch(model, batch, past_len)
-    sample = diffusion.p_sample_loop(model, tuple(batch['gt'].shape), clip_denoised=False, model_kwargs=_valid_kwargs(batch, past_len), seed=seed, **loop_kw)
+    sample = sample_loop(diffusion, model, tuple(batch['gt'].shape), clip_denoised=False, model_kwargs=_valid_kwargs(batch, past_len), seed=seed, **loop_kw)
     return calc_val_loss(sample, batch, past_len, weights)
 
 
@@ -138,7 +139,7 @@ def test_step(model, diffusion, batch, past_len=10, seed=None, diverse_samples=1
     """``test_step``: ``diverse_samples`` samples (seeds ``sample_seeds(seed, K)``), scored by ``calc_loss``."""
     batch = as_clip_batch(model, batch, past_len)
     kw = _valid_kwargs(batch, past_len)
-    samples = [diffusion.p_sample_loop(model, tuple(batch['gt'].shape), clip_denoised=False, model_kwargs=kw, seed=s, **loop_kw)
+    samples = [sample_loop(diffusion, model, tuple(batch['gt'].shape), clip_denoised=False, model_kwargs=kw, seed=s, **loop_kw)
                for s in sample_seeds(seed, diverse_samples)]
     return calc_loss(samples, batch, past_len, weights)
 

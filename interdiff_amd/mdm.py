@@ -763,23 +763,24 @@ class MDM:
         self._pick_ffn_tile(1)                    # (writes the arithmetic selection into the handle)
         return bool(self.lib.interdiff_mdm_step_chaining(C.byref(self.w)))
 
-    def forward_step(self, x, timesteps, table, state, gt=None, mask=None, y=None, memctx=None, ws=None, batch_rows=None, embed_ready=False, embed_next=False):
+    def forward_step(self, x, timesteps, table, state, gt=None, mask=None, y=None, memctx=None, ws=None, batch_rows=None, embed_ready=False, embed_next=False, tmap=None):
         """``embed_next``: this step's last launch also computes the NEXT plain step's embedding into the workspace (csrc/tail_h2.h); ``embed_ready``: the
         previous call on this x / workspace was made with ``embed_next`` and nothing touched x, the timesteps or the workspace since (same bits either way).
         One plain reverse step with the update applied inside the last GEMM (interdiff_mdm_forward_step): ``x`` [B,1,C,T] and
         the sampler state (``timesteps`` int64 [B], ``state`` int64 [8]) are advanced in place (any T; T % 4 == 0 takes the 16-byte form of the update).  ``memctx`` / ``ws``:
         caller-owned folded memory (``prepare_memory(cond, into=)``) and workspace (``workspace_bytes(B, T)`` bytes) instead of the
         model's -- what lets two chains of one sample run side by side; ``batch_rows`` then names the whole batch's B * T (see
-        ``_pick_ffn_tile``)."""
+        ``_pick_ffn_tile``).  ``tmap``: int64 [steps], the timestep map of a respaced schedule -- ``timesteps`` then advances to ``tmap[state[0]]``, the
+        model's timestep of the next loop-side step (interdiff_mdm_forward_step_map); None: the identity."""
         return self._forward_step(x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows,
-                                  (_lib.STEP_EMBED_READY if embed_ready else 0) | (_lib.STEP_EMBED_NEXT if embed_next else 0))
+                                  (_lib.STEP_EMBED_READY if embed_ready else 0) | (_lib.STEP_EMBED_NEXT if embed_next else 0), tmap=tmap)
 
-    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, **head):
+    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, tmap=None, **head):
         """The library call of a fused plain step (a model with another head overrides it: skeleton.py)."""
-        _lib.check(self.lib.interdiff_mdm_forward_step_ex(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
-                                                          _lib.dptr(timesteps, torch.int64), B, T, _lib.dptr(gt, allow_none=True),
-                                                          _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(state),
-                                                          _lib.dptr(ws), ws.numel(), flags, _lib.stream()), 'mdm_forward_step')
+        _lib.check(self.lib.interdiff_mdm_forward_step_map(C.byref(self.w), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                           _lib.dptr(timesteps, torch.int64), B, T, _lib.dptr(gt, allow_none=True),
+                                                           _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(tmap, torch.int64, allow_none=True),
+                                                           _lib.dptr(state), _lib.dptr(ws), ws.numel(), flags, _lib.stream()), 'mdm_forward_step')
 
     def _forward_step(self, x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows, flags, **head):
         B, one, Cc, T = x.shape

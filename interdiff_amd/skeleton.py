@@ -17,6 +17,7 @@ from . import _lib
 from .correction import correction_gate
 from .stgcn_pack import ArenaBuilder, pack_dct, pack_stgcn_layers, unpack_stgcn_layers, to_f64
 from . import mdm as _mdm
+from .diffusion import sample_loop
 
 N_PRE, N_JOINTS, N_OBJ = 20, 21, 12
 C_TOKENS = 3 * N_JOINTS + 3 * N_OBJ + 7          # 106
@@ -271,16 +272,16 @@ class SkeletonMDM(_mdm.MDM):
     def step_chaining(self):
         return False                              # the chained step tail is the split-f16 kernel of the 144-channel model (csrc/tail_h2.h)
 
-    def forward_step(self, x, timesteps, table, state, gt=None, mask=None, y=None, zero_pose_obj=None, memctx=None, ws=None, batch_rows=None):
+    def forward_step(self, x, timesteps, table, state, gt=None, mask=None, y=None, zero_pose_obj=None, memctx=None, ws=None, batch_rows=None, tmap=None):
         """One plain reverse step with the update over all 106 channels inside the heads GEMM (interdiff_skeleton_mdm_forward_step);
         operands as ``mdm.MDM.forward_step``."""
-        return self._forward_step(x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows, 0, z=self._zpo(zero_pose_obj, x.shape[0]))
+        return self._forward_step(x, timesteps, table, state, gt, mask, y, memctx, ws, batch_rows, 0, z=self._zpo(zero_pose_obj, x.shape[0]), tmap=tmap)
 
-    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, z):
-        _check(self.lib.interdiff_skeleton_mdm_forward_step(C.byref(self.w), C.byref(self.head), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
-                                                            _lib.dptr(timesteps, torch.int64), _lib.dptr(z), B, T, _lib.dptr(gt, allow_none=True),
-                                                            _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(state),
-                                                            _lib.dptr(ws), ws.numel(), _lib.stream()), 'skeleton_mdm_forward_step')
+    def _launch_step(self, memctx, x, timesteps, B, T, gt, mask, table, state, ws, flags, z, tmap=None):
+        _check(self.lib.interdiff_skeleton_mdm_forward_step_map(C.byref(self.w), C.byref(self.head), _lib.dptr(memctx), _lib.dptr(x, torch.float32),
+                                                                _lib.dptr(timesteps, torch.int64), _lib.dptr(z), B, T, _lib.dptr(gt, allow_none=True),
+                                                                _lib.dptr(mask, allow_none=True), _lib.dptr(table), _lib.dptr(tmap, torch.int64, allow_none=True),
+                                                                _lib.dptr(state), _lib.dptr(ws), ws.numel(), _lib.stream()), 'skeleton_mdm_forward_step')
 
     def arithmetic_report(self, device_verdicts=True):
         rep = super().arithmetic_report(device_verdicts)
@@ -310,7 +311,7 @@ def sample_once_proj(batch, model, diffusion, obj_model=None, seed=None, past_le
     """``sample_once_proj`` of eval_skeleton.py:114-142 (``obj_model=None``: eval_skeleton_no_correction.py's, identity hook).  ``batch``
     = (body [B,T,21,3], obj keypoints [B,T,12,3], pose [B,T,7], zero_pose_obj [B,12,3]) as the dataset yields it; ``obj_model``: a
     ``SkeletonObjProjector`` (or a ready ``HipSkeletonCorrection``).  Returns (obj_pred, body_pred, pose_pred, obj_gt, body_gt, pose_gt),
-    each [T,B,*] -- what ``skeleton_metrics`` takes.  ``loop_kw`` goes to ``p_sample_loop`` (``noise=``, ``step_noise=``, ``use_graph=``)."""
+    each [T,B,*] -- what ``skeleton_metrics`` takes.  ``loop_kw`` goes to ``p_sample_loop`` (``noise=``, ``step_noise=``, ``use_graph=``), or with ``sampler='ddim'`` (+ ``eta=``) to ``ddim_sample_loop``."""
     dev = torch.device(device) if device is not None else model.device
     body_gt, obj_gt, pose_gt = (batch[i].transpose(0, 1).float().to(dev) for i in range(3))
     zero_pose_obj = batch[3].float().to(dev).contiguous()
@@ -322,7 +323,7 @@ def sample_once_proj(batch, model, diffusion, obj_model=None, seed=None, past_le
     hook = None
     if obj_model is not None:
         hook = obj_model if isinstance(obj_model, HipSkeletonCorrection) else HipSkeletonCorrection(obj_model, device=dev)
-    sample = diffusion.p_sample_loop(model, tuple(gt.shape), clip_denoised=False, model_kwargs=kw, denoised_fn=hook, seed=seed, **loop_kw)
+    sample = sample_loop(diffusion, model, tuple(gt.shape), clip_denoised=False, model_kwargs=kw, denoised_fn=hook, seed=seed, **loop_kw)
     nb, no = model.n_body, 3 * model.n_points
     body_pred, obj_pred, pose_pred = torch.split(sample.squeeze(1).permute(2, 0, 1).contiguous(), [nb, no, HEAD_POSE], dim=2)
     body_g, obj_g, pose_g = torch.split(gt.squeeze(1).permute(2, 0, 1).contiguous(), [nb, no, HEAD_POSE], dim=2)

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import torch
 from . import _lib
 from .skeleton import _check
+from .diffusion import sample_loop
 
 KEYS = ('body_past', 'body_future', 'obj_past', 'obj_future', 'loss_obj_nonrot_past', 'loss_obj_nonrot_future', 'loss_obj_rot_past',
         'loss_obj_rot_future', 'quaternion_reg_loss', 'loss_obj_rot_v', 'loss_obj_nonrot_v', 'loss_body_v', 'loss_obj_v')      # the reference's dict order (:129-143, :215-229) = the kernel's term index
@@ -114,9 +115,9 @@ def sample_kwargs(model, batch, past_len=10):
 
 def validation_step(model, diffusion, batch, past_len=10, seed=None, weights=SkeletonLossWeights(), **loop_kw):
     """``validation_step`` (:329-333): ``_get_embeddings``, one full sample with the past frames inpainted (``p_sample_loop`` on the graph
-    route, no hook), scored by ``calc_val_loss``.  -> (val_loss, loss_dict, weighted_loss_dict).  ``loop_kw`` goes to ``p_sample_loop``."""
+    route, no hook), scored by ``calc_val_loss``.  -> (val_loss, loss_dict, weighted_loss_dict).  ``loop_kw`` goes to ``p_sample_loop``, or with ``sampler='ddim'`` (+ ``eta=``) to ``ddim_sample_loop``."""
     gt, kw = sample_kwargs(model, batch, past_len)
-    sample = diffusion.p_sample_loop(model, tuple(gt.shape), clip_denoised=False, model_kwargs=kw, seed=seed, **loop_kw)
+    sample = sample_loop(diffusion, model, tuple(gt.shape), clip_denoised=False, model_kwargs=kw, seed=seed, **loop_kw)
     return calc_val_loss(sample, gt, past_len, weights, model.n_body, model.n_points)
 
 
