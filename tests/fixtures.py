@@ -53,6 +53,41 @@ def mdm_weights_wc():
     return sd
 
 
+def sharpen_attention(sd, gain, self_layers=None, cross_layers=None, encoder_gain=None):
+    """A copy of a denoiser state_dict (the SMPL one or the skeleton one) whose attention LOGITS are ``gain`` ** 2 times as large: the Q and K rows ([:512]) of
+    ``in_proj_weight`` / ``in_proj_bias`` of the decoder's standard self-attention (``self_layers``) and of its cross-attention (``cross_layers``) are multiplied
+    by ``gain``; None = every layer that has one, () = none.  ``encoder_gain`` does the same to the encoder's standard layers.  A default initialisation gives logits
+    of standard deviation ~0.6 and nearly uniform softmax rows; 2 is the scale of a trained checkpoint (rows led by one or two keys), 4 saturates them.
+    The QaN layers have no such rows (their queries are normalised per head)."""
+    out = {k: torch.as_tensor(v).clone() for k, v in sd.items()}
+
+    def scale(prefix, g):
+        out[prefix + 'in_proj_weight'][:512] *= g
+        out[prefix + 'in_proj_bias'][:512] *= g
+    for k in list(out):
+        side, _, rest = k.partition('.layers.')
+        if not rest.endswith('attn.in_proj_weight'):
+            continue
+        layer, kind = int(rest.split('.')[0]), rest.split('.')[1]
+        prefix = k[:-len('in_proj_weight')]
+        if side == 'encoder':
+            if encoder_gain is not None and kind == 'self_attn':
+                scale(prefix, encoder_gain)
+        elif kind == 'self_attn':
+            if self_layers is None or layer in self_layers:
+                scale(prefix, gain)
+        elif cross_layers is None or layer in cross_layers:
+            scale(prefix, gain)
+    return out
+
+
+@functools.lru_cache(None)
+def mdm_weights_sharp(gain, self_layers=None, cross_layers=None, encoder_gain=None):
+    """``mdm_weights()`` at the attention logit scale of a trained checkpoint (``sharpen_attention``; layer lists as tuples).  Nothing is recorded from the
+    reference for these weights: the oracle run in float64 is the ground truth (tests/test_attention_scales.py)."""
+    return sharpen_attention(mdm_weights(), gain, self_layers, cross_layers, encoder_gain)
+
+
 @functools.lru_cache(None)
 def smpl_model():
     return {k: _t(v) for k, v in syn.smplh_model(seed=7).items()}

@@ -327,3 +327,47 @@ def test_well_conditioned_full_size_fixture_pair():
     cos0 = ((r0[..., :3] * r0[..., 3:]).sum(-1) / (r0[..., :3].norm(dim=-1) * r0[..., 3:].norm(dim=-1))).abs().max().item()
     assert cos0 > 0.999                                              # what the older fixture looks like
     close(R.rotation_6d_to_matrix(r6), R.axis_angle_to_matrix(torch.from_numpy(z['body'][..., :66]).reshape(T, B, 22, 3)), 1e-5, 'reference body rotations vs oracle rot6d -> matrix')
+
+
+def test_sharpened_attention_fixture_reaches_trained_softmax_scales(monkeypatch):
+    """tests/fixtures.py mdm_weights_sharp (the weights of tests/test_attention_scales.py): only the Q and K rows of the chosen attentions move, the default fixture is left
+    alone, and the softmax rows the oracle then computes are what the fixture is for -- nearly uniform at gain 1 (largest probability of a self-attention row below 0.1 on
+    average, ~0.2 of a cross-attention row), led by one or two keys at gain 2, saturated at gain 4 -- while the problem stays well conditioned: the oracle's own fp32 run
+    is within 1e-5 of its float64 run (a tenth of the 1e-4 gate), so a whole-forward comparison against float64 stays a sharp test."""
+    base = fx.mdm_weights()
+    keep = {k: v.clone() for k, v in base.items()}
+    one = fx.mdm_weights_sharp(4, (7,), ())
+    for k, v in base.items():
+        assert torch.equal(v, keep[k])
+        if k in ('decoder.layers.7.self_attn.in_proj_weight', 'decoder.layers.7.self_attn.in_proj_bias'):
+            assert torch.equal(one[k][:512], 4 * v[:512]) and torch.equal(one[k][512:], v[512:])
+        else:
+            assert torch.equal(one[k], v), k
+    enc = fx.mdm_weights_sharp(2, None, None, 3)
+    assert torch.equal(enc['encoder.layers.0.self_attn.in_proj_weight'][:512], 3 * base['encoder.layers.0.self_attn.in_proj_weight'][:512])
+    assert torch.equal(enc['decoder.layers.3.multihead_attn.in_proj_bias'][:512], 2 * base['decoder.layers.3.multihead_attn.in_proj_bias'][:512])
+    assert torch.equal(fx.mdm_weights_sharp(2)['encoder.layers.7.self_attn.in_proj_weight'], base['encoder.layers.7.self_attn.in_proj_weight'])
+    B, T = 2, 35
+    x, ts, cond = fx.mdm_inputs(B, T)
+    rows = []
+    real = torch.softmax
+
+    def spy(s, dim=-1, **kw):
+        p = real(s, dim=dim, **kw)
+        if s.dim() == 4 and s.shape[-2] == T and s.shape[-1] in (T, fx.PAST):      # nn.MultiheadAttention's [B, heads, T, keys]: self- and cross-attention (not the QaN taps)
+            rows.append((s.shape[-1], float(p.max(dim=-1)[0].mean())))
+        return p
+    monkeypatch.setattr(torch, 'softmax', spy)
+    top = {}
+    for g in (1, 2, 4):
+        sd = base if g == 1 else fx.mdm_weights_sharp(g)
+        del rows[:]
+        out32 = oden.mdm_forward(sd, x, ts, cond)
+        top[g] = {n: [p for keys, p in rows if keys == n] for n in (T, fx.PAST)}
+        assert len(top[g][T]) == 2 and len(top[g][fx.PAST]) == 8
+        out64 = oden.mdm_forward({k: v.double() for k, v in sd.items()}, x.double(), ts, cond.double())
+        close(out32.double(), out64, 1e-5, 'oracle fp32 vs float64 at gain %d' % g)
+    # mean largest probability of a row, per attention (measured: self 0.075 / 0.041, cross 0.18-0.21 | self 0.37 / 0.09, cross 0.47-0.59 | self 0.82 / 0.50, cross 0.83-0.90)
+    assert max(top[1][T]) <= 0.1 and max(top[1][fx.PAST]) <= 0.25
+    assert max(top[2][T]) >= 0.3 and min(top[2][fx.PAST]) >= 0.4
+    assert max(top[4][T]) >= 0.7 and min(top[4][T]) >= 0.4 and min(top[4][fx.PAST]) >= 0.8

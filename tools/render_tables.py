@@ -8,7 +8,7 @@ Outputs: profiles/TABLES_<round>.md (every block) and, in DESIGN.md / BASELINE.m
 
     <!-- BEGIN GENERATED <block> -->   ...   <!-- END GENERATED <block> -->
 
-is replaced by the freshly rendered block of that name (blocks: headline, legs, roofline, step_table, parity_full, parity_misc).  Nothing between such markers is ever
+is replaced by the freshly rendered block of that name (blocks: headline, legs, roofline, step_table, parity_full, parity_misc, attention_scales).  Nothing between such markers is ever
 edited by hand: round 4 spent 15 of 37 commits re-typing these numbers into five files.  --check: exit 1 if a document would change (CI-style guard)."""
 import argparse
 import json
@@ -154,11 +154,40 @@ def parity_full(p):
 def parity_misc(p):
     out = ['| check (key of the parity file) | worst relative error / result |', '|---|---|']
     for k in sorted(p):
-        if k.startswith('full_size_end_to_end') or k == 'exclusive_cu_report':
+        if k.startswith('full_size_end_to_end') or k == 'exclusive_cu_report' or k.startswith('attn_scale_'):      # (own blocks)
             continue
         e = p[k]
         vals = ', '.join('%s %s' % (kk, sci(v) if isinstance(v, float) else v) for kk, v in e.items() if isinstance(v, (int, float)))
         out.append('| `%s` | %s |' % (k, vals[:260]))
+    return '\n'.join(out)
+
+
+ATTN_ROUTES = ('default', 'amax_split_attention', 'fp32_attention', 'fp32_rowblock', 'all_fp32', 'exact')
+
+
+def attention_scales(p):
+    """The route x gain x shape table of tests/test_attention_scales.py (keys attn_scale_*): per case the oracle's own fp32 error and the HIP error of every route, all vs the oracle in float64."""
+    groups = (('clip lengths, `test_forward_at_trained_logit_scales_every_clip_length`', r'attn_scale_g(\d+)_B(\d+)_T(\d+)$', lambda m: 'B=%s T=%s' % m.groups()[1:]),
+              ('memory lengths at B=2, T=35, `test_forward_at_trained_logit_scales_every_memory_length`', r'attn_scale_g(\d+)_B\d+_T\d+_M(\d+)$', lambda m: 'M=%s' % m.group(2)),
+              ('gain on one attention only, B=2, T=100, `test_one_attention_at_gain_4_localises_a_failure`', r'attn_scale_g(\d+)_(self_layer\d|cross_only)_B\d+_T\d+$', lambda m: m.group(2).replace('_', ' ')),
+              ('encoder, `test_encoder_at_trained_logit_scales`', r'attn_scale_g(\d+)_embeddings_B(\d+)_T(\d+)$', lambda m: '`_get_embeddings` B=%s T=%s' % m.groups()[1:]),
+              ('skeleton-mode denoiser, `test_skeleton_denoiser_at_trained_logit_scales`', r'attn_scale_g(\d+)_skeleton_B(\d+)_T(\d+)$', lambda m: 'B=%s T=%s' % m.groups()[1:]))
+    out = []
+    for title, pat, label in groups:
+        rows = []
+        for k in p:
+            m = re.match(pat, k)
+            if m:
+                nums = [int(x) for x in re.findall(r'\d+', k)]
+                rows.append(((nums[0], nums[-1], k), '| %s | %s | %s | %s |' % (m.group(1), label(m), sci(p[k].get('e_oracle32')), ' | '.join(sci(p[k].get(r)) if r in p[k] else '' for r in ATTN_ROUTES))))
+        if not rows:
+            out.append('*%s: not recorded*' % title)
+            continue
+        out += ['**%s** (max|Δ|/max|ref| vs the oracle in float64):' % title, '', '| gain | case | oracle fp32 | default | amax-per-tile split attention | fp32 attention | fp32 row block | all fp32 | exact |', '|---|---|---|---|---|---|---|---|---|']
+        out += [r for _, r in sorted(rows)]
+        out.append('')
+    e = p.get('attn_scale_g2_B2_T100_chain_20_steps')
+    out.append('**20 plain steps at gain 2, B=2, T=100, `test_twenty_plain_steps_at_trained_scale_graph_equals_eager_and_oracle`**: graph route vs the oracle loop %s (graph route = eager route bit for bit).' % sci((e or {}).get('window_20_steps')))
     return '\n'.join(out)
 
 
@@ -171,7 +200,7 @@ def main():
     prof = os.path.join(ROOT, 'profiles')
     b, p = load_json(os.path.join(prof, '%s_bench.json' % tag)), load_json(os.path.join(prof, 'parity_%s.json' % tag))
     blocks = dict(headline=headline(b, tag, 'round ' + tag[1:].lstrip('0')), legs=legs(b), roofline=roofline(b), step_table=step_table(os.path.join(prof, '%s_kernel_stats_bench.txt' % tag)),
-                  parity_full=parity_full(p), parity_misc=parity_misc(p))
+                  parity_full=parity_full(p), parity_misc=parity_misc(p), attention_scales=attention_scales(p))
     tables = ['# Measured tables of %s (generated by tools/render_tables.py from profiles/%s_bench.json, parity_%s.json, %s_kernel_stats_bench.txt -- do not edit)\n' % (tag, tag, tag, tag)]
     for name, body in blocks.items():
         tables.append('## %s\n\n%s\n' % (name, body))
