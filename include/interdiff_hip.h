@@ -521,6 +521,38 @@ int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, float *arena, f
                                      float *exp_avg, float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps,
                                      double weight_decay, void *stream);
 
+/* ---- TRAINING of the skeleton predictor the way the reference trains it (train_correction_skeleton.py: the module in train()): every BatchNorm2d
+ * normalises with the statistics of the BATCH (biased variance, eps 1e-5) and updates its running buffers; nn.Dropout(p) follows the tcn BatchNorm
+ * of every ST_GCNN_layer (model/layers.py:308-318).  Device code: csrc/skeleton_bn_train.h around the fine-tuner's csrc/skeleton_train.h; launchers
+ * csrc/skeleton_train.hip.  Additive entries: interdiff_abi_version() stays what it was.  Parameter and buffer layouts: the PARAMETER TABLE above.
+ *
+ * interdiff_skeleton_train_grads   replaces loss.backward() on LitObjInteraction._common_step (train_correction_skeleton.py:128-154) with the module
+ *      in train(), and the buffer updates torch.nn.BatchNorm2d.forward makes there.  Arguments as interdiff_skeleton_finetune_grads, and:
+ *      bn [n_bn]  running mean / variance, READ AND WRITTEN IN PLACE when update_running = 1: running <- (1 - momentum) running + momentum {mean,
+ *                 variance n / (n - 1)}; untouched (and never read) when update_running = 0.
+ *      p_drop in [0, 1); masks: device uint8, one byte per element, the 12 layers in named_parameters() order, each [B][cout][20][nodes], keep iff
+ *                 nonzero, kept values times fp32(1 / (1 - p_drop)); NULL: the masks interdiff_skeleton_train_masks(seed, step) writes (p_drop = 0:
+ *                 no dropout, nothing is drawn).
+ *      batch_stats [n_bn] or NULL: mean and BIASED variance of this batch in the layout of bn.
+ *      op->arena must hold the gcn.T / gcn.A / PReLU values of `params` (interdiff_skeleton_finetune_step keeps it so); the convolutions and the
+ *      BatchNorm affine parameters are read from `params`, unfolded.
+ *      17 launches of one 1024-thread workgroup per clip, cut wherever a BatchNorm needs the whole batch (no grid barrier inside a kernel), then the
+ *      fold over clips and the statistics kernel, all on `stream`.  Statistics and their gradients are merged over the clips in ascending order in
+ *      double (Chan's merge of per-clip (sum, M2)); no atomics: two calls give the same bits.  The gradients of the 24 convolution biases, which cancel
+ *      inside the batch normalisation, are written as exact 0.  IDF_E_INVAL: null pointer, B < 1, T != op->T, p_drop outside [0, 1), momentum outside
+ *      [0, 1], update_running not 0 / 1, short workspace.
+ * interdiff_skeleton_train_masks   replaces the Bernoulli draw of nn.Dropout in train(): the keep masks of training step `step` in the layout above,
+ *      Philox4x32-10 keyed by `seed`, counter (element index / 4, layer, step); an element keeps iff its uniform draw in [0, 1) is >= p_drop.
+ * interdiff_skeleton_train_workspace_bytes   the workspace interdiff_skeleton_train_grads needs at batch B (0: bad arguments).
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_skeleton_train_workspace_bytes(const idf_skel_objproj *op, int32_t B);
+int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const float *params, float *bn, const float *obj_angles, const float *obj_trans,
+                                   const float *human_points, const float *pose_gt, int32_t B, int32_t T, const float *weights8, double p_drop,
+                                   const uint8_t *masks, uint64_t seed, uint64_t step, double momentum, int32_t update_running, float *out9,
+                                   float *grads, float *batch_stats, void *ws, size_t ws_bytes, void *stream);
+int interdiff_skeleton_train_masks(const idf_skel_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
+                                   void *stream);
+
 /* ---- the skeleton DENOISER (model/diffusion_skeleton.py MDM): the decoder / encoder of idf_mdm_weights with token width
  * C = n_body + 3 n_points + 7 = 106 (W_in = [bodyEmbedding | objEmbedding | 7 zero columns], feed-forward width <= 1024 zero-padded
  * into the 1024-wide streams) and a KEYPOINT HEAD instead of two plain linears: bodyFinalLinear gives the n_body body channels,

@@ -158,6 +158,10 @@ _SIGS = {
     'interdiff_skeleton_finetune_grads': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(f32), vp, vp, vp, sz, vp]),
     'interdiff_skeleton_finetune_step': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double,
                                                    C.c_double, vp]),
+    'interdiff_skeleton_train_workspace_bytes': (sz, [C.POINTER(SkelObjProj), i32]),
+    'interdiff_skeleton_train_grads': (C.c_int, [C.POINTER(SkelObjProj), vp, vp, vp, vp, vp, vp, i32, i32, C.POINTER(f32), C.c_double, vp, u64, u64,
+                                                 C.c_double, i32, vp, vp, vp, vp, sz, vp]),
+    'interdiff_skeleton_train_masks': (C.c_int, [C.POINTER(SkelObjProj), i32, C.c_double, u64, u64, vp, vp]),
     'interdiff_skeleton_mdm_forward': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_forward_step': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_mdm_forward_step_map': (C.c_int, [C.POINTER(MdmWeights), C.POINTER(SkelHead), vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -1,7 +1,8 @@
 // Fine-tuning of the HO-GCN skeleton correction predictor with FROZEN normalisation statistics (the module in eval() with autograd on):
 // the loss of LitObjInteraction._common_step (train_correction_skeleton.py:128-154) on ObjProjector.forward (model/correction_skeleton.py:68-137),
 // d loss / d theta for every entry of named_parameters(), and torch.optim.Adam (train_correction_skeleton.py:41-47).  Device code; launchers and the
-// fold / Adam / re-fold kernels: csrc/skeleton_train.hip.  Train-mode BatchNorm (batch statistics) and dropout are NOT built.
+// fold / Adam / re-fold kernels: csrc/skeleton_train.hip.  Train-mode BatchNorm (batch statistics) and dropout: csrc/skeleton_bn_train.h, built from the pieces
+// of this file.
 //
 // ONE 16-wave workgroup per clip, like skel_body (csrc/skeleton.h), in three parts:
 //   1. FORWARD on the folded layers of the arena the inference kernels read: st_gcn_layer's arithmetic with every sum compensated (Acc2) on the VALU.  Each
@@ -109,9 +110,11 @@ struct Acc2 {
 // arena, but every sum compensated (Acc2) on the VALU instead of K-blocked on the MFMA: a saved plane is the correctly rounded fp32 value of its exact
 // sum, which is what keeps the gradient inside 4 e_ref of the fp64 one.  Every step reads planes the PREVIOUS step saved to the workspace
 // and writes buf, so nothing is updated in place.
+// ft_fwd_graph: the input planes to sx, the temporal mix and (joint stack) the adjacency product to su / sg -- everything of a layer before its two 1x1
+// convolutions; the train-mode layer (csrc/skeleton_bn_train.h) shares it.
 template <bool V2>
-__device__ inline void ft_layer_fwd(float *buf, const LayerP &p, int cin, int cout, int nodes, float *sx, float *su, float *sg, float *sh) {
-    const int tid = threadIdx.x, npos = NP * nodes, cinp = pad16(cin);
+__device__ inline void ft_fwd_graph(const float *buf, const LayerP &p, int cin, int nodes, float *sx, float *su, float *sg) {
+    const int tid = threadIdx.x, npos = NP * nodes;
     for (int i = tid; i < cin * npos; i += NTHR) sx[i] = buf[i];
     __syncthreads();
     // temporal mix: u[c][q][v] = sum_t x[c][t][v] Tm[(v)][t][q]
@@ -136,6 +139,12 @@ __device__ inline void ft_layer_fwd(float *buf, const LayerP &p, int cin, int co
         }
         __syncthreads();
     }
+}
+
+template <bool V2>
+__device__ inline void ft_layer_fwd(float *buf, const LayerP &p, int cin, int cout, int nodes, float *sx, float *su, float *sg, float *sh) {
+    const int tid = threadIdx.x, npos = NP * nodes, cinp = pad16(cin);
+    ft_fwd_graph<V2>(buf, p, cin, nodes, sx, su, sg);
     // h = Wt' g + bt' + Wr' x + br' in one compensated sum; PReLU
     const float slope = p.prelu;
     for (int i = tid; i < cout * npos; i += NTHR) {
@@ -166,15 +175,13 @@ __device__ inline void ft_stack_fwd(float *buf, const idf_skel_objproj &op, cons
     }
 }
 
-// ---- backward of one layer: dy = cout gradient planes in, cin gradient planes out (in place); parameter gradients to part[]
-__device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, const FtLayer &L, const float *ws, float *G, float *X, float *part) {
-    const int tid = threadIdx.x, cin = L.cin, cout = L.cout, nodes = L.nodes, npos = NP * nodes, cinp = pad16(cin);
-    const float *sx = ws + L.ws_x, *sg = ws + L.ws_g, *sh = ws + L.ws_h;
-    // 1. PReLU: dh = dy * (h > 0 ? 1 : slope); d slope = sum over h <= 0 of dy * h (a strided walk per thread, then a tree: fixed order)
+// ---- backward of one layer, in three pieces (the train-mode layer, csrc/skeleton_bn_train.h, shares the first and the last)
+// PReLU: dh = dy * (h > 0 ? 1 : slope) in place; d slope = sum over h <= 0 of dy * h (a strided walk per thread, then a tree: fixed order)
+__device__ inline void ft_bwd_prelu(float *dy, float *red, float slope, const float *sh, const FtLayer &L, float *part) {
+    const int tid = threadIdx.x, n = L.cout * NP * L.nodes;
     {
-        const float slope = p.prelu;
         Acc2 acc;
-        for (int i = tid; i < cout * npos; i += NTHR) {
+        for (int i = tid; i < n; i += NTHR) {
             const float h = sh[i], d = dy[i];
             if (h > 0.f) {
                 dy[i] = d;
@@ -191,44 +198,13 @@ __device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, cons
         }
         if (tid == 0) part[L.pr] = red[0];
     }
-    // 2. folded convolution weights and biases: dWt'[o][c] = sum_pos dh[o][pos] g[c][pos], dWr'[o][c] = sum_pos dh[o][pos] x[c][pos], db' = sum_pos dh[o][pos]
-    for (int idx = tid; idx < cout * cin + cout; idx += NTHR) {
-        if (idx < cout * cin) {
-            const int o = idx / cin, c = idx - o * cin;
-            const float *d = dy + o * npos, *gp = sg + c * npos, *xp = sx + c * npos;
-            Acc2 a, b;
-            for (int pos = 0; pos < npos; ++pos) {
-                const float dv = d[pos];
-                a.mac(dv, gp[pos]);
-                b.mac(dv, xp[pos]);
-            }
-            part[L.Wt + idx] = a.value();
-            part[L.Wr + idx] = b.value();
-        } else {
-            const int o = idx - cout * cin;
-            const float *d = dy + o * npos;
-            Acc2 a;
-            for (int pos = 0; pos < npos; ++pos) a.add(d[pos]);
-            part[L.bt + o] = a.value();
-            part[L.br + o] = a.value();
-            // the BatchNorm gamma / beta slots carry nothing per clip (skel_ft_convert_kernel derives them from the folded gradients): written as zeros so
-            // that every element of partials[b][.] is written, and what the fold sums there is defined
-            part[L.gt + o] = 0.f; part[L.bet + o] = 0.f; part[L.gr + o] = 0.f; part[L.ber + o] = 0.f;
-        }
-    }
-    // 3. G = Wt'^T dh (gradient of the mixed planes), X = Wr'^T dh (the residual branch's share of dx) -> workspace
-    for (int i = tid; i < cin * npos; i += NTHR) {
-        const int c = i / npos, pos = i - c * npos;
-        Acc2 a, b;
-        for (int o = 0; o < cout; ++o) {
-            const float d = dy[o * npos + pos];
-            a.mac(p.Wt[o * cinp + c], d);
-            b.mac(p.Wr[o * cinp + c], d);
-        }
-        G[i] = a.value();
-        X[i] = b.value();
-    }
-    __syncthreads();
+}
+
+// the graph part: G = the gradient of the mixed planes g, X = the residual branch's share of dx (both [cin][npos], read only from here on); dy: scratch in
+// (its planes are dead), dx out.  dA and dT to part[].
+__device__ inline void ft_bwd_graph(float *dy, const LayerP &p, const FtLayer &L, const float *ws, const float *G, const float *X, float *part) {
+    const int tid = threadIdx.x, cin = L.cin, nodes = L.nodes, npos = NP * nodes;
+    const float *sx = ws + L.ws_x;
     // 4. adjacency product: dA[t][v][w] = sum_c u[c][t][v] G[c][t][w]; du[c][t][v] = sum_w G[c][t][w] A[t][v][w] -> dy (dh is dead)
     if (L.v2) {
         const float *su = ws + L.ws_u;
@@ -287,6 +263,53 @@ __device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, cons
         }
     }
     __syncthreads();
+}
+
+// backward of one layer: dy = cout gradient planes in, cin gradient planes out (in place); parameter gradients to part[]
+__device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, const FtLayer &L, const float *ws, float *G, float *X, float *part) {
+    const int tid = threadIdx.x, cin = L.cin, cout = L.cout, nodes = L.nodes, npos = NP * nodes, cinp = pad16(cin);
+    const float *sx = ws + L.ws_x, *sg = ws + L.ws_g;
+    // 1. PReLU
+    ft_bwd_prelu(dy, red, p.prelu, ws + L.ws_h, L, part);
+    // 2. folded convolution weights and biases: dWt'[o][c] = sum_pos dh[o][pos] g[c][pos], dWr'[o][c] = sum_pos dh[o][pos] x[c][pos], db' = sum_pos dh[o][pos]
+    for (int idx = tid; idx < cout * cin + cout; idx += NTHR) {
+        if (idx < cout * cin) {
+            const int o = idx / cin, c = idx - o * cin;
+            const float *d = dy + o * npos, *gp = sg + c * npos, *xp = sx + c * npos;
+            Acc2 a, b;
+            for (int pos = 0; pos < npos; ++pos) {
+                const float dv = d[pos];
+                a.mac(dv, gp[pos]);
+                b.mac(dv, xp[pos]);
+            }
+            part[L.Wt + idx] = a.value();
+            part[L.Wr + idx] = b.value();
+        } else {
+            const int o = idx - cout * cin;
+            const float *d = dy + o * npos;
+            Acc2 a;
+            for (int pos = 0; pos < npos; ++pos) a.add(d[pos]);
+            part[L.bt + o] = a.value();
+            part[L.br + o] = a.value();
+            // the BatchNorm gamma / beta slots carry nothing per clip (skel_ft_convert_kernel derives them from the folded gradients): written as zeros so
+            // that every element of partials[b][.] is written, and what the fold sums there is defined
+            part[L.gt + o] = 0.f; part[L.bet + o] = 0.f; part[L.gr + o] = 0.f; part[L.ber + o] = 0.f;
+        }
+    }
+    // 3. G = Wt'^T dh (gradient of the mixed planes), X = Wr'^T dh (the residual branch's share of dx) -> workspace
+    for (int i = tid; i < cin * npos; i += NTHR) {
+        const int c = i / npos, pos = i - c * npos;
+        Acc2 a, b;
+        for (int o = 0; o < cout; ++o) {
+            const float d = dy[o * npos + pos];
+            a.mac(p.Wt[o * cinp + c], d);
+            b.mac(p.Wr[o * cinp + c], d);
+        }
+        G[i] = a.value();
+        X[i] = b.value();
+    }
+    __syncthreads();
+    ft_bwd_graph(dy, p, L, ws, G, X, part);
 }
 
 __device__ inline void ft_stack_bwd(float *dy, float *red, const idf_skel_objproj &op, const FtPlan &plan, int stack, int nodes, const float *ws, float *G,
@@ -369,17 +392,19 @@ __device__ inline void ft_rot_head(const double *d, const double *dq, double *q,
     }
 }
 
-// the whole clip: forward with saves, loss sums, loss gradient, backward.  All NTHR threads call it together; sm: FT_LDS bytes.
-__device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &op, const Src &s, const FtPlan &plan, const FtArgs &a, int B, int b) {
-    float *buf = sm, *keep = sm + BUF, *small = keep + KEEP, *red = small + FT_SMALL;
-    float *og6 = small, *og = small + 96, *res = small + 288, *err = small + 480, *dres = small + 624;     // [past][9] [9][NP] [NP][9] [NP][7] [NP][9]
-    double *errd = reinterpret_cast<double *>(small + 808);                                               // [NP][7] the pose error in double (8-byte aligned: BUF + KEEP + 808 is even)
-    const int tid = threadIdx.x, past = op.past_len;
-    const float *Dp = op.arena + op.dct_pad, *Df = op.arena + op.dct, *Di = op.arena + op.idct;
-    float *ws = a.ws_clips + (size_t)b * plan.ws_clip, *G = ws + plan.ws_clip - 2 * BUF, *X = G + BUF;
-    float *part = a.partials + (size_t)b * plan.n_param;
+// ---- the pieces of a clip around the three stacks; sm: FT_LDS bytes = buf [BUF] | keep [KEEP] | small [FT_SMALL] | red [FT_RED].  All NTHR threads call
+// each of them together.  The train-mode kernels (csrc/skeleton_bn_train.h) run the same pieces with a kernel boundary wherever a BatchNorm needs the batch.
+#define FT_LDS_POINTERS \
+    float *buf = sm, *keep = sm + BUF, *small = keep + KEEP; \
+    float *og6 = small, *og = small + 96, *res = small + 288, *err = small + 480, *dres = small + 624;     /* [past][9] [9][NP] [NP][9] [NP][7] [NP][9] */ \
+    double *errd = reinterpret_cast<double *>(small + 808);      /* [NP][7] the pose error in double (8-byte aligned: BUF + KEEP + 808 is even) */ \
+    const int tid = threadIdx.x, past = op.past_len; \
+    const float *Dp = op.arena + op.dct_pad, *Df = op.arena + op.dct, *Di = op.arena + op.idct; \
+    (void)buf; (void)og6; (void)og; (void)res; (void)err; (void)dres; (void)errd; (void)past; (void)Dp; (void)Df; (void)Di; (void)tid;
 
-    // ================= forward (the non-hook path of skel_body, csrc/skeleton.h) =================
+// past object pose as 6D | translation, its DCT og, the relative branch's input -> buf and keep[.][.][1 + p]  (the non-hook path of skel_body, csrc/skeleton.h)
+__device__ inline void ft_inputs(float *sm, const idf_skel_objproj &op, const Src &s, int B, int b) {
+    FT_LDS_POINTERS
     if (tid < past) {
         const int t = tid;
         float m[6];
@@ -414,7 +439,11 @@ __device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &
         keep[c * NP * NJ + k * NJ + 1 + p] = v;
     }
     __syncthreads();
-    ft_stack_fwd(buf, op, plan, 0, J, ws);
+}
+
+// buf = the relative stack's output: keep[.][.][1 + p] = rel + stack(rel) (+ the DCT of the body over all frames in the translation channels)
+__device__ inline void ft_join_relative(float *sm, const idf_skel_objproj &op, const Src &s, int B, int b) {
+    FT_LDS_POINTERS
     for (int i = tid; i < CH * NP * J; i += NTHR) {
         const int c = i / (NP * J), r = i - c * NP * J, k = r / J, p = r - k * J;
         float *kp = keep + c * NP * NJ + k * NJ + 1 + p;
@@ -427,9 +456,18 @@ __device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &
         *kp = v;
     }
     __syncthreads();
+}
+
+// the object-only stack's input: buf = og
+__device__ inline void ft_object_input(float *sm, const idf_skel_objproj &op) {
+    FT_LDS_POINTERS
     for (int i = tid; i < CH * NP; i += NTHR) buf[i] = og[i];
     __syncthreads();
-    ft_stack_fwd(buf, op, plan, 1, 1, ws);
+}
+
+// buf = the object-only stack's output: keep[.][.][0] = og + stack(og); then buf = keep, the joint stack's input
+__device__ inline void ft_join_object(float *sm, const idf_skel_objproj &op) {
+    FT_LDS_POINTERS
     for (int i = tid; i < CH * NP; i += NTHR) {
         const int c = i / NP, k = i - c * NP;
         keep[c * NP * NJ + k * NJ] = og[i] + buf[i];
@@ -437,7 +475,12 @@ __device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &
     __syncthreads();
     for (int i = tid; i < KEEP; i += NTHR) buf[i] = keep[i];
     __syncthreads();
-    ft_stack_fwd(buf, op, plan, 2, NJ, ws);
+}
+
+// buf = the joint stack's output: keep += buf; the IDCT of node 0, the pose error and the clip's 8 sums of squares, the loss gradient on the pose and the
+// rotation head's backward -> dres [NP][9]
+__device__ inline void ft_head(float *sm, const idf_skel_objproj &op, const FtArgs &a, int B, int b) {
+    FT_LDS_POINTERS
     for (int i = tid; i < KEEP; i += NTHR) keep[i] += buf[i];
     __syncthreads();
     for (int i = tid; i < NP * CH; i += NTHR) {
@@ -510,8 +553,11 @@ __device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &
         for (int c = 0; c < 3; ++c) dres[t * CH + 6 + c] = (float)dp[c];
     }
     __syncthreads();
-    // ================= backward =================
-    // IDCT of node 0: d keep[c][k][0] = sum_t idct[t][k] dres[t][c]; the other nodes get exactly 0
+}
+
+// IDCT of node 0: d keep[c][k][0] = sum_t idct[t][k] dres[t][c]; the other nodes get exactly 0.  -> keep and buf (the joint stack's output gradient)
+__device__ inline void ft_head_bwd(float *sm, const idf_skel_objproj &op) {
+    FT_LDS_POINTERS
     for (int i = tid; i < KEEP; i += NTHR) {
         const int c = i / (NP * NJ), r = i - c * NP * NJ, k = r / NJ, n = r - k * NJ;
         Acc2 acc;
@@ -522,20 +568,51 @@ __device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &
         buf[i] = v;
     }
     __syncthreads();
-    ft_stack_bwd(buf, red, op, plan, 2, NJ, ws, G, X, part);
-    for (int i = tid; i < KEEP; i += NTHR) keep[i] += buf[i];          // skip connection of the joint stack
+}
+
+// buf = the joint stack's input gradient: keep += buf (its skip connection); then buf = node 0, the object-only stack's output gradient (its own skip
+// connection ends at the input)
+__device__ inline void ft_split_object(float *sm) {
+    float *buf = sm, *keep = sm + BUF;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < KEEP; i += NTHR) keep[i] += buf[i];
     __syncthreads();
-    for (int i = tid; i < CH * NP; i += NTHR) {                          // node 0 = the object-only branch; its skip connection ends at the input
+    for (int i = tid; i < CH * NP; i += NTHR) {
         const int c = i / NP, k = i - c * NP;
         buf[i] = keep[c * NP * NJ + k * NJ];
     }
     __syncthreads();
-    ft_stack_bwd(buf, red, op, plan, 1, 1, ws, G, X, part);
-    for (int i = tid; i < CH * NP * J; i += NTHR) {                      // nodes 1.. = the relative branch
+}
+
+// buf = nodes 1.., the relative stack's output gradient
+__device__ inline void ft_split_relative(float *sm) {
+    float *buf = sm, *keep = sm + BUF;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < CH * NP * J; i += NTHR) {
         const int c = i / (NP * J), r = i - c * NP * J, k = r / J, p = r - k * J;
         buf[i] = keep[c * NP * NJ + k * NJ + 1 + p];
     }
     __syncthreads();
+}
+
+// the whole clip: forward with saves, loss sums, loss gradient, backward.  All NTHR threads call it together; sm: FT_LDS bytes.
+__device__ __forceinline__ void ft_clip_body(float *sm, const idf_skel_objproj &op, const Src &s, const FtPlan &plan, const FtArgs &a, int B, int b) {
+    float *buf = sm, *red = sm + BUF + KEEP + FT_SMALL;
+    float *ws = a.ws_clips + (size_t)b * plan.ws_clip, *G = ws + plan.ws_clip - 2 * BUF, *X = G + BUF;
+    float *part = a.partials + (size_t)b * plan.n_param;
+    ft_inputs(sm, op, s, B, b);
+    ft_stack_fwd(buf, op, plan, 0, J, ws);
+    ft_join_relative(sm, op, s, B, b);
+    ft_object_input(sm, op);
+    ft_stack_fwd(buf, op, plan, 1, 1, ws);
+    ft_join_object(sm, op);
+    ft_stack_fwd(buf, op, plan, 2, NJ, ws);
+    ft_head(sm, op, a, B, b);
+    ft_head_bwd(sm, op);
+    ft_stack_bwd(buf, red, op, plan, 2, NJ, ws, G, X, part);
+    ft_split_object(sm);
+    ft_stack_bwd(buf, red, op, plan, 1, 1, ws, G, X, part);
+    ft_split_relative(sm);
     ft_stack_bwd(buf, red, op, plan, 0, J, ws, G, X, part);
 }
 

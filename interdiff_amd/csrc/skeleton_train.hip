@@ -1,8 +1,10 @@
 // Fine-tuning of the skeleton correction predictor with frozen normalisation statistics: launchers of the clip kernel (csrc/skeleton_train.h) and the
 // kernels around it -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients to the reference
 // parameters, Adam (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference kernels read.
+// Training with batch statistics and dropout (csrc/skeleton_bn_train.h): the phase launches, the mask generator, the batch statistics / running-buffer
+// update; it shares the fold over clips, Adam and the re-fold with the fine-tuner.
 #include <math.h>
-#include "skeleton_train.h"
+#include "skeleton_bn_train.h"
 
 namespace {
 using namespace idf_skel_train;
@@ -252,6 +254,141 @@ extern "C" int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, floa
     idf_prof_mark(IDF_K_OTHER, st);
     hipLaunchKernelGGL(skel_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
     hipLaunchKernelGGL(skel_ft_refold_kernel, dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+// ================= training with batch statistics and dropout =================
+namespace {
+
+__global__ __launch_bounds__(NTHR) void skel_tr_phase_kernel(const idf_skel_objproj op, const Src s, const FtPlan plan, const TrPlan tp, const FtArgs a,
+                                                             const TrArgs t, int B, int phase) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    tr_phase_body(sm, op, s, plan, tp, a, t, B, blockIdx.x, phase);
+}
+
+// grid (groups of FT_THR elements of the largest layer, 12 layers): out[B * mask[l] + i] = keep
+__global__ __launch_bounds__(FT_THR) void skel_tr_masks_kernel(const FtPlan plan, const TrPlan tp, int B, float p, uint64_t seed, uint64_t step,
+                                                              uint8_t *__restrict__ out) {
+    const int li = blockIdx.y;
+    const size_t n = (size_t)B * plan.L[li].cout * NP * plan.L[li].nodes, i = (size_t)blockIdx.x * FT_THR + threadIdx.x;
+    if (i < n) out[(size_t)B * tp.mask[li] + i] = tr_uniform(seed, step, li, (uint32_t)i) >= p ? 1 : 0;
+}
+
+// one block per layer: mean and biased variance of the batch -> batch_stats (when given), and the running buffers
+// running <- (1 - momentum) running + momentum {mean, var n / (n - 1)} (torch.nn.BatchNorm2d in train()), in double, rounded once
+__global__ __launch_bounds__(2 * MAXC) void skel_tr_stats_kernel(const FtPlan plan, const double *__restrict__ statp, int B, double momentum, int update,
+                                                                float *__restrict__ bn, float *__restrict__ batch_stats) {
+#pragma clang fp contract(off)
+    const int li = blockIdx.x;
+    const FtLayer &L = plan.L[li];
+    if ((int)threadIdx.x >= 2 * L.cout) return;
+    const int br = threadIdx.x / L.cout, o = threadIdx.x - br * L.cout, npos = NP * L.nodes;
+    double mean, var;
+    tr_fold_stats(statp, B, li, br, o, npos, mean, var);
+    const int at = L.bn + 2 * br * L.cout + o;
+    if (batch_stats) {
+        batch_stats[at] = (float)mean;
+        batch_stats[at + L.cout] = (float)var;
+    }
+    if (update) {
+        const double n = (double)B * (double)npos;
+        bn[at] = (float)((1.0 - momentum) * (double)bn[at] + momentum * mean);
+        bn[at + L.cout] = (float)((1.0 - momentum) * (double)bn[at + L.cout] + momentum * (var * (n / (n - 1.0))));
+    }
+}
+
+// workspace (floats): partials [B][n_param] | loss_part [B][8] | clips [B][ws_clip] | statp, dyp [B][TR_SEAM] doubles | masks [B][mask_clip] bytes
+struct TrWs {
+    size_t partials, loss_part, clips, statp, dyp, masks, total;
+};
+TrWs tr_ws(const FtPlan &P, const TrPlan &T, int B) {
+    TrWs w{};
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
+    w.partials = take((size_t)B * P.n_param);
+    w.loss_part = take((size_t)B * 8);
+    w.clips = take((size_t)B * T.ws_clip);
+    w.statp = take((size_t)B * TR_SEAM * 2);
+    w.dyp = take((size_t)B * TR_SEAM * 2);
+    w.masks = take(((size_t)B * T.mask_clip + 3) / 4);
+    w.total = o;
+    return w;
+}
+
+void tr_launch_masks(const FtPlan &P, const TrPlan &T, int B, double p, uint64_t seed, uint64_t step, uint8_t *out, hipStream_t st) {
+    size_t widest = 0;
+    for (int li = 0; li < 12; ++li) widest = std::max(widest, (size_t)B * P.L[li].cout * NP * P.L[li].nodes);
+    hipLaunchKernelGGL(skel_tr_masks_kernel, dim3((unsigned)((widest + FT_THR - 1) / FT_THR), 12), dim3(FT_THR), 0, st, P, T, B, (float)p, seed, step, out);
+}
+
+}  // namespace
+
+extern "C" size_t interdiff_skeleton_train_workspace_bytes(const idf_skel_objproj *op, int32_t B) {
+    if (!op || B < 1 || ft_check_widths(op) != IDF_OK) return 0;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    return tr_ws(P, tr_plan(P), B).total * sizeof(float);
+}
+
+extern "C" int interdiff_skeleton_train_masks(const idf_skel_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
+                                              void *stream) {
+    if (!masks_out || ft_check_widths(op) != IDF_OK || B < 1 || !(p_drop >= 0.0 && p_drop < 1.0)) return IDF_E_INVAL;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    tr_launch_masks(P, tr_plan(P), B, p_drop, seed, step, masks_out, idf_stream(stream));
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+extern "C" int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const float *params, float *bn, const float *obj_angles, const float *obj_trans,
+                                              const float *human_points, const float *pose_gt, int32_t B, int32_t T, const float *weights8, double p_drop,
+                                              const uint8_t *masks, uint64_t seed, uint64_t step, double momentum, int32_t update_running, float *out9,
+                                              float *grads, float *batch_stats, void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !bn || !obj_angles || !obj_trans || !human_points || !pose_gt || !weights8 || !out9 || !grads || !ws) return IDF_E_INVAL;
+    if (ft_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
+    if (!(p_drop >= 0.0 && p_drop < 1.0) || !(momentum >= 0.0 && momentum <= 1.0) || (update_running != 0 && update_running != 1)) return IDF_E_INVAL;
+    const FtPlan P = ft_plan(op->cin, op->cout);
+    const TrPlan TP = tr_plan(P);
+    const TrWs W = tr_ws(P, TP, B);
+    if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
+    float *base = static_cast<float *>(ws);
+    hipStream_t st = idf_stream(stream);
+    const int past = op->past_len, fut = T - past;
+    LossK lk;
+    FtArgs a{};
+    for (int k = 0; k < 8; ++k) {
+        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 4;
+        const double n = frames * (double)B * width;
+        lk.w[k] = weights8[k];
+        lk.inv_n[k] = (float)(1.0 / n);
+        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
+    }
+    a.pose_gt = pose_gt;
+    a.partials = base + W.partials;
+    a.loss_part = base + W.loss_part;
+    a.ws_clips = base + W.clips;
+    Src s{};
+    s.angles = obj_angles; s.trans = obj_trans; s.human = human_points;
+    TrArgs t{};
+    t.params = params;
+    t.statp = reinterpret_cast<double *>(base + W.statp);
+    t.dyp = reinterpret_cast<double *>(base + W.dyp);
+    t.scale = (float)(1.0 / (1.0 - p_drop));
+    t.masks = masks;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (idf_opt_in_lds(reinterpret_cast<const void *>(skel_tr_phase_kernel), (int)TR_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
+    idf_prof_mark(IDF_K_OTHER, st);
+    if (!masks && p_drop > 0.0) {                       // the generator's masks go through the same buffer layout as injected ones
+        uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
+        tr_launch_masks(P, TP, B, p_drop, seed, step, mb, st);
+        t.masks = mb;
+    }
+    for (int phase = 0; phase < TR_PHASES; ++phase)
+        hipLaunchKernelGGL(skel_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, s, P, TP, a, t, B, phase);
+    hipLaunchKernelGGL(skel_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+                       lk, grads, out9);
+    if (batch_stats || update_running)
+        hipLaunchKernelGGL(skel_tr_stats_kernel, dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
     idf_prof_mark(-1, st);
     IDF_CHECK_LAUNCH();
     return IDF_OK;

@@ -6,8 +6,9 @@ temporal and adjacency matrices, the PReLU slopes.
     loss, grads     LitObjInteraction._common_step + loss.backward()  train_correction_skeleton.py:128-154, :85-126
     training_step   + torch.optim.Adam(lr, weight_decay=l2_norm).step()  :41-47, :182-189
 
-NOT built: train-mode BatchNorm (batch statistics, running-statistics updates) and dropout -- so training from scratch is not
-built --, the SMPL predictor's trainer, learning-rate schedules and the Lightning glue.
+Training from scratch -- the module in ``train()``: batch statistics, running-statistics updates, dropout -- is
+``interdiff_amd.skeleton_train.SkeletonTrainer``, built on this class.  NOT built: the SMPL predictor's trainer, learning-rate
+schedules, the Lightning glue and the dataset.
 
 All arithmetic runs in libinterdiff_hip.so (csrc/skeleton_train.h / .hip): one workgroup per clip for forward, loss gradient and
 backward, a fixed-order fold over clips, Adam on fp32 master parameters in the reference layout, and the re-fold into the arena
@@ -140,7 +141,8 @@ class SkeletonFineTuner:
         return self._ws[B]
 
     # ---- the step
-    def _grads(self, batch):
+    def _inputs(self, batch):
+        """-> (B, T, d6_tail, obj_trans, body_gt, pose_gt), frame-major contiguous fp32 device tensors."""
         dev = self.device
         body_gt, pose_gt = batch[0].transpose(0, 1).float().to(dev).contiguous(), batch[2].transpose(0, 1).float().to(dev).contiguous()
         T, B = pose_gt.shape[:2]
@@ -151,6 +153,11 @@ class SkeletonFineTuner:
         i, j, k, r = qd.unbind(-1)
         two_s = 2.0 / (qd * qd).sum(-1)
         d6_tail = torch.stack([two_s * (i * k + j * r), two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r)], dim=-1).float().contiguous()
+        return B, T, d6_tail, obj_trans, body_gt, pose_gt
+
+    def _grads(self, batch):
+        dev = self.device
+        B, T, d6_tail, obj_trans, body_gt, pose_gt = self._inputs(batch)
         out9 = torch.empty(9, dtype=torch.float32, device=dev)
         grads = torch.empty(self.n_param, dtype=torch.float32, device=dev)
         ws = self._workspace(B)
