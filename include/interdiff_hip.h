@@ -850,6 +850,59 @@ int interdiff_debug_render_setup_vertex(const idf_render_scene *scene, int32_t v
 int interdiff_debug_render_pixel(const int32_t *rec, const int32_t *ij, int32_t *out, int32_t n);
 
 /* ------------------------------------------------------------------------------------
+ * Skeleton-mode clips (csrc/skeleton_render.hip, csrc/skeleton_render.h): the pictures of interdiff/render/viz_helper.py (visualize_skeleton and
+ * visualize_skeleton_pred_gt) without matplotlib -- 21 joints, 12 object keypoints, bones / wires as anti-aliased lines with projecting caps, scatter
+ * markers as discs, matplotlib's per-frame camera restated.  Additive.  The contract (sub-pixel grid, coverage rule, blend arithmetic, bit widths, draw
+ * order) is the head comment of csrc/skeleton_render.h; tests/skeleton_render_oracle.py restates it in numpy.
+ *  idf_skel_view   everything of the camera that does not depend on the frame (HOST struct, computed in double by interdiff_amd/skeleton_render.py):
+ *      view [3][4]: rows u (screen right), v (screen up), w (out of the screen) of the view rotation in box coordinates, each followed by -(row . eye);
+ *      aspect [3]: the box aspect per data axis; margin [3]: the share of the data span added on either side before the 1/48 view margin;
+ *      dist: eye distance (10); kx, cx, ky, cy: X = rint(tx kx + cx), Y = rint(ty ky + cy) in 1/16 pixel, origin top-left, y down (ky < 0);
+ *      line_wd, disc_wd: FULL line width / disc diameter in 1/16 pixel, 1 .. IDF_SKEL_WD_MAX; style: IDF_SKEL_PLAIN or IDF_SKEL_PREDGT;
+ *      pred_from: pred / gt style draws the prediction in frames t >= pred_from; colour [5][4]: RGBA 8-bit -- plain: bones, axis lines, body markers,
+ *      object markers, unused; pred / gt: pred bones, axis lines, pred wires, gt bones, gt wires.
+ *  interdiff_skeleton_render_frames   B clips x T frames, H x W pixels each, white background.  body f32 [B][T][21][3], obj f32 [B][T][12][3];
+ *      body_gt f32 [B][T_gt][21][3], obj_gt f32 [B][T_gt][12][3] (pred / gt style only, both or neither; drawn in frames t < T_gt);
+ *      wires int32 [n_wires][2] (DEVICE, pred / gt style, n_wires <= IDF_SKEL_MAX_WIRES; a pair with an index outside [0, 12) draws nothing and is
+ *      counted as dropped).  out_rgb uint8 [B][T][H][W][3]; out_setup (nullable) int32 [B][T][IDF_SKEL_MAX_REC][IDF_SKEL_REC_INTS], the frame's
+ *      records in draw order; out_count (nullable) int32 [B][T], the number of slots in use.  *dropped (HOST, nullable): primitives left out because
+ *      an input is not finite, lies behind the eye or a snapped coordinate leaves the guard band of IDF_RENDER_GUARD -- never clamped, the rest is drawn.
+ *      stage_ms (HOST, nullable) f32 [2]: setup, raster (hip events).  ws >= interdiff_skeleton_render_frames_workspace_bytes(1): frames are rendered
+ *      in as many chunks as the workspace asks for, with identical bits.  No float atomics; the only atomic is the 32-bit integer add of the dropped
+ *      counter: two calls give the same bits.  The call synchronises the stream (the counter is read back).
+ *      IDF_E_INVAL: null / misaligned pointer, B, T, H, W out of range (H, W 1..IDF_RENDER_MAX_DIM), a bad style, widths outside 1..IDF_SKEL_WD_MAX,
+ *      n_wires outside 0..IDF_SKEL_MAX_WIRES, one of body_gt / obj_gt without the other; IDF_E_NOMEM: a workspace that does not hold one frame.
+ *  interdiff_skeleton_raster_records   the raster stage alone on the caller's records: recs (DEVICE) int32 [n_frames][IDF_SKEL_MAX_REC][8], the first
+ *      `count` slots of every frame in draw order, each obeying the record contract (|X|, |Y| <= IDF_RENDER_GUARD, wd in 1..IDF_SKEL_WD_MAX; the
+ *      arithmetic is only defined inside it, memory safety does not depend on it) -> out_rgb uint8 [n_frames][H][W][3].  n_frames <= 65535.
+ *  interdiff_debug_skeleton_setup / _pixel   HOST-side instances of one frame's setup (the per-primitive function the kernel's lanes run, looped) and
+ *      of the per-pixel function.  setup: all arrays on the HOST, frame t of clip 0 -> rec int32 [IDF_SKEL_MAX_REC][8], *count, *dropped.
+ *      pixel: rec int32 [n_rec][8] in draw order, ij int32 [n][2] -> out int32 [n][3] = r, g, b of pixel (i, j) after folding every record.
+ * ---------------------------------------------------------------------------------- */
+#define IDF_SKEL_REC_INTS 8
+#define IDF_SKEL_MAX_REC 128
+#define IDF_SKEL_MAX_WIRES 40
+#define IDF_SKEL_WD_MAX 1024
+#define IDF_SKEL_TILE 16
+enum { IDF_SKEL_PLAIN = 0, IDF_SKEL_PREDGT = 1 };
+typedef struct {
+    float view[12];
+    float aspect[3], margin[3];
+    float dist, kx, cx, ky, cy;
+    int32_t line_wd, disc_wd, style, pred_from;
+    uint8_t colour[5][4];
+} idf_skel_view;
+size_t interdiff_skeleton_render_frames_workspace_bytes(int64_t n_frames);
+int interdiff_skeleton_render_frames(const idf_skel_view *view, const float *body, const float *obj, const float *body_gt, const float *obj_gt,
+                                     const int32_t *wires, int32_t n_wires, int64_t B, int32_t T, int32_t T_gt, int32_t H, int32_t W, uint8_t *out_rgb,
+                                     int32_t *out_setup, int32_t *out_count, int64_t *dropped, float *stage_ms, void *ws, size_t ws_bytes, void *stream);
+int interdiff_skeleton_raster_records(const int32_t *recs, int32_t count, int64_t n_frames, int32_t H, int32_t W, uint8_t *out_rgb, void *stream);
+int interdiff_debug_skeleton_setup(const idf_skel_view *view, const float *body, const float *obj, const float *body_gt, const float *obj_gt,
+                                   const int32_t *wires, int32_t n_wires, int32_t T, int32_t T_gt, int32_t t, int32_t *rec, int32_t *count,
+                                   int32_t *dropped);
+int interdiff_debug_skeleton_pixel(const int32_t *rec, int32_t n_rec, const int32_t *ij, int32_t *out, int32_t n);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

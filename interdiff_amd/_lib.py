@@ -98,6 +98,13 @@ class RenderMesh(C.Structure):
                 ('V', i32), ('F', i32), ('frames', i32), ('flags', i32)]
 
 
+class SkelView(C.Structure):
+    _fields_ = [('view', f32 * 12), ('aspect', f32 * 3), ('margin', f32 * 3), ('dist', f32), ('kx', f32), ('cx', f32), ('ky', f32), ('cy', f32),
+                ('line_wd', i32), ('disc_wd', i32), ('style', i32), ('pred_from', i32), ('colour', (C.c_uint8 * 4) * 5)]
+
+
+SKEL_PLAIN, SKEL_PREDGT = 0, 1                             # idf_skel_view.style (IDF_SKEL_*)
+SKEL_REC_INTS, SKEL_MAX_REC, SKEL_MAX_WIRES, SKEL_WD_MAX, SKEL_TILE = 8, 128, 40, 1024, 16
 RMESH_SCENE_SPACE, RMESH_VERTEX_RGB = 1, 2                 # idf_render_mesh.flags (IDF_RMESH_*)
 RENDER_SUBPIX, RENDER_GUARD, RENDER_MAX_DIM, RENDER_ZONE, RENDER_REC_INTS, RENDER_TILE = 16, 32768, 2048, 1 << 28, 20, 16
 
@@ -184,6 +191,12 @@ _SIGS = {
                                           vp, sz, vp]),
     'interdiff_debug_render_setup_vertex': (C.c_int, [C.POINTER(RenderScene), i32, i32, i32, i32, vp, vp, vp, vp, vp, i32]),
     'interdiff_debug_render_pixel': (C.c_int, [vp, vp, vp, i32]),
+    'interdiff_skeleton_render_frames_workspace_bytes': (sz, [i64]),
+    'interdiff_skeleton_render_frames': (C.c_int, [C.POINTER(SkelView), vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, vp, vp, C.POINTER(i64),
+                                                   C.POINTER(f32), vp, sz, vp]),
+    'interdiff_skeleton_raster_records': (C.c_int, [vp, i32, i64, i32, i32, vp, vp]),
+    'interdiff_debug_skeleton_setup': (C.c_int, [C.POINTER(SkelView), vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
+    'interdiff_debug_skeleton_pixel': (C.c_int, [vp, i32, vp, vp, i32]),
     'interdiff_optimize_init': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, i32, vp]),
     'interdiff_optimize_loss_grad': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
