@@ -138,7 +138,7 @@ typedef struct {
                                   [10 tiles][2 planes][64 lanes][8 halves], rows past 768 zero; mdm.py pack_linear160_h2; csrc/ffn_h2.h
                                   ln_linear_h2_kernel).  The kernel scales every input row by a power of two, so only the weights' range matters */
     int64_t qc_h2;             /* QaN only: 0, or Qc as two f16 planes in the split-f16 row block's fragment order [4 K quarters][2 K steps][3 taps][2 planes][4 kq][NQ][8 halves]
-                                  (mdm.py qan_fragments_h2; csrc/denoiser.hip rowblock_kernel<.., H2>) */
+                                  (mdm.py qan_fragments_h2; csrc/rowblock.h rowblock_kernel<.., H2>) */
     int64_t rb_h2_ok;          /* decoder layers: 1 when the packer has proved that the LayerNorm outputs this layer's row block contracts (LN_prev, norm1) stay inside
                                   the f16 range (16 max|gamma| + max|beta| < 65504; mdm.py ln_h2_range_ok) -- with tune[IDF_TUNE_FFN_MATH] == 1 the row block then runs
                                   its three contractions as split-f16 products; 0 = always exact fp32 */
@@ -188,7 +188,7 @@ typedef struct {
      * IDF_MDM_MEM_MAX is served; 10 takes the compact (fast) layout of the folded memory, other lengths a generic one (one more score-column tile in the row
      * block).  A memctx folded at one length must be consumed at the same length (its size differs: interdiff_mdm_memctx_floats_for). */
     int32_t mem_len;
-    /* tokens per workgroup of the split-f16 row block (csrc/denoiser.hip rowblock8_kernel): 0 = by the launch (8 while B x ceil(T / 8) workgroups fit the chip in one
+    /* tokens per workgroup of the split-f16 row block (csrc/rowblock.h rowblock8_kernel): 0 = by the launch (8 while B x ceil(T / 8) workgroups fit the chip in one
      * round, else 16), 8 / 16 = forced (A/B runs).  Both forms compute the same bits. */
     int32_t rb_tokens;
 } idf_mdm_weights;
@@ -204,7 +204,7 @@ int interdiff_gemm_f32(const float *A, int32_t lda, const float *W, const float 
  *   G   [L][B][40][256]  (scores = x . G^T + g0, 40 = heads*MEM, pre-scaled by 1/sqrt(64))
  *   VWT [L][B][256][48]  (out = P . VW + out_bias, stored output-column-major, 40 padded to 48)
  *   g0  [L][B][40]
- * and, behind them, the same G / VW as split-f16 plane fragments for the row block's f16-MFMA form (csrc/denoiser.hip G_H2 / VW_H2: each (layer,
+ * and, behind them, the same G / VW as split-f16 plane fragments for the row block's f16-MFMA form (csrc/denoiser_common.h G_H2, csrc/rowblock.h VW_H2: each (layer,
  * clip) matrix divided by the power of two that puts its largest magnitude in [2^13, 2^14), two f16 planes, fragment order) with the two powers
  * of two per (layer, clip).  Both forms are always folded; which one a forward reads follows tune[IDF_TUNE_FFN_MATH].  The layout is private to
  * the library: `memctx` is an opaque buffer of interdiff_mdm_memctx_floats(B) floats.
@@ -225,7 +225,7 @@ int interdiff_mdm_prepare_memory(const idf_mdm_weights *w, const float *cond, in
  * Size limits (IDF_E_INVAL beyond them): T <= max_T of the packed positional table (mdm.py pack_mdm_weights(max_T=): up to the 5000 rows of the
  * reference's PositionalEncoding).  Up to T = 208 the temporal self-attention of the two standard layers parks K and V of one (clip, head) in one CU's
  * LDS (2 x T x 68 floats + the score tile = 149 KiB at T = 208: the fast path, every BASELINE shape); longer clips take a K/V-tiled form of the same
- * attention (64-key tiles, running row maximum / sum; csrc/denoiser.hip self_attn_tiled_kernel) -- correct, not tuned.  Memory length: idf_mdm_weights.mem_len;
+ * attention (64-key tiles, running row maximum / sum; csrc/attn.h self_attn_tiled_kernel) -- correct, not tuned.  Memory length: idf_mdm_weights.mem_len;
  * C <= 256 (any width: W_in's rows are packed zero-padded to a multiple of 4 floats, mdm.py; BASELINE config #1 has C = 106).  The reference itself is bounded only by PositionalEncoding(max_len=5000) (model/layers.py:11); its
  * datasets use T = 35 (eval_smpl_short.py:376-377) and BASELINE.json T = 100.  B is unbounded (clips are independent). */
 int interdiff_mdm_forward(const idf_mdm_weights *w, const float *memctx, const float *x,

@@ -1,4 +1,4 @@
-// THE DEFAULT self-attention of the split arithmetic since round 5 (the fp32 kernel of denoiser.hip is its fallback).  Round 4 built it and
+// THE DEFAULT self-attention of the split arithmetic since round 5 (the fp32 kernel of attn.h is its fallback).  Round 4 built it and
 // left it off the route: owning the CU costs the overlap of two co-resident workgroups, and with V staged as fp32 and transposed through LDS it was 1.5 % slower over whole
 // samples (profiles/r04_attn_split_f16_ab.txt).  With V kept row-major and read by ds_read_b64_tr_b16 -- no staging, no transposition, two barriers fewer: 17.4 k -> 15.2 k
 // cycles per workgroup -- it is 1.2 % FASTER than the fp32 kernel (profiles/r05_attn_split_f16_ab.txt); a denoiser forward is 3.2e-7 from the fp64 answer with it, 4.6e-7 without.
@@ -7,7 +7,7 @@
 //
 //     ctx = softmax(Q K^T / 8) V   per (clip, head);   slab[head] = ctx . W_o[:, head]^T        (torch.nn.MultiheadAttention inside TransformerDecoderLayer)
 //
-// Same contract as denoiser.hip self_attn_kernel<OUTPROJ>: qkv [N][768] in, H partial slabs [N][256] out (the row block sums them).  What differs:
+// Same contract as attn.h self_attn_kernel<OUTPROJ>: qkv [N][768] in, H partial slabs [N][256] out (the row block sums them).  What differs:
 //  * 32 queries per workgroup and ONE workgroup per CU (ceil(T/32) x 4 heads x B = 256 workgroups at T = 100, B = 16: exactly the chip), 512 threads;
 //    the fp32 kernel runs 448 workgroups of 16 queries, two per CU -- a kernel that issues the f16 MFMA must own its CU (ffn_h2.h "exclusive CU"), so the
 //    overlap of two co-resident workgroups is replaced by twice the waves on twice the rows and K / V fetched once per 32 queries instead of per 16;

@@ -44,7 +44,7 @@ static inline int idf_opt_in_lds(const void *fn, int bytes, std::atomic<uint64_t
 //   * hipOccupancyMaxActiveBlocksPerMultiprocessor(kernel, threads, dyn) == 1            -- no second workgroup of the same kernel,
 //   * static + dynamic LDS == 160 KiB                                                     -- no LDS-using workgroup of any other kernel,
 //   * the compiler really allocated >= 256 registers per lane (hipFuncAttributes.numRegs) -- with threads / 256 waves per SIMD no LDS-free wave fits either
-// and returns the dynamic LDS to launch with, or -1: the caller then takes its fp32-MFMA kernel instead (csrc/denoiser.hip) -- a configuration where
+// and returns the dynamic LDS to launch with, or -1: the caller then takes its fp32-MFMA kernel instead (csrc/rowblock.h rowblock_route, csrc/denoiser.hip) -- a configuration where
 // the claim does not hold (LDS partitioning, a compiler that stops honouring the clobber) degrades to the exact arithmetic, never to an unprotected launch
 // and never to IDF_E_LAUNCH.  Every verdict is kept in a table that interdiff_exclusive_cu_report() prints (tests, bench.py).
 struct idf_excl_entry {

@@ -99,7 +99,7 @@ __device__ __forceinline__ void split4(const float4 v, uint2 &hi, uint2 &lo) {
 // The same split WITHOUT the hi plane's flush rule, on packed instructions (v_cvt_pk_f16_f32, v_pk_add_f32, v_pk_mul_f32: 3 VALU instructions per
 // element instead of 8).  gfx950's f16 MFMA honours subnormal inputs (tools/mfma_f16_subnormal_probe.hip: 2^-24 x 2^10 comes out exact), so a subnormal
 // hi is as good as a flushed one.  Every IN-KERNEL split of activations uses this form (x2 rows and hidden activations of the feed-forward kernel, the
-// QKV kernel's scaled rows, the row block's A operands in csrc/denoiser.hip); the pre-packed WEIGHT planes keep the rule (mdm.py split_f16 -- either is exact
+// QKV kernel's scaled rows, the row block's A operands in csrc/rowblock.h); the pre-packed WEIGHT planes keep the rule (mdm.py split_f16 -- either is exact
 // to 2^-22, the two only differ below 2^-14).  tests/ffn_emulator.py restates both.
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));

@@ -61,7 +61,7 @@ def qan_constants(queries, rotary=ROTARY_DEFAULT, heads=HEADS):
 
 
 def qan_fragments(qc):
-    """Qc [NQ, 3, D] -> the row block's MFMA B-operand fragment order [16 k-groups][3 taps][4 kq][NQ][4] (csrc/denoiser.hip FRAG note):
+    """Qc [NQ, 3, D] -> the row block's MFMA B-operand fragment order [16 k-groups][3 taps][4 kq][NQ][4] (csrc/rowblock.h FRAG note):
     lane (kq, li < NQ) holds Qc[li, tap, 16 kg + 4 kq : +4]; a wave's load instruction reads 4 * NQ * 16 contiguous bytes."""
     qc = np.asarray(qc, np.float32)
     nq, _, d = qc.shape
@@ -73,7 +73,7 @@ def qan_fragments(qc):
 
 
 def qan_fragments_h2(qc):
-    """Qc [NQ, 3, D] -> the split-f16 row block's B-operand fragments (csrc/denoiser.hip G_H2 note): [4 waves = K quarter][2 K steps][3 taps]
+    """Qc [NQ, 3, D] -> the split-f16 row block's B-operand fragments (csrc/rowblock.h G_H2 note): [4 waves = K quarter][2 K steps][3 taps]
     [2 planes][4 kq][NQ][8 halves], lane (kq, li < NQ) holds plane(Qc[li, tap, 64 w + 32 s + 8 kq : +8]) -- the v_mfma_f32_16x16x32_f16 operand
     of that lane.  Returned as float32 words (two halves each), the same 7680 words as ``qan_fragments``."""
     qc = np.asarray(qc, np.float32)
@@ -283,7 +283,7 @@ def qkv_bounds_usable(w, b, bnd):
 
 def sa_out_fragments(w):
     """out_proj.weight [256 out, 256 in] -> MFMA B-operand fragment order of the attention kernel's out-projection tail
-    (csrc/denoiser.hip self_attn_kernel<true>): [head][wave = output column quarter][k-group of 16][column tile][lane = kq*16+li][4],
+    (csrc/attn.h self_attn_kernel<true>): [head][wave = output column quarter][k-group of 16][column tile][lane = kq*16+li][4],
     element e of lane (kq, li) = w[(wave*4 + tile)*16 + li][head*64 + 16*kgroup + 4*kq + e]."""
     w = np.asarray(w, np.float32)
     assert w.shape == (D, D)
@@ -709,7 +709,7 @@ class MDM:
                 attn_packed = bool(split and ly.sa_out_frag_h2)
                 planes = bool(attn_packed and ly.sa_in_pack_h2 and ly.qkv_bounds_ok and not bad('ln_linear_h2_kernel<' + slabs + ', planes out>') and not bad('self_attn_h2_kernel<planes in>'))
                 d['qkv'] = 'split' if (split and ly.sa_in_pack_h2 and (planes or not any(n == 'ln_linear_h2_kernel<%s>' % slabs for n in failing))) else 'exact'
-                # csrc/denoiser.hip: the split-f16 attention kernel unless its fragments were not packed; clips longer than 192 frames take the fp32 kernel at launch time (not known here)
+                # csrc/denoiser.hip (mdm_forward_impl_t): the split-f16 attention kernel unless its fragments were not packed; clips longer than 192 frames take the fp32 kernel at launch time (not known here)
                 d['self_attention'] = 'split' if (attn_packed and (planes or 'self_attn_h2_kernel' not in failing)) else 'exact'
                 d['qkv_hands_over_planes'] = planes
             layers.append(d)

@@ -293,7 +293,7 @@ def test_split_f16_ffn_pack_and_kernel_addressing_by_emulation():
 
 
 def test_out_projection_fragments_match_the_attention_kernel_addressing():
-    """mdm.sa_out_fragments vs the loads of self_attn_kernel<true> (csrc/denoiser.hip): lane (kq, li) of wave `wave` reads, for head h,
+    """mdm.sa_out_fragments vs the loads of self_attn_kernel<true> (csrc/attn.h): lane (kq, li) of wave `wave` reads, for head h,
     k-group s and column tile c, the float4 at ((((h*4+wave)*4+s)*4+c)*64+lane)*4 and uses element e as W_o[(wave*4+c)*16+li][h*64+16s+4kq+e];
     the per-head partial products it forms must add up to the plain out-projection."""
     from interdiff_amd.mdm import sa_out_fragments
@@ -364,7 +364,7 @@ def test_split_f16_qkv_pack_and_kernel_addressing_by_emulation():
 
 
 def test_split_f16_row_block_query_fragments_and_range_proof():
-    """The split-f16 row block (csrc/denoiser.hip rowblock_kernel<.., H2>) reads the learned queries as 16-byte plane fragments: wave w (K quarter),
+    """The split-f16 row block (csrc/rowblock.h rowblock_kernel<.., H2>) reads the learned queries as 16-byte plane fragments: wave w (K quarter),
     K step s, tap j, lane (kq, li < NQ) loads word offset ((((2 w + s) 3 + j) 2 + plane) 4 + kq) NQ + li of mdm.py qan_fragments_h2 and contracts its 8
     halves with k = 64 w + 32 s + 8 kq .. + 7 of the token row.  Restated here: the three-product sum over those fragments equals the fp32
     contraction to 2^-21, and the LayerNorm range proof accepts ordinary weights and refuses ones that could leave the f16 range."""

@@ -1323,7 +1323,7 @@ def test_denoiser_edge_sizes(mdm, B, T):
 def test_denoiser_any_memory_length_and_long_clips(lib, M, B, T):
     """The two hard limits of rounds 1-4, lifted behind slower-but-correct paths (round 5):
       * memory length != 10 -- the reference takes --past_len from the CLI (eval_smpl_short.py:376-377; cond = the encoded past frames, model/diffusion_smpl.py:195-223);
-        lengths 1..16 take the generic layout of the folded memory (one 16-column score tile per head, absent slots masked; csrc/denoiser.hip MemLay);
+        lengths 1..16 take the generic layout of the folded memory (one 16-column score tile per head, absent slots masked; csrc/denoiser_common.h MemLay);
       * clips longer than 208 frames -- the reference's bound is PositionalEncoding(max_len=5000) (model/layers.py:10); they take the K/V-tiled self-attention.
     Against oracle/denoiser.py (1e-4) and its float64 run (the split-f16 form as close to fp64 as the exact form, like test_mdm_forward_split_f16_vs_exact_and_fp64),
     both arithmetics; then back to the default shape on the same handle (the compact layout must be undisturbed)."""

@@ -1,4 +1,4 @@
-"""Exact-fp32 vs split-f16 row block (csrc/denoiser.hip rowblock_kernel<.., H2>) under the split-f16 feed-forward / QKV arithmetic: denoiser forward and
+"""Exact-fp32 vs split-f16 row block (csrc/rowblock.h rowblock_kernel<.., H2>) under the split-f16 feed-forward / QKV arithmetic: denoiser forward and
 whole samples, alternating in one process on one box (not product code).  Output -> profiles/r04_rowblock_split_f16_ab.txt."""
 import json
 import os

@@ -1,4 +1,4 @@
-"""Time of the K/V-tiled self-attention (csrc/denoiser.hip self_attn_tiled_kernel: clips longer than 208 frames) next to the one-shot kernels, once (not product code):
+"""Time of the K/V-tiled self-attention (csrc/attn.h self_attn_tiled_kernel: clips longer than 208 frames) next to the one-shot kernels, once (not product code):
     python tools/tiled_attn_time.py   -> per shape: us per launch of the self-attention stage inside a denoiser forward (library profile hooks, HIP events), forward us."""
 import json
 import os
