@@ -36,15 +36,12 @@ class HipCorrection:
         ctx = _lib.CorrectionCtx()
         ctx.smpl = C.pointer(smpl_layer.cmodel)
         ctx.objproj = C.pointer(objprojector.cop)
-        ctx.faces, ctx.adj_ptr = self.topo.faces.data_ptr(), self.topo.adj_ptr.data_ptr()
-        ctx.adj_face, ctx.adj_corner = self.topo.adj_face.data_ptr(), self.topo.adj_corner.data_ptr()
+        self.topo.fill_ctx(ctx)
         ctx.markers_idx = self.markers_idx.data_ptr()
         ctx.n_markers, ctx.n_points, ctx.past_len = len(markers), n_points, past_len
         if self.topo.vorder is not None:       # scan order of the exact nearest-vertex scan (block culling); results do not depend on it
             self.markers_scan = self.topo.scan_positions(markers, self.device)
-            ctx.vorder, ctx.faces_scan, ctx.markers_scan = self.topo.vorder.data_ptr(), self.topo.faces_scan.data_ptr(), self.markers_scan.data_ptr()
-            ctx.adj_pair_scan = self.topo.adj_pair_scan.data_ptr()
-            ctx.vrank = self.topo.vrank.data_ptr()
+            ctx.markers_scan = self.markers_scan.data_ptr()
         ctx.tune = 0                 # bit 1 (value 2, tests and tools): the one-launch predictor after the scan instead of inside its launch
         self.ctx = ctx
         self._ws = {}

@@ -8,15 +8,10 @@
 // used): exact argmin of d2 = (dx*dx + dy*dy) + dz*dz, every operation individually rounded (no
 // FMA contraction -> bit-identical to the CPU oracle), lowest index wins ties.
 #include "common.h"
+#include "vec3.h"
 #include <float.h>
 
 namespace {
-
-__device__ __forceinline__ float3 ld3(const float *p) { return make_float3(p[0], p[1], p[2]); }
-__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ float3 cross3(float3 a, float3 b) {
-    return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
 
 // un-normalised area-weighted normal of vertex v (sum over incident faces, reference order)
 __device__ __forceinline__ float3 vertex_normal_sum(const float *__restrict__ vf, const int32_t *__restrict__ faces,

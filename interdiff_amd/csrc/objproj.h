@@ -11,7 +11,7 @@
 //     [n_pre x past_len] DCT matrix, so only the past markers enter the relative branch,
 //   - the IDCT is evaluated only for the node that the contact rule selects.
 // The ST-GCN layer's arena block and its three products (1x1 convolution tile, temporal mix, adjacency product): csrc/stgcn.h.
-// (Device code in a header since round 6: the correction hook runs PART 1 as sixteen leading workgroups of its contact-scan launch, csrc/correction.hip.)
+// (Device code in a header since round 6: the correction hook runs PART 1 as sixteen leading workgroups of its contact-scan launch, csrc/contact_scan.h.)
 #pragma once
 #include "stgcn.h"
 

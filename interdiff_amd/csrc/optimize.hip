@@ -16,6 +16,7 @@
 #include "common.h"
 #include "rot_math.h"
 #include "rot_dual.h"
+#include "vec3.h"
 #include <cfloat>
 
 namespace {
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void opt_objpts_kernel(const float *__restrict
 // the argmin is bit-identical to geometry.hip and to the oracle), vertices stream through LDS in chunks as (x, y, z, z)
 // records, and the per-vertex "some point is near" bit is a wave ballot folded into a 64-bit scalar mask (SALU work that
 // overlaps the VALU of the other waves), OR-ed into LDS once per 64 vertices.
-// As in correction.hip's contact scan the loop only keeps the running MINIMUM (v_min3_f32 over vertex pairs); which vertex
+// As in contact_scan.h's contact scan the loop only keeps the running MINIMUM (v_min3_f32 over vertex pairs); which vertex
 // it was is settled per block of 8 -- one compare + two selects per point per block -- and resolved after the scan by
 // re-scoring the winning block (the lowest vertex whose bit-identical distance equals the minimum): 17 -> ~11.5 VALU
 // instructions per vertex per thread.
@@ -197,12 +198,6 @@ __global__ __launch_bounds__(NN_T) void opt_nn_kernel(const float *__restrict__ 
         if (i0 < P) yidx[(size_t)n * P + i0] = r0;
         if (i1 < P) yidx[(size_t)n * P + i1] = r1;
     }
-}
-
-__device__ __forceinline__ float3 ld3(const float *p) { return make_float3(p[0], p[1], p[2]); }
-__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ float3 cross3(float3 a, float3 b) {
-    return make_float3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
 
 // vector to the nearest vertex, its norm, and the inside/outside sign from the vertex normal (tools.py:55-61) -- the normal
@@ -661,7 +656,7 @@ int loss_grad(const idf_opt_ctx *c, const idf_opt_state *st, void *stream, bool 
     int rc = interdiff_smpl_forward(m, st->pose, st->betas, st->tr, N, st->verts, st->jtr, st->vposed, st->smpl_ws, st->smpl_ws_bytes, stream);
     if (rc) return rc;
     if (c->geo->vorder && st->porder && st->psort && st->pbox) {
-        // scan order given: the two questions are asked separately, each with its own exact cull (correction.hip) -- nearest vertex per
+        // scan order given: the two questions are asked separately, each with its own exact cull (contact_scan.h, near_mask.h) -- nearest vertex per
         // point by the hook's block-culled scan, "any point within 0.5 m" per vertex against the boxes of 64-point patches
         rc = idf_nn_scan_opt(s, N, T, st->verts, V, st->pts, st->obj_points, P, st->porder, c->geo, st->yidx);            // porder: from interdiff_optimize_init
         if (rc) return rc;

@@ -37,7 +37,7 @@ def morton_order(points, bits=10):
 
 class MeshTopology:
     """Device copies of faces + adjacency for one mesh (built once).  With ``rest_vertices`` [V,3] it also carries the SCAN ORDER of
-    the exact nearest-vertex kernels (csrc/correction.hip): ``vorder`` = Morton order of the rest pose (skinning is spatially smooth,
+    the exact nearest-vertex kernels (csrc/contact_scan.h): ``vorder`` = Morton order of the rest pose (skinning is spatially smooth,
     so 16 consecutive scan positions stay a compact clump under any pose and whole blocks can be culled by their bounding box),
     ``faces_scan`` = faces in scan positions.  Results never depend on the order -- only how many vertex blocks a scan can skip."""
 
@@ -64,6 +64,17 @@ class MeshTopology:
             self.vorder, self.faces_scan = t(order.astype(np.int32)), t(rank[f].astype(np.int32))
             self.adj_pair_scan = t(rank[pair].astype(np.int32))
             self.vrank = t(rank.astype(np.int32))                    # vertex -> scan position on the device: the contact scan reads a frame's vertices coalesced and scatters them
+
+    def fill_ctx(self, ctx, adj_pair=False):
+        """The geometry half of a ``CorrectionCtx``: faces and adjacency (``adj_pair``, original vertex ids, only for a caller whose kernels read it) and,
+        when a scan order exists, ``vorder`` / ``faces_scan`` / ``adj_pair_scan`` / ``vrank``.  Markers, ``markers_scan``, counts and ``tune`` stay the caller's."""
+        ctx.faces, ctx.adj_ptr = self.faces.data_ptr(), self.adj_ptr.data_ptr()
+        ctx.adj_face, ctx.adj_corner = self.adj_face.data_ptr(), self.adj_corner.data_ptr()
+        if adj_pair:
+            ctx.adj_pair = self.adj_pair.data_ptr()
+        if self.vorder is not None:
+            ctx.vorder, ctx.faces_scan, ctx.adj_pair_scan = self.vorder.data_ptr(), self.faces_scan.data_ptr(), self.adj_pair_scan.data_ptr()
+            ctx.vrank = self.vrank.data_ptr()
 
     def scan_positions(self, vertex_ids, device):
         """Scan positions of the given vertices (e.g. the marker set) as a device int32 tensor."""

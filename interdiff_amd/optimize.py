@@ -28,14 +28,10 @@ class PhysicsOptimizer:
         self.topo = MeshTopology(smpl_layer.th_faces, cm.V, self.device, rest_vertices=getattr(smpl_layer, 'v_template', None) if scan_order else None)
         geo = _lib.CorrectionCtx()
         geo.smpl = C.pointer(cm)
-        geo.faces, geo.adj_ptr = self.topo.faces.data_ptr(), self.topo.adj_ptr.data_ptr()
-        geo.adj_face, geo.adj_corner = self.topo.adj_face.data_ptr(), self.topo.adj_corner.data_ptr()
-        geo.adj_pair = self.topo.adj_pair.data_ptr()
-        if self.topo.vorder is not None:       # scan order of the exact nearest-vertex scan (block culling, csrc/correction.hip); results do not depend on it
+        self.topo.fill_ctx(geo, adj_pair=True)
+        if self.topo.vorder is not None:       # scan order of the exact nearest-vertex scan (block culling, csrc/contact_scan.h); results do not depend on it
             self._markers_scan = self.topo.scan_positions([0], self.device)
-            geo.vorder, geo.faces_scan, geo.adj_pair_scan = self.topo.vorder.data_ptr(), self.topo.faces_scan.data_ptr(), self.topo.adj_pair_scan.data_ptr()
             geo.markers_scan = self._markers_scan.data_ptr()
-            geo.vrank = self.topo.vrank.data_ptr()
         self.geo = geo
         # constants of the backward pass: the blend basis transposed (k-major rows, zero padded to the split-K slice) and
         # the skinning weights regrouped by joint

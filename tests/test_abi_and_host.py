@@ -729,11 +729,11 @@ def test_qkv_plane_bounds_hold_and_keep_the_split_in_range():
 
 
 def test_marker_contact_threshold_constant_is_the_exact_one():
-    """csrc/correction.hip tests d2 < MARK_D2 instead of sqrtf(d2) < 0.02f (eval_smpl_short.py:110-112) -- valid because a correctly rounded square root is monotone:
+    """csrc/contact_scan.h tests d2 < MARK_D2 instead of sqrtf(d2) < 0.02f (eval_smpl_short.py:110-112) -- valid because a correctly rounded square root is monotone:
     MARK_D2 must be THE smallest float whose root is >= 0.02f.  Re-derived here from the definition and compared with the literal in the source; a neighbourhood of
     floats around it is checked element by element."""
     import re
-    src = open(os.path.join(os.path.dirname(__file__), '..', 'interdiff_amd', 'csrc', 'correction.hip')).read()
+    src = open(os.path.join(os.path.dirname(__file__), '..', 'interdiff_amd', 'csrc', 'contact_scan.h')).read()
     lit = np.float32(float(re.search(r'constexpr float MARK_D2 = ([0-9.eE+-]+)f;', src).group(1)))
     t = np.float32(0.02)
     x = np.float32(t * t)

@@ -250,7 +250,7 @@ def _posed_body(smpl_layer, n_frames, seed):
 
 
 def test_contact_scan_block_culling_is_exact(smpl):
-    """The nearest-vertex scan of the hook (csrc/correction.hip corr_contact_kernel: Morton scan order, 16-vertex blocks culled by
+    """The nearest-vertex scan of the hook (csrc/contact_scan.h corr_contact_kernel: Morton scan order, 16-vertex blocks culled by
     their boxes per wave) against the brute-force oracle: indices bit-identical with and without the scan order, on a posed body,
     with the object near / inside / far from the body, duplicated vertices (ties inside a block, across blocks, a 100-vertex clump
     -> the all-records tie fallback), the winner in the last (partial: 6890 % 16 = 10) block; and the culling really happens."""
@@ -1131,7 +1131,7 @@ def test_optimize_loss_and_gradients_golden(phys):
 @pytest.mark.gpu
 def test_optimize_culled_scans_equal_brute_force(smpl):
     """The post-optimisation's two nearest-neighbour questions (optimization.py:64-65,74-75) through the culled kernels of
-    csrc/correction.hip -- nearest vertex per point by the hook's block-culled scan, "any point within 0.5 m" per vertex against the
+    csrc/contact_scan.h and csrc/near_mask.h -- nearest vertex per point by the hook's block-culled scan, "any point within 0.5 m" per vertex against the
     boxes of 64-point patches -- against the round-2 brute-force kernel (``scan_order=False``): indices and near flags bit for bit,
     on overlapping objects, an object 0.45 m away (the radius cuts through the body) and one 1.5 m away (nothing near)."""
     import ctypes as C
@@ -1509,7 +1509,7 @@ def test_correction_edge_sizes(smpl, T, B, P):
 @pytest.mark.gpu
 def test_hook_with_the_predictor_inside_the_scan_launch_equals_the_serial_one(smpl):
     """Round 6: the contact-frame predictor's three stacks ride in the contact scan's launch as leading workgroups (they need the markers only) and a small kernel picks the node
-    once the labels exist (csrc/correction.hip correction_impl, corr_contact_kernel<false, true>, csrc/objproj.h).  Same bits as the scan followed by the one-launch predictor
+    once the labels exist (csrc/correction.hip correction_impl, csrc/contact_scan.h corr_contact_kernel<false, true>, csrc/objproj.h).  Same bits as the scan followed by the one-launch predictor
     (ctx.tune = 2), outputs and decisions, called eagerly, on a non-default stream, and replayed from a captured graph; repeated calls do not disturb each other."""
     T, B, P = 14, 3, 300
     bt = fx._clip(4242, B, T, P)

@@ -1,4 +1,4 @@
-"""numpy model of three candidate changes to the contact scan (csrc/correction.hip corr_contact_kernel), round 6 -- not product code:
+"""numpy model of three candidate changes to the contact scan (csrc/contact_scan.h corr_contact_kernel), round 6 -- not product code:
 (a) 8-vertex blocks, (b) a flat box-vs-box prefilter (lanes = boxes, the task's bounding box against the largest seeded minimum of its 64 points) in front of the per-point tests,
 (c) re-running that prefilter every `refilter` survivors.  Prints tests / executed blocks per 64-point task; the instruction model next to it is in profiles/r06_contact_bound.txt.
     python tools/contact_prefilter_sim.py"""

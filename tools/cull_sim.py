@@ -1,6 +1,6 @@
 """numpy model of the contact scan's block culling (not product code): fraction of 16-vertex blocks a task of WAVE (64) Morton-sorted object
 points has to score, for block sizes 8 / 16 / 32, on the synthetic body (default or `coherent`) posed by ground-truth and by noisy poses.
-The block size, the seed and the two-level hierarchy of csrc/correction.hip were chosen with it.    python tools/cull_sim.py [coherent]"""
+The block size, the seed and the two-level hierarchy of csrc/contact_scan.h were chosen with it.    python tools/cull_sim.py [coherent]"""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from interdiff_amd import synthetic as syn
@@ -8,7 +8,7 @@ from oracle.smpl import smpl_forward
 from oracle import rotations as R
 torch.set_grad_enabled(False)
 
-WAVE = 64          # points per task (csrc/correction.hip TASK)
+WAVE = 64          # points per task (csrc/contact_scan.h TASK)
 
 def morton(p, bits=10):
     lo, hi = p.min(0), p.max(0)
