@@ -376,6 +376,55 @@ size_t interdiff_objprojector_forward_workspace_bytes(int32_t B);
 int interdiff_objprojector_forward(const idf_objproj *op, const float *obj_angles, const float *obj_trans, const float *markers,
                                    const int32_t *contact, int32_t B, int32_t initialize, float *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- FINE-TUNING of the correction predictor under the object-pose loss, with FROZEN normalisation statistics (the reference module in eval() with
+ * autograd on: BatchNorm uses its running statistics and never writes them, dropout is off, contact clips take the argmax node; `multinomial` selection,
+ * train-mode BatchNorm, dropout and the gradient of the contact / penetration terms are NOT built).  Device code: csrc/objproj_train.h, launchers
+ * csrc/objproj_train.hip; the layer backward and the fold / Adam / re-fold kernels are shared with the skeleton fine-tuner (csrc/stgcn_train.h).
+ * Additive entries: interdiff_abi_version() stays what it was.
+ *
+ * PARAMETER TABLE.  `params`, `grads`, `exp_avg`, `exp_avg_sq` are flat fp32 vectors of n_param = 224 174 floats in the order of
+ * ObjProjector.named_parameters(): the stacks st_gcnns_relative (67 nodes), st_gcnns (1 node), st_gcnns_all (68 nodes), four layers each, and per layer
+ *     [gcn.A [10][68][68]  (st_gcnns_all only)]
+ *     gcn.T [10][10]  (st_gcnns_all: [68][10][10])
+ *     tcn.0.weight [cout][cin], tcn.0.bias [cout], tcn.1.weight [cout], tcn.1.bias [cout],
+ *     residual.0.weight [cout][cin], residual.0.bias [cout], residual.1.weight [cout], residual.1.bias [cout], prelu.weight [1].
+ * `bn` is the flat vector of the BatchNorm buffers (n_bn floats, read only -- no entry writes it), per layer
+ *     tcn.1.running_mean, tcn.1.running_var, residual.1.running_mean, residual.1.running_var, [cout] each.
+ * interdiff_correction_finetune_param_table writes table[12][16] in the column layout of interdiff_skeleton_finetune_param_table (below); only op's
+ * cin / cout are read.  interdiff_amd/correction_finetune.py builds the same table from the state_dict and its constructor compares the two.
+ *
+ * interdiff_correction_finetune_grads   replaces loss.backward() on LitInteraction.calc_loss (train_correction_smpl.py:60-101) of ObjProjector.forward
+ *      (model/correction_smpl.py:69-138) -- what _common_step (:187-189) trains on while its annealed geometry weights are zero, epoch 0 at the defaults.
+ *      op->arena must be the fold of `params` / `bn` (interdiff_correction_finetune_step keeps it so).  obj_angles [T,B,6], obj_trans [T,B,3],
+ *      markers [T,B,67,3], contact int32 [B,67] are what interdiff_objprojector_forward takes (contact may be NULL when initialize != 0); they are the
+ *      target as well (obj_gt = obj_angles | obj_trans).  d_obj_pred [T,B,9] or NULL: added to the loss gradient at the prediction before the backward
+ *      starts -- the gradient of whatever else the caller's objective reads from obj_pred (the seam for the contact / penetration terms).
+ *      weights8: HOST pointer, the 8 loss weights in the order rot_past, nonrot_past, rot_future, nonrot_future, rot_v_past, nonrot_v_past, rot_v_future,
+ *      nonrot_v_future (rot = the six rotation channels).  -> out9 (device) = loss, the 8 unweighted terms (of the MSE terms alone, whatever d_obj_pred
+ *      is); grads (device) [n_param] in the reference layout.  One 1024-thread workgroup per clip (forward with saves, loss gradient, backward, per-clip
+ *      partials by plain stores), then the fold over clips in ascending order and the conversion from the folded convolutions: no atomics, two calls
+ *      give the same bits.  Clips whose contact rule selects a node leave EXACT zeros in the columns of st_gcnns_all.3.gcn.A of every other node.
+ *      IDF_E_INVAL: null pointer, B < 1, T != op->T, T > 64, past_len >= T, short workspace.
+ *      PRECISION: the three stacks run in fp32 on the VALU with compensated sums (not the MFMA forward of interdiff_objprojector_sample); everything
+ *      around them -- the DCT (its matrix is formed in the kernel in double; the arena's fp32 dct_pad / dct / idct are not read), the skip connections,
+ *      the node selection, the IDCT, the prediction error and the loss gradient -- runs in DOUBLE, a departure from fp32-throughout taken to keep every
+ *      gradient tensor within 4x the reference's own fp32 error of the fp64 gradient.  The loss therefore agrees with calc_loss on
+ *      interdiff_objprojector_forward's prediction to ~1e-6 relative, not in bits.
+ * interdiff_correction_finetune_step    replaces optimizer.step() of torch.optim.Adam(lr, betas, eps, weight_decay) (:51-58), torch's order of
+ *      operations, weight decay added to the gradient; `step` = 1 for the first step.  Updates params / exp_avg / exp_avg_sq in place and re-folds
+ *      params into `arena` (the float arena op->layer[] indexes: MFMA layout, gcn.A transposed and padded to 80 x 80; folded in double without
+ *      contraction, like the host packer).
+ * ---------------------------------------------------------------------------------- */
+int interdiff_correction_finetune_param_table(const idf_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn);
+size_t interdiff_correction_finetune_workspace_bytes(const idf_objproj *op, int32_t B);
+int interdiff_correction_finetune_grads(const idf_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                        const float *obj_trans, const float *markers, const int32_t *contact, const float *d_obj_pred,
+                                        int32_t B, int32_t T, int32_t initialize, const float *weights8, float *out9, float *grads, void *ws,
+                                        size_t ws_bytes, void *stream);
+int interdiff_correction_finetune_step(const idf_objproj *op, float *arena, float *params, const float *bn, const float *grads,
+                                       float *exp_avg, float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps,
+                                       double weight_decay, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * denoised_fn, fused   replaces eval_smpl_short.py:84-130 for one gated step.
  * x0 [B,1,144,T] is updated in place.  hand_pose [T,B,90] (already idx-padded),

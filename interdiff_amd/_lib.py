@@ -148,6 +148,11 @@ _SIGS = {
     'interdiff_objprojector_sample': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, vp, vp]),
     'interdiff_objprojector_forward_workspace_bytes': (sz, [i32]),
     'interdiff_objprojector_forward': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),
+    'interdiff_correction_finetune_param_table': (C.c_int, [C.POINTER(ObjProj), vp, C.POINTER(i32), C.POINTER(i32)]),
+    'interdiff_correction_finetune_workspace_bytes': (sz, [C.POINTER(ObjProj), i32]),
+    'interdiff_correction_finetune_grads': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, sz, vp]),
+    'interdiff_correction_finetune_step': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                     C.c_double, vp]),
     'interdiff_correction_workspace_bytes': (sz, [C.POINTER(CorrectionCtx), i32, i32]),
     'interdiff_correction': (C.c_int, [C.POINTER(CorrectionCtx), vp, vp, vp, vp, vp, i32, i32, f32,
                                        vp, vp, vp, vp, vp, sz, vp]),

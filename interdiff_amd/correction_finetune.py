@@ -1,0 +1,142 @@
+"""Fine-tuning of the SMPL contact-frame correction predictor (``checkpoints/correction.ckpt``) on the HIP path under the object-pose loss,
+with FROZEN normalisation statistics: the reference module in ``eval()`` with autograd on.  BatchNorm uses its running statistics and
+never updates them, dropout is off, contact clips take the ``argmax`` node, and every one of the 224,174 parameters is trained --
+convolutions, BatchNorm affine weights, the temporal and adjacency matrices, the PReLU slopes.
+
+    loss, grads     LitInteraction.calc_loss + loss.backward() on ObjProjector.forward   train_correction_smpl.py:60-101, model/correction_smpl.py:69-138
+    training_step   + torch.optim.Adam(lr, weight_decay=l2_norm).step()                  :51-58, :263-270
+
+That is the reference's own regime where its schedule starts: ``_common_step`` anneals the contact and penetration terms by
+``min(1, epoch / second_stage) ** 2``, exactly 0 at epoch 0, so there it trains on the eight MSE terms alone.  From epoch 1 on those two
+terms add a gradient that reaches the network only through ``obj_pred`` [T,B,9]: ``d_obj_pred`` is the seam through which a caller hands
+it in.  NOT built: the contact / penetration gradient itself, ``multinomial`` node selection, train-mode BatchNorm and dropout,
+learning-rate schedules, the Lightning glue and the dataset.
+
+All arithmetic runs in libinterdiff_hip.so (csrc/objproj_train.h / .hip, csrc/stgcn_train.h): one workgroup per clip for forward, loss
+gradient and backward, a fixed-order fold over clips, Adam on fp32 master parameters in the reference layout, and the re-fold into the
+arena that ``ObjProjector``, the correction hook and ``correction_losses.validation_step`` read.  The flat parameter layout
+(``param_table``) is documented in include/interdiff_hip.h.
+"""
+import ctypes as C
+import numpy as np
+import torch
+from . import _lib
+from .objprojector import ObjProjector
+from .skeleton import _check, _strip
+from .skeleton_finetune import FlatParameters, LAYER_PARAMS, LAYER_BUFFERS, TABLE_COLS, param_table, buffer_table
+from .stgcn_pack import STACKS
+from .correction_losses import CorrectionLossWeights, MSE_KEYS
+
+N_MARKERS = 67
+
+
+def rotation_6d_of_axis_angle(aa):
+    """``matrix_to_rotation_6d(axis_angle_to_matrix(aa))`` (ObjProjector.forward, model/correction_smpl.py:71; pytorch3d 0.7.2: through the
+    quaternion) evaluated in float64 and rounded once: the loss gradient is proportional to prediction - target, and the target is this."""
+    a = aa.double()
+    angle = a.norm(dim=-1, keepdim=True)
+    small = angle.abs() < 1e-6
+    safe = torch.where(small, torch.ones_like(angle), angle)
+    sinc_half = torch.where(small, 0.5 - angle * angle / 48.0, torch.sin(safe * 0.5) / safe)
+    r, (i, j, k) = torch.cos(angle * 0.5)[..., 0], (a * sinc_half).unbind(-1)
+    two_s = 2.0 / (r * r + i * i + j * j + k * k)
+    return torch.stack([1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
+                        two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r)], dim=-1).float().contiguous()
+
+
+class CorrectionFineTuner(FlatParameters):
+    """Adapts a contact-frame predictor to a user's own clips.  ``batch`` is what ``ObjProjector.forward`` takes: the reference's
+    dict-of-lists (``frames[t]['objfit_params']['angle' | 'trans']`` [B,3], ``frames[t]['markers']`` [B,67,7]) or the stacked tensors
+    ``dict(obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7])``."""
+
+    def __init__(self, state_dict, T=35, past_len=10, lr=3e-4, weight_decay=0., betas=(0.9, 0.999), eps=1e-8, weights=CorrectionLossWeights(), device='cuda'):
+        sd = _strip(state_dict)
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.weights = weights
+        self.predictor = ObjProjector(sd, T, past_len, device=device)          # its arena is the live one
+        self.past_len, self.T = past_len, T
+        self.table, self.btable = param_table(sd), buffer_table(sd)
+        self.n_param = self.table[-1][1] + int(np.prod(self.table[-1][2]))
+        self._check_table()
+        self._init_state(sd)
+        self._w8 = (C.c_float * 8)(*self.weights.vector(0)[2:])
+        self._ws = {}
+
+    def _check_table(self):
+        """The C side derives the same table from the channel widths (csrc/objproj_train.h ot_plan): they must agree."""
+        cop = self.predictor.cop
+        tab = (C.c_int32 * (12 * TABLE_COLS))()
+        n_param, n_bn = C.c_int32(), C.c_int32()
+        _check(self.lib.interdiff_correction_finetune_param_table(C.byref(cop), tab, C.byref(n_param), C.byref(n_bn)), 'correction_finetune_param_table')
+        offs = {n: o for n, o, _ in self.table}
+        boffs = {n: o for n, o, _ in self.btable}
+        for li in range(12):
+            p = '%s.%d.' % (STACKS[li // 4], li % 4)
+            row = list(tab[li * TABLE_COLS:(li + 1) * TABLE_COLS])
+            want = [offs.get(p + s, -1) for s in LAYER_PARAMS] + [cop.cin[li], cop.cout[li], (N_MARKERS, 1, N_MARKERS + 1)[li // 4], int(li // 4 == 2),
+                                                                 boffs[p + LAYER_BUFFERS[0]]]
+            if row != want:
+                raise RuntimeError('parameter table of layer %d: library %r, state_dict %r' % (li, row, want))
+        nb = self.btable[-1][1] + int(np.prod(self.btable[-1][2]))
+        if n_param.value != self.n_param or n_bn.value != nb:
+            raise RuntimeError('parameter count: library %d / %d, state_dict %d / %d' % (n_param.value, n_bn.value, self.n_param, nb))
+
+    def _workspace(self, B):
+        if B not in self._ws:
+            n = self.lib.interdiff_correction_finetune_workspace_bytes(C.byref(self.predictor.cop), B)
+            self._ws = {B: torch.empty(n, dtype=torch.uint8, device=self.device)}
+        return self._ws[B]
+
+    # ---- the step
+    def _grads(self, batch, initialize=False, d_obj_pred=None):
+        dev = self.device
+        aa, ot, mk = self.predictor.batch_tensors(batch)
+        T, B = aa.shape[:2]
+        if T != self.T or tuple(aa.shape) != (T, B, 3) or tuple(ot.shape) != (T, B, 3) or tuple(mk.shape[:3]) != (T, B, N_MARKERS):
+            raise ValueError('expected obj_angle, obj_trans [%d,B,3] and markers [%d,B,%d,7]' % (self.T, self.T, N_MARKERS))
+        d6, ot = rotation_6d_of_axis_angle(aa), ot.contiguous()
+        pos = mk[..., :3].contiguous()
+        contact = mk[self.past_len:, :, :, 6].sum(dim=0).to(torch.int32).contiguous()
+        extra = None
+        if d_obj_pred is not None:
+            extra = d_obj_pred.to(dev, torch.float32).contiguous()
+            if tuple(extra.shape) != (T, B, 9):
+                raise ValueError('d_obj_pred must be [%d,%d,9]' % (T, B))
+        out9 = torch.empty(9, dtype=torch.float32, device=dev)
+        grads = torch.empty(self.n_param, dtype=torch.float32, device=dev)
+        ws = self._workspace(B)
+        _check(self.lib.interdiff_correction_finetune_grads(C.byref(self.predictor.cop), _lib.dptr(self.params), _lib.dptr(self.bn), _lib.dptr(d6), _lib.dptr(ot),
+                                                            _lib.dptr(pos), _lib.dptr(contact, torch.int32), _lib.dptr(extra, allow_none=True), B, T,
+                                                            int(bool(initialize)), self._w8, _lib.dptr(out9), _lib.dptr(grads), _lib.dptr(ws), ws.numel(),
+                                                            _lib.stream()), 'correction_finetune_grads')
+        return out9, grads
+
+    def loss_and_grads(self, batch, initialize=False, d_obj_pred=None):
+        """-> (loss, loss_dict, weighted_loss_dict, grads): 0-dim device tensors under the reference's 8 MSE keys, ``grads`` = {reference
+        parameter name: d (loss + <d_obj_pred, obj_pred>) / d parameter} (views of one flat device tensor).  ``d_obj_pred`` [T,B,9]: the gradient
+        at the prediction of any further term of the caller's objective; the returned loss stays that of the 8 terms."""
+        out9, grads = self._grads(batch, initialize, d_obj_pred)
+        w = torch.tensor(self.weights.vector(0)[2:], dtype=torch.float32, device=self.device) * out9[1:]
+        return out9[0], {k: out9[1 + n] for n, k in enumerate(MSE_KEYS)}, {k: w[n] for n, k in enumerate(MSE_KEYS)}, self.unflatten(grads)
+
+    def apply_gradients(self, grads):
+        """One Adam step on ``grads`` (flat [n_param] or a dict under reference names) and the re-fold of the arena."""
+        g = self._flat(grads)
+        self.step += 1
+        _check(self.lib.interdiff_correction_finetune_step(C.byref(self.predictor.cop), _lib.dptr(self.predictor.arena), _lib.dptr(self.params), _lib.dptr(self.bn),
+                                                           _lib.dptr(g), _lib.dptr(self.exp_avg), _lib.dptr(self.exp_avg_sq), self.step, self.lr, self.betas[0],
+                                                           self.betas[1], self.eps, self.weight_decay, _lib.stream()), 'correction_finetune_step')
+
+    def training_step(self, batch, current_epoch=0, d_obj_pred=None):
+        """Gradients (``initialize = current_epoch < 10``, like ``_common_step``), Adam, re-fold.  -> the loss of the 8 MSE terms BEFORE the step
+        (0-dim device tensor).  At an epoch whose annealed contact / penetration weights are not zero the reference trains on those terms too:
+        their gradient at the prediction must then come in as ``d_obj_pred`` -- without it this raises instead of training on another loss."""
+        geometry = self.weights.vector(current_epoch)[:2]
+        if any(w != 0 for w in geometry) and d_obj_pred is None:
+            raise ValueError('epoch %d weighs the penetration / contact terms by %r: pass their gradient at obj_pred as d_obj_pred [T,B,9] '
+                             '(their backward is not built here)' % (current_epoch, geometry))
+        out9, grads = self._grads(batch, current_epoch < 10, d_obj_pred)
+        self.apply_gradients(grads)
+        return out9[0]

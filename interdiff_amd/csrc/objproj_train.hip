@@ -1,0 +1,126 @@
+// Fine-tuning of the SMPL contact-frame correction predictor with frozen normalisation statistics: launchers of the clip kernel (csrc/objproj_train.h) and
+// of the kernels around it (csrc/stgcn_train.h) -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions'
+// gradients to the reference parameters, Adam on the fp32 master parameters, and the re-fold into the arena that interdiff_objprojector_sample / _forward
+// and the correction hook read.
+#include <math.h>
+#include "objproj_train.h"
+
+namespace {
+using namespace idf_objproj_train;
+using namespace idf_stgcn_train;
+
+__global__ __launch_bounds__(NTHR) void objproj_ft_clip_kernel(const idf_objproj op, const FtPlan plan, const OtArgs a, int B) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    ot_clip_body(sm, op, plan, a, B, blockIdx.x);
+}
+
+// the channel widths the kernels were built for (all the parameter table needs)
+int ot_check_widths(const idf_objproj *op) {
+    if (idf_objproj_check(op) != IDF_OK) return IDF_E_INVAL;
+    for (int st = 0; st < 3; ++st) {
+        if (op->cin[st * 4] != CH || op->cout[st * 4 + 3] != CH) return IDF_E_INVAL;
+        for (int l = 0; l < 4; ++l) {
+            const int li = st * 4 + l;
+            if (op->cin[li] < 1 || op->cin[li] > MAXC || op->cout[li] < 1 || op->cout[li] > MAXC) return IDF_E_INVAL;
+            if (l < 3 && op->cout[li] != op->cin[li + 1]) return IDF_E_INVAL;
+        }
+    }
+    return IDF_OK;
+}
+
+int ot_check(const idf_objproj *op, int B) {
+    if (ot_check_widths(op) != IDF_OK || !op->arena || B < 1 || op->T < 2 || op->T > MAXT || op->past_len >= op->T) return IDF_E_INVAL;
+    for (int li = 0; li < 12; ++li)
+        if (op->layer[li] < 0) return IDF_E_INVAL;
+    return IDF_OK;
+}
+
+// workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]
+struct OtWs {
+    size_t partials, loss_part, gsum, clips, total;
+};
+OtWs ot_ws(const FtPlan &P, int B) {
+    OtWs w{};
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
+    w.partials = take((size_t)B * P.n_param);
+    w.loss_part = take((size_t)B * 8);
+    w.gsum = take((size_t)P.n_param);
+    w.clips = take((size_t)B * P.ws_clip);
+    w.total = o;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int interdiff_correction_finetune_param_table(const idf_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn) {
+    if (!table || !n_param || !n_bn || ot_check_widths(op) != IDF_OK) return IDF_E_INVAL;
+    const FtPlan P = ot_plan(op->cin, op->cout);
+    for (int li = 0; li < 12; ++li) {
+        const int32_t *src = reinterpret_cast<const int32_t *>(&P.L[li]);
+        for (int k = 0; k < FT_TABLE_COLS; ++k) table[li * FT_TABLE_COLS + k] = src[k];
+    }
+    *n_param = P.n_param;
+    *n_bn = P.n_bn;
+    return IDF_OK;
+}
+
+extern "C" size_t interdiff_correction_finetune_workspace_bytes(const idf_objproj *op, int32_t B) {
+    if (B < 1 || ot_check_widths(op) != IDF_OK) return 0;
+    return ot_ws(ot_plan(op->cin, op->cout), B).total * sizeof(float);
+}
+
+extern "C" int interdiff_correction_finetune_grads(const idf_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                                   const float *obj_trans, const float *markers, const int32_t *contact, const float *d_obj_pred,
+                                                   int32_t B, int32_t T, int32_t initialize, const float *weights8, float *out9, float *grads, void *ws,
+                                                   size_t ws_bytes, void *stream) {
+    if (!params || !bn || !obj_angles || !obj_trans || !markers || !weights8 || !out9 || !grads || !ws) return IDF_E_INVAL;
+    if (!initialize && !contact) return IDF_E_INVAL;
+    if (ot_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
+    const FtPlan P = ot_plan(op->cin, op->cout);
+    const OtWs W = ot_ws(P, B);
+    if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
+    float *base = static_cast<float *>(ws);
+    hipStream_t st = idf_stream(stream);
+    const int past = op->past_len, fut = T - past;
+    LossK lk;
+    OtArgs a{};
+    for (int k = 0; k < 8; ++k) {
+        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 6;
+        const double n = frames * (double)B * width;
+        lk.w[k] = weights8[k];
+        lk.inv_n[k] = (float)(1.0 / n);
+        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
+    }
+    a.obj_angles = obj_angles; a.obj_trans = obj_trans; a.markers = markers; a.contact = contact; a.d_obj_pred = d_obj_pred;
+    a.partials = base + W.partials;
+    a.loss_part = base + W.loss_part;
+    a.ws_clips = base + W.clips;
+    a.initialize = initialize != 0;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (idf_opt_in_lds(reinterpret_cast<const void *>(objproj_ft_clip_kernel), (int)OT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(objproj_ft_clip_kernel, dim3(B), dim3(NTHR), OT_LDS, st, *op, P, a, B);
+    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+                       lk, base + W.gsum, out9);
+    hipLaunchKernelGGL(stgcn_ft_convert_kernel<NP>, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+extern "C" int interdiff_correction_finetune_step(const idf_objproj *op, float *arena, float *params, const float *bn, const float *grads, float *exp_avg,
+                                                  float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                                  void *stream) {
+    if (!arena || !params || !bn || !grads || !exp_avg || !exp_avg_sq || step < 1 || ot_check(op, 1) != IDF_OK) return IDF_E_INVAL;
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return IDF_E_INVAL;
+    const FtPlan P = ot_plan(op->cin, op->cout);
+    hipStream_t st = idf_stream(stream);
+    const AdamK k = ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay);
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(stgcn_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
+    hipLaunchKernelGGL((stgcn_ft_refold_kernel<NP, VP, idf_objproj>), dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}

@@ -31,7 +31,7 @@
 // Dropout keep masks: one byte per element, the 12 layers in named_parameters() order, each [B][cout][20][nodes]; keep iff the byte is nonzero.  The generator
 // (skel_tr_masks_kernel) writes that buffer: Philox4x32-10 keyed by the seed, counter = (element index / 4, layer, step); an element keeps iff its uniform
 // draw in [0, 1) is >= p.  The phases only ever read bytes, so the injected and the generated route are the same code.
-// Parameter gradients: partials[b][.] by plain stores in the flat reference layout, folded over the clips in ascending order (skel_ft_fold_kernel): no atomics;
+// Parameter gradients: partials[b][.] by plain stores in the flat reference layout, folded over the clips in ascending order (stgcn_ft_fold_kernel, csrc/stgcn_train.h): no atomics;
 // two calls give the same bits at any B.
 #pragma once
 #include "skeleton_train.h"

@@ -1,8 +1,9 @@
 // Fine-tuning of the HO-GCN skeleton correction predictor with FROZEN normalisation statistics (the module in eval() with autograd on):
 // the loss of LitObjInteraction._common_step (train_correction_skeleton.py:128-154) on ObjProjector.forward (model/correction_skeleton.py:68-137),
-// d loss / d theta for every entry of named_parameters(), and torch.optim.Adam (train_correction_skeleton.py:41-47).  Device code; launchers and the
-// fold / Adam / re-fold kernels: csrc/skeleton_train.hip.  Train-mode BatchNorm (batch statistics) and dropout: csrc/skeleton_bn_train.h, built from the pieces
-// of this file.
+// d loss / d theta for every entry of named_parameters(), and torch.optim.Adam (train_correction_skeleton.py:41-47).  Device code; launchers:
+// csrc/skeleton_train.hip.  The ST-GCN layer's forward with saves and its backward, the compensated sum, the flat parameter plan and the fold / Adam / re-fold
+// kernels are shared with the SMPL predictor's trainer: csrc/stgcn_train.h.  Train-mode BatchNorm (batch statistics) and dropout: csrc/skeleton_bn_train.h,
+// built from the pieces of this file.
 //
 // ONE 16-wave workgroup per clip, like skel_body (csrc/skeleton.h), in three parts:
 //   1. FORWARD on the folded layers of the arena the inference kernels read: st_gcn_layer's arithmetic with every sum compensated (Acc2) on the VALU.  Each
@@ -17,60 +18,23 @@
 // LDS: the gradient planes live in the layer buffer [64][440] (in place: dy -> dh -> du -> dx); in the 64 <-> 32 layers input planes + gradient planes would
 // be 168 960 B > 160 KiB, so the other operand of every product (x, u, g, h and two scratch plane sets G = W^T dh, X = Wr^T dh) comes from the clip's
 // workspace slice, which only this workgroup touches (__syncthreads orders its global accesses at workgroup scope).
-// Parameter gradients: partials[b][.] in the FLAT REFERENCE LAYOUT (FtPlan below), gradients of the FOLDED convolutions in the conv slots, plain stores,
+// Parameter gradients: partials[b][.] in the FLAT REFERENCE LAYOUT (FtPlan, csrc/stgcn_train.h), gradients of the FOLDED convolutions in the conv slots, plain stores,
 // every element written by exactly one thread in a fixed summation order -- no atomics; two calls give the same bits.
 #pragma once
 #include "skeleton.h"
+#include "stgcn_train.h"
 
 namespace idf_skel_train {
 
 using namespace idf_skel_dev;
+using idf_stgcn_train::Acc2;
+using idf_stgcn_train::FtLayer;
+using idf_stgcn_train::FtPlan;
+using idf_stgcn_train::FT_TABLE_COLS;
 
-// Offsets (floats) of a layer's tensors in the flat parameter / gradient vector = named_parameters() order of ObjProjector:
-//   [gcn.A [NP][nodes][nodes] (joint stack only)] gcn.T [NP][NP] or [nodes][NP][NP], tcn.0.weight [cout][cin], tcn.0.bias, tcn.1.weight, tcn.1.bias,
-//   residual.0.weight [cout][cin], residual.0.bias, residual.1.weight, residual.1.bias, prelu.weight [1]
-// bn: offset in the flat BatchNorm-buffer vector: tcn.1.running_mean, tcn.1.running_var, residual.1.running_mean, residual.1.running_var, cout each.
-// ws_*: offsets of the saved planes in a clip's workspace slice.
-struct FtLayer {
-    int32_t A, T, Wt, bt, gt, bet, Wr, br, gr, ber, pr;
-    int32_t cin, cout, nodes, v2, bn;
-    int32_t ws_x, ws_u, ws_g, ws_h;
-};
-struct FtPlan {
-    FtLayer L[12];
-    int32_t n_param, n_bn, ws_clip;          // ws_clip: saved planes + the scratch plane sets G, X (BUF floats each) at its end
-};
-constexpr int FT_TABLE_COLS = 16;            // interdiff_skeleton_finetune_param_table: the first 16 ints of an FtLayer
-
-inline FtPlan ft_plan(const int32_t *cin, const int32_t *cout) {
-    FtPlan P{};
-    int o = 0, bn = 0, ws = 0;
-    for (int li = 0; li < 12; ++li) {
-        FtLayer &L = P.L[li];
-        const int st = li / 4, nodes = st == 0 ? J : st == 1 ? 1 : NJ, ci = cin[li], co = cout[li], npos = NP * nodes;
-        L.cin = ci; L.cout = co; L.nodes = nodes; L.v2 = st == 2;
-        L.A = -1;
-        if (L.v2) { L.A = o; o += NP * nodes * nodes; }
-        L.T = o; o += (L.v2 ? nodes : 1) * NP * NP;
-        L.Wt = o; o += co * ci;
-        L.bt = o; o += co;
-        L.gt = o; o += co;
-        L.bet = o; o += co;
-        L.Wr = o; o += co * ci;
-        L.br = o; o += co;
-        L.gr = o; o += co;
-        L.ber = o; o += co;
-        L.pr = o; o += 1;
-        L.bn = bn; bn += 4 * co;
-        L.ws_x = ws; ws += ci * npos;
-        L.ws_u = -1;
-        if (L.v2) { L.ws_u = ws; ws += ci * npos; }
-        L.ws_g = ws; ws += ci * npos;
-        L.ws_h = ws; ws += co * npos;
-    }
-    P.n_param = o; P.n_bn = bn; P.ws_clip = ws + 2 * BUF;
-    return P;
-}
+// the flat parameter plan (csrc/stgcn_train.h) of this predictor: 21 / 1 / 22 nodes over NP = 20 coefficients; ws_clip ends with the scratch plane sets G, X
+// (BUF floats each)
+inline FtPlan ft_plan(const int32_t *cin, const int32_t *cout) { return idf_stgcn_train::ft_plan_for(cin, cout, NP, J, BUF); }
 
 constexpr int FT_SMALL = 1536, FT_RED = NTHR;
 constexpr size_t FT_LDS = (size_t)(BUF + KEEP + FT_SMALL + FT_RED) * sizeof(float);
@@ -83,85 +47,22 @@ struct FtArgs {
     float coef[8];             // 2 w_k / n_k, MSE_KEYS order: rot_past, nonrot_past, rot_future, nonrot_future, then the four velocity terms
 };
 
-// Compensated fp32 accumulation (Ogita-Rump-Oishi Dot2: TwoProduct by fma, TwoSum, the errors summed aside): every sum of the backward runs through it, so
-// a gradient carries the rounding of its operands and of one final addition, not of the summation order -- the reference's BLAS sums blockwise, a plain
-// sequential fp32 chain over 440 positions would be the larger error.  fp32 arithmetic only; contraction off so that p is the rounded product TwoSum assumes.
-struct Acc2 {
-    float s = 0.f, c = 0.f;
-    __device__ __forceinline__ void mac(float a, float b) {
-#pragma clang fp contract(off)
-        const float p = a * b, ep = fmaf(a, b, -p);
-        const float t = s + p, bb = t - s;
-        const float es = (s - (t - bb)) + (p - bb);
-        s = t;
-        c += ep + es;
-    }
-    __device__ __forceinline__ void add(float p) {
-#pragma clang fp contract(off)
-        const float t = s + p, bb = t - s;
-        const float es = (s - (t - bb)) + (p - bb);
-        s = t;
-        c += es;
-    }
-    __device__ __forceinline__ float value() const { return s + c; }
-};
-
-// ---- forward of one layer on buf (cin planes in, cout planes out), saving x, u, g, h.  The arithmetic of st_gcn_layer (csrc/skeleton.h) on the same folded
-// arena, but every sum compensated (Acc2) on the VALU instead of K-blocked on the MFMA: a saved plane is the correctly rounded fp32 value of its exact
-// sum, which is what keeps the gradient inside 4 e_ref of the fp64 one.  Every step reads planes the PREVIOUS step saved to the workspace
-// and writes buf, so nothing is updated in place.
-// ft_fwd_graph: the input planes to sx, the temporal mix and (joint stack) the adjacency product to su / sg -- everything of a layer before its two 1x1
-// convolutions; the train-mode layer (csrc/skeleton_bn_train.h) shares it.
+// ---- the ST-GCN layer's forward with saves and its backward (csrc/stgcn_train.h) at this predictor's geometry
+using Ft = idf_stgcn_train::StgcnFt<NP, VP>;
 template <bool V2>
 __device__ inline void ft_fwd_graph(const float *buf, const LayerP &p, int cin, int nodes, float *sx, float *su, float *sg) {
-    const int tid = threadIdx.x, npos = NP * nodes;
-    for (int i = tid; i < cin * npos; i += NTHR) sx[i] = buf[i];
-    __syncthreads();
-    // temporal mix: u[c][q][v] = sum_t x[c][t][v] Tm[(v)][t][q]
-    float *su_or_sg = V2 ? su : sg;
-    for (int i = tid; i < cin * npos; i += NTHR) {
-        const int c = i / npos, r = i - c * npos, q = r / nodes, v = r - q * nodes;
-        const float *xc = sx + c * npos + v, *tmv = p.Tm + (V2 ? v * NP * NP : 0) + q;
-        Acc2 a;
-#pragma unroll 4
-        for (int t = 0; t < NP; ++t) a.mac(xc[t * nodes], tmv[t * NP]);
-        su_or_sg[i] = a.value();
-    }
-    __syncthreads();
-    // adjacency product: g[c][t][w] = sum_v u[c][t][v] A[t][v][w]  (AT[t][w][v])
-    if (V2) {
-        for (int i = tid; i < cin * npos; i += NTHR) {
-            const int c = i / npos, r = i - c * npos, t = r / nodes, w = r - t * nodes;
-            const float *u = su + (c * NP + t) * nodes, *At = p.AT + ((size_t)t * VP + w) * VP;
-            Acc2 a;
-            for (int v = 0; v < nodes; ++v) a.mac(u[v], At[v]);
-            sg[i] = a.value();
-        }
-        __syncthreads();
-    }
+    Ft::ft_fwd_graph<V2>(buf, p, cin, nodes, sx, su, sg);
 }
-
 template <bool V2>
 __device__ inline void ft_layer_fwd(float *buf, const LayerP &p, int cin, int cout, int nodes, float *sx, float *su, float *sg, float *sh) {
-    const int tid = threadIdx.x, npos = NP * nodes, cinp = pad16(cin);
-    ft_fwd_graph<V2>(buf, p, cin, nodes, sx, su, sg);
-    // h = Wt' g + bt' + Wr' x + br' in one compensated sum; PReLU
-    const float slope = p.prelu;
-    for (int i = tid; i < cout * npos; i += NTHR) {
-        const int o = i / npos, pos = i - o * npos;
-        const float *wt = p.Wt + o * cinp, *wr = p.Wr + o * cinp;
-        Acc2 a;
-        a.add(p.bt[o]);
-        a.add(p.br[o]);
-        for (int c = 0; c < cin; ++c) {
-            a.mac(wt[c], sg[c * npos + pos]);
-            a.mac(wr[c], sx[c * npos + pos]);
-        }
-        const float h = a.value();
-        sh[i] = h;
-        buf[i] = h >= 0.f ? h : slope * h;
-    }
-    __syncthreads();
+    Ft::ft_layer_fwd<V2>(buf, p, cin, cout, nodes, sx, su, sg, sh);
+}
+__device__ inline void ft_bwd_prelu(float *dy, float *red, float slope, const float *sh, const FtLayer &L, float *part) { Ft::ft_bwd_prelu(dy, red, slope, sh, L, part); }
+__device__ inline void ft_bwd_graph(float *dy, const LayerP &p, const FtLayer &L, const float *ws, const float *G, const float *X, float *part) {
+    Ft::ft_bwd_graph(dy, p, L, ws, G, X, part);
+}
+__device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, const FtLayer &L, const float *ws, float *G, float *X, float *part) {
+    Ft::ft_layer_bwd(dy, red, p, L, ws, G, X, part);
 }
 
 __device__ inline void ft_stack_fwd(float *buf, const idf_skel_objproj &op, const FtPlan &plan, int stack, int nodes, float *ws) {
@@ -173,143 +74,6 @@ __device__ inline void ft_stack_fwd(float *buf, const idf_skel_objproj &op, cons
         if (stack == 2) ft_layer_fwd<true>(buf, p, L.cin, L.cout, nodes, ws + L.ws_x, ws + L.ws_u, ws + L.ws_g, ws + L.ws_h);
         else ft_layer_fwd<false>(buf, p, L.cin, L.cout, nodes, ws + L.ws_x, nullptr, ws + L.ws_g, ws + L.ws_h);
     }
-}
-
-// ---- backward of one layer, in three pieces (the train-mode layer, csrc/skeleton_bn_train.h, shares the first and the last)
-// PReLU: dh = dy * (h > 0 ? 1 : slope) in place; d slope = sum over h <= 0 of dy * h (a strided walk per thread, then a tree: fixed order)
-__device__ inline void ft_bwd_prelu(float *dy, float *red, float slope, const float *sh, const FtLayer &L, float *part) {
-    const int tid = threadIdx.x, n = L.cout * NP * L.nodes;
-    {
-        Acc2 acc;
-        for (int i = tid; i < n; i += NTHR) {
-            const float h = sh[i], d = dy[i];
-            if (h > 0.f) {
-                dy[i] = d;
-            } else {
-                acc.mac(d, h);
-                dy[i] = slope * d;
-            }
-        }
-        red[tid] = acc.value();
-        __syncthreads();
-        for (int s = NTHR / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        if (tid == 0) part[L.pr] = red[0];
-    }
-}
-
-// the graph part: G = the gradient of the mixed planes g, X = the residual branch's share of dx (both [cin][npos], read only from here on); dy: scratch in
-// (its planes are dead), dx out.  dA and dT to part[].
-__device__ inline void ft_bwd_graph(float *dy, const LayerP &p, const FtLayer &L, const float *ws, const float *G, const float *X, float *part) {
-    const int tid = threadIdx.x, cin = L.cin, nodes = L.nodes, npos = NP * nodes;
-    const float *sx = ws + L.ws_x;
-    // 4. adjacency product: dA[t][v][w] = sum_c u[c][t][v] G[c][t][w]; du[c][t][v] = sum_w G[c][t][w] A[t][v][w] -> dy (dh is dead)
-    if (L.v2) {
-        const float *su = ws + L.ws_u;
-        for (int idx = tid; idx < NP * nodes * nodes; idx += NTHR) {
-            const int t = idx / (nodes * nodes), r = idx - t * nodes * nodes, v = r / nodes, w = r - v * nodes;
-            Acc2 a;
-            for (int c = 0; c < cin; ++c) a.mac(su[(c * NP + t) * nodes + v], G[(c * NP + t) * nodes + w]);
-            part[L.A + idx] = a.value();
-        }
-        for (int i = tid; i < cin * npos; i += NTHR) {
-            const int c = i / npos, r = i - c * npos, t = r / nodes, v = r - t * nodes;
-            const float *g = G + (c * NP + t) * nodes, *At = p.AT + (size_t)t * VP * VP + v;       // AT[t][w][v]
-            Acc2 a;
-            for (int w = 0; w < nodes; ++w) a.mac(g[w], At[w * VP]);
-            dy[i] = a.value();
-        }
-    } else {
-        for (int i = tid; i < cin * npos; i += NTHR) dy[i] = G[i];
-    }
-    __syncthreads();
-    // 5. temporal mix: dT[(v)][t][q] = sum_c (sum_v) x[c][t][v] du[c][q][v]
-    if (L.v2) {
-        for (int idx = tid; idx < nodes * NP * NP; idx += NTHR) {
-            const int v = idx / (NP * NP), r = idx - v * NP * NP, t = r / NP, q = r - t * NP;
-            Acc2 a;
-            for (int c = 0; c < cin; ++c) a.mac(sx[(c * NP + t) * nodes + v], dy[(c * NP + q) * nodes + v]);
-            part[L.T + idx] = a.value();
-        }
-    } else {
-        for (int idx = tid; idx < NP * NP; idx += NTHR) {
-            const int t = idx / NP, q = idx - t * NP;
-            Acc2 a;
-            for (int c = 0; c < cin; ++c) {
-                const float *xp = sx + (c * NP + t) * nodes, *dp = dy + (c * NP + q) * nodes;
-                for (int v = 0; v < nodes; ++v) a.mac(xp[v], dp[v]);
-            }
-            part[L.T + idx] = a.value();
-        }
-    }
-    __syncthreads();
-    // 6. dx[c][t][v] = X[c][t][v] + sum_q du[c][q][v] Tm[(v)][t][q], in place (a thread owns its column)
-    for (int i = tid; i < cin * nodes; i += NTHR) {
-        const int c = i / nodes, v = i - c * nodes;
-        float *col = dy + c * npos + v;
-        const float *xc = X + c * npos + v, *tmv = p.Tm + (L.v2 ? v * NP * NP : 0);
-        float du[NP];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) du[q] = col[q * nodes];
-#pragma unroll 2
-        for (int t = 0; t < NP; ++t) {
-            Acc2 a;
-            a.add(xc[t * nodes]);
-#pragma unroll
-            for (int q = 0; q < NP; ++q) a.mac(du[q], tmv[t * NP + q]);
-            col[t * nodes] = a.value();
-        }
-    }
-    __syncthreads();
-}
-
-// backward of one layer: dy = cout gradient planes in, cin gradient planes out (in place); parameter gradients to part[]
-__device__ inline void ft_layer_bwd(float *dy, float *red, const LayerP &p, const FtLayer &L, const float *ws, float *G, float *X, float *part) {
-    const int tid = threadIdx.x, cin = L.cin, cout = L.cout, nodes = L.nodes, npos = NP * nodes, cinp = pad16(cin);
-    const float *sx = ws + L.ws_x, *sg = ws + L.ws_g;
-    // 1. PReLU
-    ft_bwd_prelu(dy, red, p.prelu, ws + L.ws_h, L, part);
-    // 2. folded convolution weights and biases: dWt'[o][c] = sum_pos dh[o][pos] g[c][pos], dWr'[o][c] = sum_pos dh[o][pos] x[c][pos], db' = sum_pos dh[o][pos]
-    for (int idx = tid; idx < cout * cin + cout; idx += NTHR) {
-        if (idx < cout * cin) {
-            const int o = idx / cin, c = idx - o * cin;
-            const float *d = dy + o * npos, *gp = sg + c * npos, *xp = sx + c * npos;
-            Acc2 a, b;
-            for (int pos = 0; pos < npos; ++pos) {
-                const float dv = d[pos];
-                a.mac(dv, gp[pos]);
-                b.mac(dv, xp[pos]);
-            }
-            part[L.Wt + idx] = a.value();
-            part[L.Wr + idx] = b.value();
-        } else {
-            const int o = idx - cout * cin;
-            const float *d = dy + o * npos;
-            Acc2 a;
-            for (int pos = 0; pos < npos; ++pos) a.add(d[pos]);
-            part[L.bt + o] = a.value();
-            part[L.br + o] = a.value();
-            // the BatchNorm gamma / beta slots carry nothing per clip (skel_ft_convert_kernel derives them from the folded gradients): written as zeros so
-            // that every element of partials[b][.] is written, and what the fold sums there is defined
-            part[L.gt + o] = 0.f; part[L.bet + o] = 0.f; part[L.gr + o] = 0.f; part[L.ber + o] = 0.f;
-        }
-    }
-    // 3. G = Wt'^T dh (gradient of the mixed planes), X = Wr'^T dh (the residual branch's share of dx) -> workspace
-    for (int i = tid; i < cin * npos; i += NTHR) {
-        const int c = i / npos, pos = i - c * npos;
-        Acc2 a, b;
-        for (int o = 0; o < cout; ++o) {
-            const float d = dy[o * npos + pos];
-            a.mac(p.Wt[o * cinp + c], d);
-            b.mac(p.Wr[o * cinp + c], d);
-        }
-        G[i] = a.value();
-        X[i] = b.value();
-    }
-    __syncthreads();
-    ft_bwd_graph(dy, p, L, ws, G, X, part);
 }
 
 __device__ inline void ft_stack_bwd(float *dy, float *red, const idf_skel_objproj &op, const FtPlan &plan, int stack, int nodes, const float *ws, float *G,

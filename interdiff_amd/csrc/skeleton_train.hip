@@ -1,6 +1,7 @@
-// Fine-tuning of the skeleton correction predictor with frozen normalisation statistics: launchers of the clip kernel (csrc/skeleton_train.h) and the
-// kernels around it -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients to the reference
-// parameters, Adam (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference kernels read.
+// Fine-tuning of the skeleton correction predictor with frozen normalisation statistics: launchers of the clip kernel (csrc/skeleton_train.h) and of the
+// kernels around it (csrc/stgcn_train.h) -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients
+// to the reference parameters, Adam (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference
+// kernels read.
 // Training with batch statistics and dropout (csrc/skeleton_bn_train.h): the phase launches, the mask generator, the batch statistics / running-buffer
 // update; it shares the fold over clips, Adam and the re-fold with the fine-tuner.
 #include <math.h>
@@ -8,136 +9,11 @@
 
 namespace {
 using namespace idf_skel_train;
-
-constexpr int FT_THR = 256;
-constexpr float BN_EPS = 1e-5f;
+using namespace idf_stgcn_train;
 
 __global__ __launch_bounds__(NTHR) void skel_ft_clip_kernel(const idf_skel_objproj op, const Src s, const FtPlan plan, const FtArgs a, int B) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     ft_clip_body(sm, op, s, plan, a, B, blockIdx.x);
-}
-
-// gsum[i] = sum_b partials[b][i], b ascending; block 0 also folds the loss: out9 = loss, the 8 terms
-struct LossK {
-    float w[8], inv_n[8];      // the 8 weights, 1 / (frames * B * width) of each mean
-};
-__global__ __launch_bounds__(FT_THR) void skel_ft_fold_kernel(const float *__restrict__ partials, const float *__restrict__ loss_part, int B, int n_param,
-                                                             const LossK lk, float *__restrict__ gsum, float *__restrict__ out9) {
-    const int i = blockIdx.x * FT_THR + threadIdx.x;
-    if (i < n_param) {
-        Acc2 a;
-        for (int b = 0; b < B; ++b) a.add(partials[(size_t)b * n_param + i]);
-        gsum[i] = a.value();
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        float loss = 0.f;
-        for (int k = 0; k < 8; ++k) {
-            float a = 0.f;
-            for (int b = 0; b < B; ++b) a += loss_part[(size_t)b * 8 + k];
-            a *= lk.inv_n[k];
-            out9[1 + k] = a;
-            loss += lk.w[k] * a;
-        }
-        out9[0] = loss;
-    }
-}
-
-// one block per layer: gradients of the folded (W s, (b - mu) s + beta), s = gamma / sqrt(var + eps), back to conv weight / bias and BN gamma / beta;
-// T, A and the PReLU slope pass through
-__global__ __launch_bounds__(FT_THR) void skel_ft_convert_kernel(const FtPlan plan, const float *__restrict__ gsum, const float *__restrict__ params,
-                                                                const float *__restrict__ bn, float *__restrict__ grads) {
-    const FtLayer &L = plan.L[blockIdx.x];
-    const int tid = threadIdx.x, cin = L.cin, cout = L.cout;
-    const int nT = (L.v2 ? L.nodes : 1) * NP * NP;
-    if (L.v2)
-        for (int i = tid; i < NP * L.nodes * L.nodes; i += FT_THR) grads[L.A + i] = gsum[L.A + i];
-    for (int i = tid; i < nT; i += FT_THR) grads[L.T + i] = gsum[L.T + i];
-    if (tid == 0) grads[L.pr] = gsum[L.pr];
-    for (int br = 0; br < 2; ++br) {
-        const int W = br ? L.Wr : L.Wt, bb = br ? L.br : L.bt, ga = br ? L.gr : L.gt, be = br ? L.ber : L.bet;
-        const float *mu = bn + L.bn + 2 * br * cout, *var = mu + cout;
-        for (int i = tid; i < cout * cin; i += FT_THR) {
-            const int o = i / cin;
-            const float s = params[ga + o] / sqrtf(var[o] + BN_EPS);
-            grads[W + i] = gsum[W + i] * s;
-        }
-        for (int o = tid; o < cout; o += FT_THR) {
-            const float r = 1.0f / sqrtf(var[o] + BN_EPS), db = gsum[bb + o];
-            Acc2 a;
-            for (int c = 0; c < cin; ++c) a.mac(gsum[W + o * cin + c], params[W + o * cin + c]);
-            a.mac(db, params[bb + o] - mu[o]);
-            grads[bb + o] = db * (params[ga + o] * r);
-            grads[be + o] = db;
-            grads[ga + o] = r * a.value();
-        }
-    }
-}
-
-// torch.optim.Adam (torch/optim/adam.py _single_tensor_adam): grad += wd * p; exp_avg.lerp_(grad, 1 - beta1); exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) grad^2;
-// denom = sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps; p += -(lr / (1 - beta1^step)) * exp_avg / denom
-struct AdamK {
-    float w1, beta2, w2, step_size, bc2_sqrt, eps, wd;
-    int use_wd;
-};
-__global__ __launch_bounds__(FT_THR) void skel_ft_adam_kernel(float *__restrict__ p, const float *__restrict__ grad, float *__restrict__ m, float *__restrict__ v, int n,
-                                                             const AdamK k) {
-    const int i = blockIdx.x * FT_THR + threadIdx.x;
-    if (i >= n) return;
-    float g = grad[i];
-    const float pi = p[i];
-    if (k.use_wd) g = g + k.wd * pi;
-    float mi = m[i], vi = v[i];
-    mi = mi + k.w1 * (g - mi);
-    vi = vi * k.beta2 + k.w2 * g * g;
-    const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi + (-k.step_size) * (mi / denom);
-}
-
-// one block per layer: the arena layer block (csrc/stgcn.h) from the master parameters, folded in double exactly as stgcn_pack.fold_bn does on the host
-// (no contraction: W * s and (b - mu) * s + beta round once per operation); padding stays what the host packer wrote (zero)
-__device__ __forceinline__ double ft_scale(float gamma, float var) {
-#pragma clang fp contract(off)
-    return (double)gamma / sqrt((double)var + 1e-5);
-}
-__device__ __forceinline__ float ft_fold_w(float w, double s) {
-#pragma clang fp contract(off)
-    return (float)((double)w * s);
-}
-__device__ __forceinline__ float ft_fold_b(float b, float mu, double s, float beta) {
-#pragma clang fp contract(off)
-    const double t = ((double)b - (double)mu) * s;
-    return (float)(t + (double)beta);
-}
-__global__ __launch_bounds__(FT_THR) void skel_ft_refold_kernel(const idf_skel_objproj op, const FtPlan plan, const float *__restrict__ params,
-                                                               const float *__restrict__ bn, float *__restrict__ arena) {
-    const int li = blockIdx.x;
-    const FtLayer &L = plan.L[li];
-    const int tid = threadIdx.x, cin = L.cin, cout = L.cout, nodes = L.nodes, cinp = pad16(cin), coutp = pad16(cout);
-    const int nT = (L.v2 ? nodes : 1) * NP * NP;
-    float *blk = arena + op.layer[li];
-    for (int i = tid; i < nT; i += FT_THR) blk[i] = params[L.T + i];
-    blk += pad16(nT);
-    if (L.v2) {
-        for (int i = tid; i < NP * nodes * nodes; i += FT_THR) {
-            const int t = i / (nodes * nodes), r = i - t * nodes * nodes, v = r / nodes, w = r - v * nodes;
-            blk[(t * VP + w) * VP + v] = params[L.A + i];
-        }
-        blk += NP * VP * VP;
-    }
-    for (int br = 0; br < 2; ++br) {
-        const int W = br ? L.Wr : L.Wt, bb = br ? L.br : L.bt, ga = br ? L.gr : L.gt, be = br ? L.ber : L.bet;
-        const float *mu = bn + L.bn + 2 * br * cout, *var = mu + cout;
-        for (int i = tid; i < cout * cin; i += FT_THR) {
-            const int o = i / cin, c = i - o * cin;
-            blk[o * cinp + c] = ft_fold_w(params[W + i], ft_scale(params[ga + o], var[o]));
-        }
-        blk += coutp * cinp;
-        for (int o = tid; o < cout; o += FT_THR) blk[o] = ft_fold_b(params[bb + o], mu[o], ft_scale(params[ga + o], var[o]), params[be + o]);
-        blk += coutp;
-    }
-    if (tid == 0) blk[0] = params[L.pr];
 }
 
 // the channel widths the kernels were built for (all the parameter table needs)
@@ -226,9 +102,9 @@ extern "C" int interdiff_skeleton_finetune_grads(const idf_skel_objproj *op, con
     if (idf_opt_in_lds(reinterpret_cast<const void *>(skel_ft_clip_kernel), (int)FT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
     idf_prof_mark(IDF_K_OTHER, st);
     hipLaunchKernelGGL(skel_ft_clip_kernel, dim3(B), dim3(NTHR), FT_LDS, st, *op, s, P, a, B);
-    hipLaunchKernelGGL(skel_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
                        lk, base + W.gsum, out9);
-    hipLaunchKernelGGL(skel_ft_convert_kernel, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
+    hipLaunchKernelGGL(stgcn_ft_convert_kernel<NP>, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
     idf_prof_mark(-1, st);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
@@ -241,19 +117,10 @@ extern "C" int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, floa
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return IDF_E_INVAL;
     const FtPlan P = ft_plan(op->cin, op->cout);
     hipStream_t st = idf_stream(stream);
-    AdamK k;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    k.w1 = (float)(1.0 - beta1);
-    k.beta2 = (float)beta2;
-    k.w2 = (float)(1.0 - beta2);
-    k.step_size = (float)(lr / bc1);
-    k.bc2_sqrt = (float)sqrt(bc2);
-    k.eps = (float)eps;
-    k.wd = (float)weight_decay;
-    k.use_wd = weight_decay != 0.0;
+    const AdamK k = ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay);
     idf_prof_mark(IDF_K_OTHER, st);
-    hipLaunchKernelGGL(skel_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
-    hipLaunchKernelGGL(skel_ft_refold_kernel, dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
+    hipLaunchKernelGGL(stgcn_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
+    hipLaunchKernelGGL((stgcn_ft_refold_kernel<NP, VP, idf_skel_objproj>), dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
     idf_prof_mark(-1, st);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
@@ -385,7 +252,7 @@ extern "C" int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const 
     }
     for (int phase = 0; phase < TR_PHASES; ++phase)
         hipLaunchKernelGGL(skel_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, s, P, TP, a, t, B, phase);
-    hipLaunchKernelGGL(skel_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
                        lk, grads, out9);
     if (batch_stats || update_running)
         hipLaunchKernelGGL(skel_tr_stats_kernel, dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);

@@ -39,12 +39,8 @@ class ObjProjector:
     def eval(self):
         return self
 
-    def forward(self, data, initialize=False):
-        """``ObjProjector.forward`` (model/correction_smpl.py:69-77): ``data`` is the reference's dict-of-lists batch
-        (``frames[t]['objfit_params']['angle' | 'trans']`` [B,3], ``frames[t]['markers']`` [B,67,7]) or the stacked tensors
-        ``dict(obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7])``.  Axis-angle -> 6D on the rotation kernels, contact =
-        the future frames' marker labels summed, then ``sample``.  Returns (final_results [T,B,9], obj_gt [T,B,9])."""
-        from . import transforms
+    def batch_tensors(self, data):
+        """Either batch form of ``forward`` -> (obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7]), float32 on the device."""
         if 'frames' in data:
             fr = data['frames']
             aa = torch.stack([f['objfit_params']['angle'] for f in fr])
@@ -55,6 +51,15 @@ class ObjProjector:
         aa, ot, mk = (a.to(self.device).float() for a in (aa, ot, mk))
         if mk.dim() != 4 or mk.shape[-1] != 7:
             raise ValueError('markers must be [T,B,67,7] (position | normal | contact label)')
+        return aa, ot, mk
+
+    def forward(self, data, initialize=False):
+        """``ObjProjector.forward`` (model/correction_smpl.py:69-77): ``data`` is the reference's dict-of-lists batch
+        (``frames[t]['objfit_params']['angle' | 'trans']`` [B,3], ``frames[t]['markers']`` [B,67,7]) or the stacked tensors
+        ``dict(obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7])``.  Axis-angle -> 6D on the rotation kernels, contact =
+        the future frames' marker labels summed, then ``sample``.  Returns (final_results [T,B,9], obj_gt [T,B,9])."""
+        from . import transforms
+        aa, ot, mk = self.batch_tensors(data)
         d6 = transforms.matrix_to_rotation_6d(transforms.axis_angle_to_matrix(aa))
         contact = mk[self.past_len:, :, :, 6].sum(dim=0)
         return self.sample(d6, ot, mk, contact, initialize), torch.cat([d6, ot], dim=2)

@@ -7,7 +7,7 @@ temporal and adjacency matrices, the PReLU slopes.
     training_step   + torch.optim.Adam(lr, weight_decay=l2_norm).step()  :41-47, :182-189
 
 Training from scratch -- the module in ``train()``: batch statistics, running-statistics updates, dropout -- is
-``interdiff_amd.skeleton_train.SkeletonTrainer``, built on this class.  NOT built: the SMPL predictor's trainer, learning-rate
+``interdiff_amd.skeleton_train.SkeletonTrainer``, built on this class.  The SMPL predictor's fine-tuner is ``interdiff_amd.correction_finetune``.  NOT built: learning-rate
 schedules, the Lightning glue and the dataset.
 
 All arithmetic runs in libinterdiff_hip.so (csrc/skeleton_train.h / .hip): one workgroup per clip for forward, loss gradient and
@@ -70,13 +70,60 @@ def flatten(state_dict, table):
 
 def folded_to_reference_grads(dWf, dbf, W, b, gamma, mean, var, eps=BN_EPS):
     """Gradients of the folded convolution (W s, (b - mean) s + beta), s = gamma / sqrt(var + eps), back to the reference tensors
-    -> (dW, db, dgamma, dbeta).  What skel_ft_convert_kernel evaluates, in numpy."""
+    -> (dW, db, dgamma, dbeta).  What stgcn_ft_convert_kernel (csrc/stgcn_train.h) evaluates, in numpy."""
     r = 1.0 / np.sqrt(var + eps)
     s = gamma * r
     return dWf * s[:, None], dbf * s, r * ((dWf * W).sum(axis=1) + dbf * (b - mean)), dbf
 
 
-class SkeletonFineTuner:
+class FlatParameters:
+    """The master copy of a predictor's trained parameters as ONE flat device vector in ``named_parameters()`` order (``self.table``), its Adam moments, and
+    the reference-named views of them: what ``SkeletonFineTuner`` and ``correction_finetune.CorrectionFineTuner`` share."""
+
+    def _init_state(self, sd):
+        self.params = torch.from_numpy(flatten(sd, self.table)).to(self.device)
+        self.bn = torch.from_numpy(flatten(sd, self.btable)).to(self.device)
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
+        self.step = 0
+        trained = {n for n, _, _ in self.table}
+        self._keys = list(sd.keys())
+        self._fixed = {k: torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)).clone() for k, v in sd.items() if k not in trained}
+        self._dtypes = {k: torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)).dtype for k, v in sd.items() if k in trained}
+
+    # ---- views
+    def unflatten(self, flat):
+        """A flat vector -> {reference name: view of its slice, reference shape}."""
+        return OrderedDict((n, flat[o:o + int(np.prod(s))].view(s)) for n, o, s in self.table)
+
+    def _flat(self, t):
+        if isinstance(t, dict):
+            t = torch.cat([t[n].reshape(-1).to(self.device, torch.float32) for n, _, _ in self.table])
+        t = t.to(self.device, torch.float32).contiguous()
+        if t.numel() != self.n_param:
+            raise ValueError('expected %d values, got %d' % (self.n_param, t.numel()))
+        return t
+
+    # ---- state
+    def named_parameters(self):
+        return self.unflatten(self.params)
+
+    def state_dict(self):
+        """The reference's keys, shapes and dtypes (CPU tensors): trained parameters from the master copy, buffers as they came in."""
+        cur = {n: v.detach().cpu() for n, v in self.unflatten(self.params).items()}
+        return OrderedDict((k, cur[k].to(self._dtypes[k]).clone() if k in cur else self._fixed[k].clone()) for k in self._keys)
+
+    def optimizer_state(self):
+        return dict(step=self.step, exp_avg={n: v.detach().cpu().clone() for n, v in self.unflatten(self.exp_avg).items()},
+                    exp_avg_sq={n: v.detach().cpu().clone() for n, v in self.unflatten(self.exp_avg_sq).items()})
+
+    def load_optimizer_state(self, state):
+        self.exp_avg.copy_(self._flat(state['exp_avg']))
+        self.exp_avg_sq.copy_(self._flat(state['exp_avg_sq']))
+        self.step = int(state['step'])
+
+
+class SkeletonFineTuner(FlatParameters):
     """Adapts a skeleton predictor to a user's own clips.  ``batch`` is what ``skeleton_validation_step`` takes: (body [B,T,21,3],
     object keypoints [B,T,12,3], pose [B,T,7], zero_pose_obj [B,12,3]); T = past_len + future_len = 20."""
 
@@ -91,15 +138,7 @@ class SkeletonFineTuner:
         self.table, self.btable = param_table(sd), buffer_table(sd)
         self.n_param = self.table[-1][1] + int(np.prod(self.table[-1][2]))
         self._check_table()
-        self.params = torch.from_numpy(flatten(sd, self.table)).to(self.device)
-        self.bn = torch.from_numpy(flatten(sd, self.btable)).to(self.device)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.step = 0
-        trained = {n for n, _, _ in self.table}
-        self._keys = list(sd.keys())
-        self._fixed = {k: torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)).clone() for k, v in sd.items() if k not in trained}
-        self._dtypes = {k: torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)).dtype for k, v in sd.items() if k in trained}
+        self._init_state(sd)
         self._w8 = (C.c_float * 8)(*self.weights.vector(0)[2:])
         self._ws = {}
 
@@ -120,19 +159,6 @@ class SkeletonFineTuner:
         nb = self.btable[-1][1] + int(np.prod(self.btable[-1][2]))
         if n_param.value != self.n_param or n_bn.value != nb:
             raise RuntimeError('parameter count: library %d / %d, state_dict %d / %d' % (n_param.value, n_bn.value, self.n_param, nb))
-
-    # ---- views
-    def unflatten(self, flat):
-        """A flat vector -> {reference name: view of its slice, reference shape}."""
-        return OrderedDict((n, flat[o:o + int(np.prod(s))].view(s)) for n, o, s in self.table)
-
-    def _flat(self, t):
-        if isinstance(t, dict):
-            t = torch.cat([t[n].reshape(-1).to(self.device, torch.float32) for n, _, _ in self.table])
-        t = t.to(self.device, torch.float32).contiguous()
-        if t.numel() != self.n_param:
-            raise ValueError('expected %d values, got %d' % (self.n_param, t.numel()))
-        return t
 
     def _workspace(self, B):
         if B not in self._ws:
@@ -186,21 +212,3 @@ class SkeletonFineTuner:
         out9, grads = self._grads(batch)
         self.apply_gradients(grads)
         return out9[0]
-
-    # ---- state
-    def named_parameters(self):
-        return self.unflatten(self.params)
-
-    def state_dict(self):
-        """The reference's keys, shapes and dtypes (CPU tensors): trained parameters from the master copy, buffers as they came in."""
-        cur = {n: v.detach().cpu() for n, v in self.unflatten(self.params).items()}
-        return OrderedDict((k, cur[k].to(self._dtypes[k]).clone() if k in cur else self._fixed[k].clone()) for k in self._keys)
-
-    def optimizer_state(self):
-        return dict(step=self.step, exp_avg={n: v.detach().cpu().clone() for n, v in self.unflatten(self.exp_avg).items()},
-                    exp_avg_sq={n: v.detach().cpu().clone() for n, v in self.unflatten(self.exp_avg_sq).items()})
-
-    def load_optimizer_state(self, state):
-        self.exp_avg.copy_(self._flat(state['exp_avg']))
-        self.exp_avg_sq.copy_(self._flat(state['exp_avg_sq']))
-        self.step = int(state['step'])
