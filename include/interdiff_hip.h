@@ -377,8 +377,8 @@ int interdiff_objprojector_forward(const idf_objproj *op, const float *obj_angle
                                    const int32_t *contact, int32_t B, int32_t initialize, float *out, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- FINE-TUNING of the correction predictor under the object-pose loss, with FROZEN normalisation statistics (the reference module in eval() with
- * autograd on: BatchNorm uses its running statistics and never writes them, dropout is off, contact clips take the argmax node; `multinomial` selection,
- * train-mode BatchNorm, dropout and the gradient of the contact / penetration terms are NOT built).  Device code: csrc/objproj_train.h, launchers
+ * autograd on: BatchNorm uses its running statistics and never writes them, dropout is off, contact clips take the argmax node; the module in train() -- batch statistics,
+ * dropout, drawn nodes -- is the TRAINING block below; the gradient of the contact / penetration terms is NOT built).  Device code: csrc/objproj_train.h, launchers
  * csrc/objproj_train.hip; the layer backward and the fold / Adam / re-fold kernels are shared with the skeleton fine-tuner (csrc/stgcn_train.h).
  * Additive entries: interdiff_abi_version() stays what it was.
  *
@@ -424,6 +424,47 @@ int interdiff_correction_finetune_grads(const idf_objproj *op, const float *para
 int interdiff_correction_finetune_step(const idf_objproj *op, float *arena, float *params, const float *bn, const float *grads,
                                        float *exp_avg, float *exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps,
                                        double weight_decay, void *stream);
+
+/* ---- TRAINING of the correction predictor the way the reference trains it (train_correction_smpl.py: the module in train()): every BatchNorm2d
+ * normalises with the statistics of the BATCH (biased variance, eps 1e-5) and updates its running buffers; nn.Dropout(p) follows the tcn BatchNorm of
+ * every ST_GCNN_layer (model/layers.py:308-318); the contact node of a clip is GIVEN (the caller draws it: torch.multinomial, model/correction_smpl.py:
+ * 131-132).  Device code: csrc/objproj_bn_train.h around the fine-tuner's csrc/objproj_train.h, the train-mode layer shared with the skeleton trainer
+ * (csrc/stgcn_bn_train.h); launchers csrc/objproj_bn_train.hip.  Additive entries: interdiff_abi_version() stays what it was.  Parameter and buffer
+ * layouts: the PARAMETER TABLE above.  NOT built: the gradient of the contact / penetration terms (d_obj_pred stays their seam).
+ *
+ * interdiff_correction_train_grads   replaces loss.backward() on LitInteraction.calc_loss (train_correction_smpl.py:60-101) of ObjProjector.forward
+ *      (model/correction_smpl.py:69-138) with the module in train(), and the buffer updates torch.nn.BatchNorm2d.forward makes there.  Arguments as
+ *      interdiff_correction_finetune_grads, and:
+ *      nodes int32 [B] or NULL  the node clip b reads when initialize = 0 (replaces :125-136, both branches): 0 = the object node (a clip without
+ *                 contact), 1 + marker otherwise; values outside 0 .. 67 are clamped.  NULL: the fine-tuner's rule (node 0 without contact, else
+ *                 1 + argmax(contact + hand bonus)); contact may be NULL when nodes is given.  Not read when initialize != 0 (the 68-node mean).
+ *      bn [n_bn]  running mean / variance, READ AND WRITTEN IN PLACE when update_running = 1: running <- (1 - momentum) running + momentum {mean,
+ *                 variance n / (n - 1)}, n = B * 10 * nodes; untouched (and never read) when update_running = 0.
+ *      p_drop in [0, 1); masks: device uint8, one byte per element, the 12 layers in named_parameters() order, each [B][cout][10][nodes] (121 040 bytes
+ *                 per clip), keep iff nonzero, kept values times fp32(1 / (1 - p_drop)); NULL: the masks interdiff_correction_train_masks(seed, step)
+ *                 writes (p_drop = 0: no dropout, nothing is drawn).
+ *      batch_stats [n_bn] or NULL: mean and BIASED variance of this batch in the layout of bn.
+ *      op->arena must hold the gcn.T / gcn.A / PReLU values of `params` (interdiff_correction_finetune_step keeps it so); the convolutions and the
+ *      BatchNorm affine parameters are read from `params`, unfolded.
+ *      17 launches of one 1024-thread workgroup per clip, cut wherever a BatchNorm needs the whole batch (no grid barrier inside a kernel), then the
+ *      fold over clips and the statistics kernel, all on `stream`.  Statistics and their gradients are merged over the clips in ascending order in
+ *      double (Chan's merge of per-clip (sum, M2)); no atomics: two calls give the same bits.  The gradients of the 24 convolution biases, which cancel
+ *      inside the batch normalisation, are written as exact 0.  IDF_E_INVAL: null pointer, B < 1, T != op->T, T > 64, past_len >= T, p_drop outside
+ *      [0, 1), momentum outside [0, 1], update_running not 0 / 1, short workspace.
+ * interdiff_correction_train_masks   replaces the Bernoulli draw of nn.Dropout in train() (model/layers.py:317): the keep masks of training step `step`
+ *      in the layout above, Philox4x32-10 keyed by `seed`, counter (element index / 4, layer, step); an element keeps iff its uniform draw in [0, 1)
+ *      is >= p_drop.
+ * interdiff_correction_train_workspace_bytes   the workspace interdiff_correction_train_grads needs at batch B (0: bad arguments).
+ * optimizer.step() and the re-fold: interdiff_correction_finetune_step above, with the bn vector this entry has just updated.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_correction_train_workspace_bytes(const idf_objproj *op, int32_t B);
+int interdiff_correction_train_grads(const idf_objproj *op, const float *params, float *bn, const float *obj_angles, const float *obj_trans,
+                                     const float *markers, const int32_t *contact, const int32_t *nodes, const float *d_obj_pred, int32_t B,
+                                     int32_t T, int32_t initialize, const float *weights8, double p_drop, const uint8_t *masks, uint64_t seed,
+                                     uint64_t step, double momentum, int32_t update_running, float *out9, float *grads, float *batch_stats,
+                                     void *ws, size_t ws_bytes, void *stream);
+int interdiff_correction_train_masks(const idf_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
+                                     void *stream);
 
 /* ------------------------------------------------------------------------------------
  * denoised_fn, fused   replaces eval_smpl_short.py:84-130 for one gated step.
@@ -572,8 +613,8 @@ int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, float *arena, f
 
 /* ---- TRAINING of the skeleton predictor the way the reference trains it (train_correction_skeleton.py: the module in train()): every BatchNorm2d
  * normalises with the statistics of the BATCH (biased variance, eps 1e-5) and updates its running buffers; nn.Dropout(p) follows the tcn BatchNorm
- * of every ST_GCNN_layer (model/layers.py:308-318).  Device code: csrc/skeleton_bn_train.h around the fine-tuner's csrc/skeleton_train.h; launchers
- * csrc/skeleton_train.hip.  Additive entries: interdiff_abi_version() stays what it was.  Parameter and buffer layouts: the PARAMETER TABLE above.
+ * of every ST_GCNN_layer (model/layers.py:308-318).  Device code: csrc/skeleton_bn_train.h around the fine-tuner's csrc/skeleton_train.h, the train-mode
+ * layer in csrc/stgcn_bn_train.h; launchers csrc/skeleton_train.hip.  Additive entries: interdiff_abi_version() stays what it was.  Parameter and buffer layouts: the PARAMETER TABLE above.
  *
  * interdiff_skeleton_train_grads   replaces loss.backward() on LitObjInteraction._common_step (train_correction_skeleton.py:128-154) with the module
  *      in train(), and the buffer updates torch.nn.BatchNorm2d.forward makes there.  Arguments as interdiff_skeleton_finetune_grads, and:

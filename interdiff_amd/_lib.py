@@ -153,6 +153,10 @@ _SIGS = {
     'interdiff_correction_finetune_grads': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, sz, vp]),
     'interdiff_correction_finetune_step': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double,
                                                      C.c_double, vp]),
+    'interdiff_correction_train_workspace_bytes': (sz, [C.POINTER(ObjProj), i32]),
+    'interdiff_correction_train_grads': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), C.c_double, vp, u64, u64,
+                                                   C.c_double, i32, vp, vp, vp, vp, sz, vp]),
+    'interdiff_correction_train_masks': (C.c_int, [C.POINTER(ObjProj), i32, C.c_double, u64, u64, vp, vp]),
     'interdiff_correction_workspace_bytes': (sz, [C.POINTER(CorrectionCtx), i32, i32]),
     'interdiff_correction': (C.c_int, [C.POINTER(CorrectionCtx), vp, vp, vp, vp, vp, i32, i32, f32,
                                        vp, vp, vp, vp, vp, sz, vp]),

@@ -9,8 +9,9 @@ convolutions, BatchNorm affine weights, the temporal and adjacency matrices, the
 That is the reference's own regime where its schedule starts: ``_common_step`` anneals the contact and penetration terms by
 ``min(1, epoch / second_stage) ** 2``, exactly 0 at epoch 0, so there it trains on the eight MSE terms alone.  From epoch 1 on those two
 terms add a gradient that reaches the network only through ``obj_pred`` [T,B,9]: ``d_obj_pred`` is the seam through which a caller hands
-it in.  NOT built: the contact / penetration gradient itself, ``multinomial`` node selection, train-mode BatchNorm and dropout,
-learning-rate schedules, the Lightning glue and the dataset.
+it in.  Training the way the reference trains -- the module in ``train()``: batch statistics, running-statistics updates, dropout,
+``multinomial`` node selection -- is ``interdiff_amd.correction_train.CorrectionTrainer``, built on this class.  NOT built: the contact /
+penetration gradient itself, learning-rate schedules, the Lightning glue and the dataset.
 
 All arithmetic runs in libinterdiff_hip.so (csrc/objproj_train.h / .hip, csrc/stgcn_train.h): one workgroup per clip for forward, loss
 gradient and backward, a fixed-order fold over clips, Adam on fp32 master parameters in the reference layout, and the re-fold into the
@@ -90,7 +91,8 @@ class CorrectionFineTuner(FlatParameters):
         return self._ws[B]
 
     # ---- the step
-    def _grads(self, batch, initialize=False, d_obj_pred=None):
+    def _inputs(self, batch, d_obj_pred=None):
+        """-> (B, T, d6, obj_trans, marker positions, contact int32 [B,67], d_obj_pred or None): contiguous device tensors, what the library takes."""
         dev = self.device
         aa, ot, mk = self.predictor.batch_tensors(batch)
         T, B = aa.shape[:2]
@@ -104,6 +106,11 @@ class CorrectionFineTuner(FlatParameters):
             extra = d_obj_pred.to(dev, torch.float32).contiguous()
             if tuple(extra.shape) != (T, B, 9):
                 raise ValueError('d_obj_pred must be [%d,%d,9]' % (T, B))
+        return B, T, d6, ot, pos, contact, extra
+
+    def _grads(self, batch, initialize=False, d_obj_pred=None):
+        dev = self.device
+        B, T, d6, ot, pos, contact, extra = self._inputs(batch, d_obj_pred)
         out9 = torch.empty(9, dtype=torch.float32, device=dev)
         grads = torch.empty(self.n_param, dtype=torch.float32, device=dev)
         ws = self._workspace(B)

@@ -49,6 +49,28 @@ static_assert(OT_LDS + 64 <= 160 * 1024, "one workgroup per CU");
 // the flat parameter plan of this predictor: 67 / 1 / 68 nodes over NP = 10 coefficients
 inline FtPlan ot_plan(const int32_t *cin, const int32_t *cout) { return idf_stgcn_train::ft_plan_for(cin, cout, NP, NM, BUF); }
 
+// ---- host: what the launchers (csrc/objproj_train.hip, csrc/objproj_bn_train.hip) check before a launch
+// the channel widths the kernels were built for (all the parameter table needs)
+inline int ot_check_widths(const idf_objproj *op) {
+    if (idf_objproj_check(op) != IDF_OK) return IDF_E_INVAL;
+    for (int st = 0; st < 3; ++st) {
+        if (op->cin[st * 4] != CH || op->cout[st * 4 + 3] != CH) return IDF_E_INVAL;
+        for (int l = 0; l < 4; ++l) {
+            const int li = st * 4 + l;
+            if (op->cin[li] < 1 || op->cin[li] > MAXC || op->cout[li] < 1 || op->cout[li] > MAXC) return IDF_E_INVAL;
+            if (l < 3 && op->cout[li] != op->cin[li + 1]) return IDF_E_INVAL;
+        }
+    }
+    return IDF_OK;
+}
+
+inline int ot_check(const idf_objproj *op, int B) {
+    if (ot_check_widths(op) != IDF_OK || !op->arena || B < 1 || op->T < 2 || op->T > MAXT || op->past_len >= op->T) return IDF_E_INVAL;
+    for (int li = 0; li < 12; ++li)
+        if (op->layer[li] < 0) return IDF_E_INVAL;
+    return IDF_OK;
+}
+
 struct OtArgs {
     const float *obj_angles;   // [T][B][6] 6D rotation: input of the past frames and target of all
     const float *obj_trans;    // [T][B][3]

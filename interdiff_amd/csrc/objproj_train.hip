@@ -2,6 +2,7 @@
 // of the kernels around it (csrc/stgcn_train.h) -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions'
 // gradients to the reference parameters, Adam on the fp32 master parameters, and the re-fold into the arena that interdiff_objprojector_sample / _forward
 // and the correction hook read.
+// Training with batch statistics and dropout: csrc/objproj_bn_train.hip, which shares Adam and the re-fold below.
 #include <math.h>
 #include "objproj_train.h"
 
@@ -12,27 +13,6 @@ using namespace idf_stgcn_train;
 __global__ __launch_bounds__(NTHR) void objproj_ft_clip_kernel(const idf_objproj op, const FtPlan plan, const OtArgs a, int B) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     ot_clip_body(sm, op, plan, a, B, blockIdx.x);
-}
-
-// the channel widths the kernels were built for (all the parameter table needs)
-int ot_check_widths(const idf_objproj *op) {
-    if (idf_objproj_check(op) != IDF_OK) return IDF_E_INVAL;
-    for (int st = 0; st < 3; ++st) {
-        if (op->cin[st * 4] != CH || op->cout[st * 4 + 3] != CH) return IDF_E_INVAL;
-        for (int l = 0; l < 4; ++l) {
-            const int li = st * 4 + l;
-            if (op->cin[li] < 1 || op->cin[li] > MAXC || op->cout[li] < 1 || op->cout[li] > MAXC) return IDF_E_INVAL;
-            if (l < 3 && op->cout[li] != op->cin[li + 1]) return IDF_E_INVAL;
-        }
-    }
-    return IDF_OK;
-}
-
-int ot_check(const idf_objproj *op, int B) {
-    if (ot_check_widths(op) != IDF_OK || !op->arena || B < 1 || op->T < 2 || op->T > MAXT || op->past_len >= op->T) return IDF_E_INVAL;
-    for (int li = 0; li < 12; ++li)
-        if (op->layer[li] < 0) return IDF_E_INVAL;
-    return IDF_OK;
 }
 
 // workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]

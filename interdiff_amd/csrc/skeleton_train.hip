@@ -2,8 +2,8 @@
 // kernels around it (csrc/stgcn_train.h) -- the fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients
 // to the reference parameters, Adam (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference
 // kernels read.
-// Training with batch statistics and dropout (csrc/skeleton_bn_train.h): the phase launches, the mask generator, the batch statistics / running-buffer
-// update; it shares the fold over clips, Adam and the re-fold with the fine-tuner.
+// Training with batch statistics and dropout (csrc/skeleton_bn_train.h): the phase launches; the mask generator and the batch statistics /
+// running-buffer update are csrc/stgcn_bn_train.h's; it shares the fold over clips, Adam and the re-fold with the fine-tuner.
 #include <math.h>
 #include "skeleton_bn_train.h"
 
@@ -135,37 +135,6 @@ __global__ __launch_bounds__(NTHR) void skel_tr_phase_kernel(const idf_skel_objp
     tr_phase_body(sm, op, s, plan, tp, a, t, B, blockIdx.x, phase);
 }
 
-// grid (groups of FT_THR elements of the largest layer, 12 layers): out[B * mask[l] + i] = keep
-__global__ __launch_bounds__(FT_THR) void skel_tr_masks_kernel(const FtPlan plan, const TrPlan tp, int B, float p, uint64_t seed, uint64_t step,
-                                                              uint8_t *__restrict__ out) {
-    const int li = blockIdx.y;
-    const size_t n = (size_t)B * plan.L[li].cout * NP * plan.L[li].nodes, i = (size_t)blockIdx.x * FT_THR + threadIdx.x;
-    if (i < n) out[(size_t)B * tp.mask[li] + i] = tr_uniform(seed, step, li, (uint32_t)i) >= p ? 1 : 0;
-}
-
-// one block per layer: mean and biased variance of the batch -> batch_stats (when given), and the running buffers
-// running <- (1 - momentum) running + momentum {mean, var n / (n - 1)} (torch.nn.BatchNorm2d in train()), in double, rounded once
-__global__ __launch_bounds__(2 * MAXC) void skel_tr_stats_kernel(const FtPlan plan, const double *__restrict__ statp, int B, double momentum, int update,
-                                                                float *__restrict__ bn, float *__restrict__ batch_stats) {
-#pragma clang fp contract(off)
-    const int li = blockIdx.x;
-    const FtLayer &L = plan.L[li];
-    if ((int)threadIdx.x >= 2 * L.cout) return;
-    const int br = threadIdx.x / L.cout, o = threadIdx.x - br * L.cout, npos = NP * L.nodes;
-    double mean, var;
-    tr_fold_stats(statp, B, li, br, o, npos, mean, var);
-    const int at = L.bn + 2 * br * L.cout + o;
-    if (batch_stats) {
-        batch_stats[at] = (float)mean;
-        batch_stats[at + L.cout] = (float)var;
-    }
-    if (update) {
-        const double n = (double)B * (double)npos;
-        bn[at] = (float)((1.0 - momentum) * (double)bn[at] + momentum * mean);
-        bn[at + L.cout] = (float)((1.0 - momentum) * (double)bn[at + L.cout] + momentum * (var * (n / (n - 1.0))));
-    }
-}
-
 // workspace (floats): partials [B][n_param] | loss_part [B][8] | clips [B][ws_clip] | statp, dyp [B][TR_SEAM] doubles | masks [B][mask_clip] bytes
 struct TrWs {
     size_t partials, loss_part, clips, statp, dyp, masks, total;
@@ -184,12 +153,6 @@ TrWs tr_ws(const FtPlan &P, const TrPlan &T, int B) {
     return w;
 }
 
-void tr_launch_masks(const FtPlan &P, const TrPlan &T, int B, double p, uint64_t seed, uint64_t step, uint8_t *out, hipStream_t st) {
-    size_t widest = 0;
-    for (int li = 0; li < 12; ++li) widest = std::max(widest, (size_t)B * P.L[li].cout * NP * P.L[li].nodes);
-    hipLaunchKernelGGL(skel_tr_masks_kernel, dim3((unsigned)((widest + FT_THR - 1) / FT_THR), 12), dim3(FT_THR), 0, st, P, T, B, (float)p, seed, step, out);
-}
-
 }  // namespace
 
 extern "C" size_t interdiff_skeleton_train_workspace_bytes(const idf_skel_objproj *op, int32_t B) {
@@ -202,7 +165,7 @@ extern "C" int interdiff_skeleton_train_masks(const idf_skel_objproj *op, int32_
                                               void *stream) {
     if (!masks_out || ft_check_widths(op) != IDF_OK || B < 1 || !(p_drop >= 0.0 && p_drop < 1.0)) return IDF_E_INVAL;
     const FtPlan P = ft_plan(op->cin, op->cout);
-    tr_launch_masks(P, tr_plan(P), B, p_drop, seed, step, masks_out, idf_stream(stream));
+    stgcn_tr_launch_masks<NP>(P, tr_plan(P), B, p_drop, seed, step, masks_out, idf_stream(stream));
     IDF_CHECK_LAUNCH();
     return IDF_OK;
 }
@@ -247,7 +210,7 @@ extern "C" int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const 
     idf_prof_mark(IDF_K_OTHER, st);
     if (!masks && p_drop > 0.0) {                       // the generator's masks go through the same buffer layout as injected ones
         uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
-        tr_launch_masks(P, TP, B, p_drop, seed, step, mb, st);
+        stgcn_tr_launch_masks<NP>(P, TP, B, p_drop, seed, step, mb, st);
         t.masks = mb;
     }
     for (int phase = 0; phase < TR_PHASES; ++phase)
@@ -255,7 +218,7 @@ extern "C" int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const 
     hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
                        lk, grads, out9);
     if (batch_stats || update_running)
-        hipLaunchKernelGGL(skel_tr_stats_kernel, dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
+        hipLaunchKernelGGL((stgcn_tr_stats_kernel<Tr, NP, MAXC>), dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
     idf_prof_mark(-1, st);
     IDF_CHECK_LAUNCH();
     return IDF_OK;

@@ -13,9 +13,10 @@ Departure from the reference: the 24 convolution biases cancel inside a batch no
 reference computes fp32 rounding noise there, which Adam turns into a +-lr random walk of parameters that cannot influence the
 train-mode output; here those gradients are exact 0.0, and with ``weight_decay = 0`` the biases do not move.
 
-NOT built: the SMPL predictor's trainer, learning-rate schedules, the Lightning glue, the dataset.
+The SMPL predictor's trainer is ``interdiff_amd.correction_train``.  NOT built: learning-rate schedules, the Lightning glue, the dataset.
 
-All arithmetic runs in libinterdiff_hip.so (csrc/skeleton_bn_train.h around csrc/skeleton_train.h; launchers csrc/skeleton_train.hip).
+All arithmetic runs in libinterdiff_hip.so (csrc/skeleton_bn_train.h around csrc/skeleton_train.h, the train-mode layer in
+csrc/stgcn_bn_train.h; launchers csrc/skeleton_train.hip).
 """
 import ctypes as C
 import math

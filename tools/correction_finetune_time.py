@@ -46,7 +46,7 @@ def synthetic_state_dict(seed=8200):
     return {k: np.asarray(v, np.float32) for k, v in sd.items()}
 
 
-def synthetic_batch(seed=82):
+def synthetic_batch(seed=82, B=B):
     rs = np.random.RandomState(seed)
     walk = lambda scale, step, *s: scale * rs.standard_normal((1, B) + s) + np.cumsum(step * rs.standard_normal((T, B) + s), axis=0)
     mk = np.concatenate([walk(0.3, 0.004, NM, 3), rs.standard_normal((T, B, NM, 3)), (rs.uniform(size=(T, B, NM, 1)) < 0.2).astype(np.float64)], axis=3)
