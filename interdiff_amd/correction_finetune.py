@@ -16,19 +16,18 @@ penetration gradient itself, learning-rate schedules, the Lightning glue and the
 All arithmetic runs in libinterdiff_hip.so (csrc/objproj_train.h / .hip, csrc/stgcn_train.h): one workgroup per clip for forward, loss
 gradient and backward, a fixed-order fold over clips, Adam on fp32 master parameters in the reference layout, and the re-fold into the
 arena that ``ObjProjector``, the correction hook and ``correction_losses.validation_step`` read.  The flat parameter layout
-(``param_table``) is documented in include/interdiff_hip.h.
+(``param_table``) is documented in include/interdiff_hip.h; it, the master copy and the Adam state (``FlatParameters``) are
+``interdiff_amd.stgcn_trainer``'s, shared with the skeleton predictor.
 """
-import ctypes as C
-import numpy as np
 import torch
 from . import _lib
 from .objprojector import ObjProjector
-from .skeleton import _check, _strip
-from .skeleton_finetune import FlatParameters, LAYER_PARAMS, LAYER_BUFFERS, TABLE_COLS, param_table, buffer_table
-from .stgcn_pack import STACKS
-from .correction_losses import CorrectionLossWeights, MSE_KEYS
+from .skeleton import _strip
+from .correction_losses import CorrectionLossWeights
+from .stgcn_trainer import FlatParameters, param_table            # noqa: F401
 
 N_MARKERS = 67
+N_PRE = 10
 
 
 def rotation_6d_of_axis_angle(aa):
@@ -50,6 +49,8 @@ class CorrectionFineTuner(FlatParameters):
     dict-of-lists (``frames[t]['objfit_params']['angle' | 'trans']`` [B,3], ``frames[t]['markers']`` [B,67,7]) or the stacked tensors
     ``dict(obj_angle [T,B,3], obj_trans [T,B,3], markers [T,B,67,7])``."""
 
+    PREFIX, NODES, N_PRE = 'correction', N_MARKERS, N_PRE
+
     def __init__(self, state_dict, T=35, past_len=10, lr=3e-4, weight_decay=0., betas=(0.9, 0.999), eps=1e-8, weights=CorrectionLossWeights(), device='cuda'):
         sd = _strip(state_dict)
         self.lib = _lib.load()
@@ -58,37 +59,7 @@ class CorrectionFineTuner(FlatParameters):
         self.weights = weights
         self.predictor = ObjProjector(sd, T, past_len, device=device)          # its arena is the live one
         self.past_len, self.T = past_len, T
-        self.table, self.btable = param_table(sd), buffer_table(sd)
-        self.n_param = self.table[-1][1] + int(np.prod(self.table[-1][2]))
-        self._check_table()
         self._init_state(sd)
-        self._w8 = (C.c_float * 8)(*self.weights.vector(0)[2:])
-        self._ws = {}
-
-    def _check_table(self):
-        """The C side derives the same table from the channel widths (csrc/objproj_train.h ot_plan): they must agree."""
-        cop = self.predictor.cop
-        tab = (C.c_int32 * (12 * TABLE_COLS))()
-        n_param, n_bn = C.c_int32(), C.c_int32()
-        _check(self.lib.interdiff_correction_finetune_param_table(C.byref(cop), tab, C.byref(n_param), C.byref(n_bn)), 'correction_finetune_param_table')
-        offs = {n: o for n, o, _ in self.table}
-        boffs = {n: o for n, o, _ in self.btable}
-        for li in range(12):
-            p = '%s.%d.' % (STACKS[li // 4], li % 4)
-            row = list(tab[li * TABLE_COLS:(li + 1) * TABLE_COLS])
-            want = [offs.get(p + s, -1) for s in LAYER_PARAMS] + [cop.cin[li], cop.cout[li], (N_MARKERS, 1, N_MARKERS + 1)[li // 4], int(li // 4 == 2),
-                                                                 boffs[p + LAYER_BUFFERS[0]]]
-            if row != want:
-                raise RuntimeError('parameter table of layer %d: library %r, state_dict %r' % (li, row, want))
-        nb = self.btable[-1][1] + int(np.prod(self.btable[-1][2]))
-        if n_param.value != self.n_param or n_bn.value != nb:
-            raise RuntimeError('parameter count: library %d / %d, state_dict %d / %d' % (n_param.value, n_bn.value, self.n_param, nb))
-
-    def _workspace(self, B):
-        if B not in self._ws:
-            n = self.lib.interdiff_correction_finetune_workspace_bytes(C.byref(self.predictor.cop), B)
-            self._ws = {B: torch.empty(n, dtype=torch.uint8, device=self.device)}
-        return self._ws[B]
 
     # ---- the step
     def _inputs(self, batch, d_obj_pred=None):
@@ -109,32 +80,19 @@ class CorrectionFineTuner(FlatParameters):
         return B, T, d6, ot, pos, contact, extra
 
     def _grads(self, batch, initialize=False, d_obj_pred=None):
-        dev = self.device
         B, T, d6, ot, pos, contact, extra = self._inputs(batch, d_obj_pred)
-        out9 = torch.empty(9, dtype=torch.float32, device=dev)
-        grads = torch.empty(self.n_param, dtype=torch.float32, device=dev)
+        out9, grads = self._outputs()
         ws = self._workspace(B)
-        _check(self.lib.interdiff_correction_finetune_grads(C.byref(self.predictor.cop), _lib.dptr(self.params), _lib.dptr(self.bn), _lib.dptr(d6), _lib.dptr(ot),
-                                                            _lib.dptr(pos), _lib.dptr(contact, torch.int32), _lib.dptr(extra, allow_none=True), B, T,
-                                                            int(bool(initialize)), self._w8, _lib.dptr(out9), _lib.dptr(grads), _lib.dptr(ws), ws.numel(),
-                                                            _lib.stream()), 'correction_finetune_grads')
+        self._call('finetune_grads', _lib.dptr(self.params), _lib.dptr(self.bn), _lib.dptr(d6), _lib.dptr(ot), _lib.dptr(pos),
+                   _lib.dptr(contact, torch.int32), _lib.dptr(extra, allow_none=True), B, T, int(bool(initialize)), self._w8, _lib.dptr(out9),
+                   _lib.dptr(grads), _lib.dptr(ws), ws.numel(), _lib.stream())
         return out9, grads
 
     def loss_and_grads(self, batch, initialize=False, d_obj_pred=None):
         """-> (loss, loss_dict, weighted_loss_dict, grads): 0-dim device tensors under the reference's 8 MSE keys, ``grads`` = {reference
         parameter name: d (loss + <d_obj_pred, obj_pred>) / d parameter} (views of one flat device tensor).  ``d_obj_pred`` [T,B,9]: the gradient
         at the prediction of any further term of the caller's objective; the returned loss stays that of the 8 terms."""
-        out9, grads = self._grads(batch, initialize, d_obj_pred)
-        w = torch.tensor(self.weights.vector(0)[2:], dtype=torch.float32, device=self.device) * out9[1:]
-        return out9[0], {k: out9[1 + n] for n, k in enumerate(MSE_KEYS)}, {k: w[n] for n, k in enumerate(MSE_KEYS)}, self.unflatten(grads)
-
-    def apply_gradients(self, grads):
-        """One Adam step on ``grads`` (flat [n_param] or a dict under reference names) and the re-fold of the arena."""
-        g = self._flat(grads)
-        self.step += 1
-        _check(self.lib.interdiff_correction_finetune_step(C.byref(self.predictor.cop), _lib.dptr(self.predictor.arena), _lib.dptr(self.params), _lib.dptr(self.bn),
-                                                           _lib.dptr(g), _lib.dptr(self.exp_avg), _lib.dptr(self.exp_avg_sq), self.step, self.lr, self.betas[0],
-                                                           self.betas[1], self.eps, self.weight_decay, _lib.stream()), 'correction_finetune_step')
+        return self._packed(*self._grads(batch, initialize, d_obj_pred))
 
     def training_step(self, batch, current_epoch=0, d_obj_pred=None):
         """Gradients (``initialize = current_epoch < 10``, like ``_common_step``), Adam, re-fold.  -> the loss of the 8 MSE terms BEFORE the step

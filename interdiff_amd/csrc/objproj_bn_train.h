@@ -1,6 +1,6 @@
 // Training of the SMPL contact-frame correction predictor the way the reference trains it (train_correction_smpl.py: the module in train()): every
 // BatchNorm2d normalises with the statistics of the BATCH and nn.Dropout follows the tcn BatchNorm (model/layers.py:308-318, :339-345); from epoch 10 on the
-// contact node is drawn (model/correction_smpl.py:131-132) and arrives here as nodes[b].  Device code; launchers: csrc/objproj_train.hip.  The train-mode
+// contact node is drawn (model/correction_smpl.py:131-132) and arrives here as nodes[b].  Device code; launchers: csrc/objproj_bn_train.hip.  The train-mode
 // ST-GCN layer (FRONT, FIN, A, B), the Chan fold of the statistics, the keep masks and their Philox generator are csrc/stgcn_bn_train.h's, shared with the
 // skeleton trainer; the flat parameter plan, the compensated sum and the graph forward / backward are the fine-tuner's (csrc/stgcn_train.h).
 //
@@ -16,9 +16,9 @@
 //             12       B(8), the skip connections; A(7), A(3)
 //             13..15   B(l), A(l-1) for l = 20 - phase and 16 - phase
 //             16       B(4), B(0)
-// The pieces around the stacks below are ot_clip_body's (csrc/objproj_train.h) sections, statement for statement -- the DCT, the skip connections and the head
-// in DOUBLE for the reason given there -- as separate functions, so that a launch can end between any two of them.  The fine-tuner's kernel
-// keeps its one-piece body: it is not recompiled by this file.  keep (double) crosses the launches 4 -> 8 and 8 -> 12 through the clip's workspace slice.
+// The glue around the stacks -- the DCT, the skip connections and the head, in DOUBLE -- is the fine-tuner's (csrc/objproj_train.h ot_dct ..
+// ot_split_relative): its clip body and the phases below call the same functions.  keep (double) crosses the launches 4 -> 8 and 8 -> 12 through the clip's
+// workspace slice.
 // LDS: the fine-tuner's 156 736 B + mu / rstd / the two seam means of 2 x 32 channels in double (2 048 B) = 158 784 B.
 // Parameter gradients: partials[b][.] by plain stores in the flat reference layout, folded over the clips in ascending order (stgcn_ft_fold_kernel): no
 // atomics; two calls give the same bits at any B.
@@ -43,225 +43,6 @@ static_assert(TR_LDS + 64 <= 160 * 1024, "one workgroup per CU");
 inline TrPlan tr_plan(const FtPlan &P) { return idf_stgcn_train::tr_plan_for(P, NP, 2 * KEEP, true); }
 
 __device__ __forceinline__ double *tr_stat_lds(float *sm) { return reinterpret_cast<double *>(reinterpret_cast<char *>(sm) + OT_LDS); }
-
-#define OT_LDS_POINTERS \
-    float *buf = sm; \
-    double *keep = reinterpret_cast<double *>(sm + BUF), *head = keep + KEEP; \
-    double *Dd = head + OT_DCT, *og = head + OT_OG, *col = head + OT_COL, *dcol = head + OT_DCOL, *err = head + OT_ERR, *dres = head + OT_DRES; \
-    const int tid = threadIdx.x, T = op.T, past = op.past_len; \
-    (void)buf; (void)keep; (void)Dd; (void)og; (void)col; (void)dcol; (void)err; (void)dres; (void)tid; (void)T; (void)past;
-
-__device__ __forceinline__ float *ot_red(float *sm) { return reinterpret_cast<float *>(reinterpret_cast<double *>(sm + BUF) + KEEP + OT_HEAD); }
-
-// the orthonormal DCT-II matrix Dd[k][t], k < NP (numpy's expression order); the IDCT is its transpose
-__device__ inline void ot_dct(float *sm, const idf_objproj &op) {
-    OT_LDS_POINTERS
-    for (int i = tid; i < NP * T; i += NTHR) {
-        const int k = i / T, t = i - k * T;
-        Dd[i] = sqrt((k == 0 ? 1.0 : 2.0) / (double)T) * cos(M_PI * ((double)t + 0.5) * (double)k / (double)T);
-    }
-    __syncthreads();
-}
-
-// the DCT matrix, the object's DCT coefficients og, the relative stack's input -> buf and keep[.][.][1 + p]
-__device__ inline void ot_inputs(float *sm, const idf_objproj &op, const OtArgs &a, int B, int b) {
-    OT_LDS_POINTERS
-    ot_dct(sm, op);
-    // object DCT coefficients og[c][k] over the idx_pad frames (the future frames repeat the last past frame)
-    for (int i = tid; i < CH * NP; i += NTHR) {
-        const int c = i / NP, k = i - c * NP;
-        double v = 0.0;
-        for (int t = 0; t < T; ++t) v += Dd[k * T + t] * (double)ot_pose_at(a, B, b, min(t, past - 1), c);
-        og[i] = v;
-    }
-    __syncthreads();
-    // the relative stack's input rel[c][k][p] -> buf (67 nodes) and keep[.][.][1 + p]
-    for (int i = tid; i < CH * NP * NM; i += NTHR) {
-        const int c = i / (NP * NM), r = i - c * NP * NM, k = r / NM, p = r - k * NM;
-        double v = og[c * NP + k];
-        if (c >= 6) {
-            double h = 0.0;
-            for (int t = 0; t < T; ++t) h += Dd[k * T + t] * (double)ot_marker_at(a, B, b, min(t, past - 1), p, c - 6);
-            v -= h;
-        }
-        buf[i] = (float)v;
-        keep[c * PLANE + k * MAXN + 1 + p] = v;
-    }
-    __syncthreads();
-}
-
-// buf = the relative stack's output: keep[.][.][1 + p] = rel + stack(rel) (+ the DCT of the markers over ALL frames in the translation channels)
-__device__ inline void ot_join_relative(float *sm, const idf_objproj &op, const OtArgs &a, int B, int b) {
-    OT_LDS_POINTERS
-    for (int i = tid; i < CH * NP * NM; i += NTHR) {
-        const int c = i / (NP * NM), r = i - c * NP * NM, k = r / NM, p = r - k * NM;
-        double *kp = keep + c * PLANE + k * MAXN + 1 + p;
-        double v = *kp + (double)buf[i];
-        if (c >= 6) {
-            double h = 0.0;
-            for (int t = 0; t < T; ++t) h += Dd[k * T + t] * (double)ot_marker_at(a, B, b, t, p, c - 6);
-            v += h;
-        }
-        *kp = v;
-    }
-    __syncthreads();
-}
-
-// the object-only stack's input (1 node): buf = og
-__device__ inline void ot_object_input(float *sm, const idf_objproj &op) {
-    OT_LDS_POINTERS
-    for (int i = tid; i < CH * NP; i += NTHR) buf[i] = (float)og[i];
-    __syncthreads();
-}
-
-// buf = the object-only stack's output: keep[.][.][0] = og + stack(og); then buf = keep, the joint stack's input over the 68 nodes
-__device__ inline void ot_join_object(float *sm, const idf_objproj &op) {
-    OT_LDS_POINTERS
-    for (int i = tid; i < CH * NP; i += NTHR) {
-        const int c = i / NP, k = i - c * NP;
-        keep[c * PLANE + k * MAXN] = og[i] + (double)buf[i];
-    }
-    __syncthreads();
-    for (int i = tid; i < KEEP; i += NTHR) buf[i] = (float)keep[i];
-    __syncthreads();
-}
-
-// buf = the joint stack's output: keep += buf (its skip connection); node selection, one IDCT, the prediction error, the clip's 8 sums of squares and the
-// loss gradient on the prediction -> dres.  nodes: [B] the node of every clip, or null: the reference's eval branch.  -> the node (-1: the mean)
-__device__ inline int ot_head(float *sm, const idf_objproj &op, const OtArgs &a, const int32_t *nodes, int B, int b) {
-    OT_LDS_POINTERS
-    __shared__ int pick_s;
-    for (int i = tid; i < KEEP; i += NTHR) keep[i] += (double)buf[i];
-    // node selection (correction_smpl.py:122-136): -1 = the mean over the nodes
-    if (tid == 0) {
-        int pick = -1;
-        if (!a.initialize) {
-            if (nodes) {
-                pick = min(max(nodes[b], 0), MAXN - 1);
-            } else {
-                const float *bonus = op.arena + op.hand_bonus;
-                long csum = 0;
-                float best = -1.f;
-                int bi = 0;
-                for (int p = 0; p < NM; ++p) {
-                    const int cv = a.contact[(size_t)b * NM + p];
-                    csum += cv;
-                    const float sc = (float)cv + bonus[p];
-                    if (sc > best) { best = sc; bi = p; }
-                }
-                pick = csum > 0 ? 1 + bi : 0;
-            }
-        }
-        pick_s = pick;
-    }
-    __syncthreads();
-    const int pick = pick_s;
-    for (int i = tid; i < CH * NP; i += NTHR) {
-        const double *row = keep + (i / NP) * PLANE + (i % NP) * MAXN;
-        double v;
-        if (pick < 0) {
-            v = 0.0;
-            for (int n = 0; n < MAXN; ++n) v += row[n];
-            v /= (double)MAXN;
-        } else {
-            v = row[pick];
-        }
-        col[i] = v;
-    }
-    __syncthreads();
-    for (int i = tid; i < T * CH; i += NTHR) {
-        const int t = i / CH, c = i - t * CH;
-        double v = 0.0;
-        for (int k = 0; k < NP; ++k) v += Dd[k * T + t] * col[c * NP + k];
-        err[i] = v - (double)ot_pose_at(a, B, b, t, c);
-    }
-    __syncthreads();
-    // ================= the clip's 8 sums of squares =================
-    if (tid < 8) {
-        // term tid: rot (channels 0..5) when even, nonrot (6..8) when odd; 0,1 past  2,3 future  4,5 past velocity  6,7 future velocity
-        const int c0 = (tid & 1) ? 6 : 0, c1 = (tid & 1) ? CH : 6, kind = tid >> 1;
-        double acc = 0.0;
-        for (int t = 0; t < T; ++t) {
-            const bool in = (kind == 0 || kind == 2) ? t < past : t >= past;
-            if (!in) continue;
-            for (int c = c0; c < c1; ++c) {
-                double v = err[t * CH + c];
-                if (kind == 2) v = err[(t + 1) * CH + c] - v;
-                if (kind == 3) v = v - err[(t - 1) * CH + c];
-                acc += v * v;
-            }
-        }
-        a.loss_part[(size_t)b * 8 + tid] = (float)acc;
-    }
-    // ================= loss gradient on the prediction =================
-    for (int i = tid; i < T * CH; i += NTHR) {
-        const int t = i / CH, c = i - t * CH, nr = c < 6 ? 0 : 1;
-        const double e = err[i];
-        double g = (double)(t < past ? a.coef[nr] : a.coef[2 + nr]) * e;
-        // past velocity d_s = e[s+1] - e[s], s = 0 .. past-1
-        double vp = 0.0;
-        if (t >= 1 && t - 1 < past) vp += e - err[(t - 1) * CH + c];
-        if (t < past) vp -= err[(t + 1) * CH + c] - e;
-        g += (double)a.coef[4 + nr] * vp;
-        // future velocity d_s = e[s] - e[s-1], s = past .. T-1
-        double vf = 0.0;
-        if (t >= past) vf += e - err[(t - 1) * CH + c];
-        if (t + 1 >= past && t + 1 < T) vf -= err[(t + 1) * CH + c] - e;
-        g += (double)a.coef[6 + nr] * vf;
-        if (a.d_obj_pred) g += (double)a.d_obj_pred[((size_t)t * B + b) * CH + c];
-        dres[i] = g;
-    }
-    __syncthreads();
-    return pick;
-}
-
-// IDCT transposed: dcol[c][k] = sum_t Dd[k][t] dres[t][c]; the selection: the mean hands every node 1/68, a selected node takes all and the others
-// EXACTLY 0.  -> keep and buf (the joint stack's output gradient)
-__device__ inline void ot_head_bwd(float *sm, const idf_objproj &op, int pick) {
-    OT_LDS_POINTERS
-    for (int i = tid; i < CH * NP; i += NTHR) {
-        const int c = i / NP, k = i - c * NP;
-        double v = 0.0;
-        for (int t = 0; t < T; ++t) v += Dd[k * T + t] * dres[t * CH + c];
-        dcol[i] = v;
-    }
-    __syncthreads();
-    for (int i = tid; i < KEEP; i += NTHR) {
-        const int c = i / PLANE, r = i - c * PLANE, k = r / MAXN, n = r - k * MAXN;
-        const double d = dcol[c * NP + k];
-        const double v = pick < 0 ? d / (double)MAXN : n == pick ? d : 0.0;
-        keep[i] = v;
-        buf[i] = (float)v;
-    }
-    __syncthreads();
-}
-
-// buf = the joint stack's input gradient: keep += buf (its skip connection); then buf = node 0, the object-only stack's output gradient (that stack's own
-// skip connection ends at the input)
-__device__ inline void ot_split_object(float *sm) {
-    float *buf = sm;
-    double *keep = reinterpret_cast<double *>(sm + BUF);
-    const int tid = threadIdx.x;
-    for (int i = tid; i < KEEP; i += NTHR) keep[i] += (double)buf[i];
-    __syncthreads();
-    for (int i = tid; i < CH * NP; i += NTHR) {
-        const int c = i / NP, k = i - c * NP;
-        buf[i] = (float)keep[c * PLANE + k * MAXN];
-    }
-    __syncthreads();
-}
-
-// buf = nodes 1.., the relative stack's output gradient
-__device__ inline void ot_split_relative(float *sm) {
-    float *buf = sm;
-    const double *keep = reinterpret_cast<const double *>(sm + BUF);
-    const int tid = threadIdx.x;
-    for (int i = tid; i < CH * NP * NM; i += NTHR) {
-        const int c = i / (NP * NM), r = i - c * NP * NM, k = r / NM, p = r - k * NM;
-        buf[i] = (float)keep[c * PLANE + k * MAXN + 1 + p];
-    }
-    __syncthreads();
-}
 
 __device__ inline void tr_keep_copy(double *dst, const double *src) {
     for (int i = threadIdx.x; i < KEEP; i += NTHR) dst[i] = src[i];

@@ -1,7 +1,7 @@
 // Training of the SMPL contact-frame correction predictor with batch statistics, dropout and given contact nodes: launchers of the phase kernel
 // (csrc/objproj_bn_train.h) and of the kernels around it -- the mask generator and the batch statistics / running-buffer update (csrc/stgcn_bn_train.h), the
 // fold of the per-clip partials in ascending clip order (csrc/stgcn_train.h).  Adam and the re-fold are the fine-tuner's interdiff_correction_finetune_step
-// (csrc/objproj_train.hip).  A translation unit of its own: the fine-tuner's kernels are compiled from what they were compiled from before.
+// (csrc/objproj_train.hip).  A translation unit of its own, next to the fine-tuner's.
 #include <math.h>
 #include "objproj_bn_train.h"
 
@@ -15,30 +15,12 @@ __global__ __launch_bounds__(NTHR) void objproj_tr_phase_kernel(const idf_objpro
     tr_phase_body(sm, op, plan, tp, a, t, nodes, B, blockIdx.x, phase);
 }
 
-// workspace (floats): partials [B][n_param] | loss_part [B][8] | clips [B][ws_clip] | statp, dyp [B][TR_SEAM] doubles | masks [B][mask_clip] bytes
-struct TrWs {
-    size_t partials, loss_part, clips, statp, dyp, masks, total;
-};
-TrWs tr_ws(const FtPlan &P, const TrPlan &T, int B) {
-    TrWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
-    w.partials = take((size_t)B * P.n_param);
-    w.loss_part = take((size_t)B * 8);
-    w.clips = take((size_t)B * T.ws_clip);
-    w.statp = take((size_t)B * TR_SEAM * 2);
-    w.dyp = take((size_t)B * TR_SEAM * 2);
-    w.masks = take(((size_t)B * T.mask_clip + 3) / 4);
-    w.total = o;
-    return w;
-}
-
 }  // namespace
 
 extern "C" size_t interdiff_correction_train_workspace_bytes(const idf_objproj *op, int32_t B) {
     if (B < 1 || ot_check_widths(op) != IDF_OK) return 0;
     const FtPlan P = ot_plan(op->cin, op->cout);
-    return tr_ws(P, tr_plan(P), B).total * sizeof(float);
+    return tr_ws(P, tr_plan(P), B, TR_SEAM).total * sizeof(float);
 }
 
 extern "C" int interdiff_correction_train_masks(const idf_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
@@ -61,46 +43,21 @@ extern "C" int interdiff_correction_train_grads(const idf_objproj *op, const flo
     if (!(p_drop >= 0.0 && p_drop < 1.0) || !(momentum >= 0.0 && momentum <= 1.0) || (update_running != 0 && update_running != 1)) return IDF_E_INVAL;
     const FtPlan P = ot_plan(op->cin, op->cout);
     const TrPlan TP = tr_plan(P);
-    const TrWs W = tr_ws(P, TP, B);
+    const TrWs W = tr_ws(P, TP, B, TR_SEAM);
     if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
     float *base = static_cast<float *>(ws);
     hipStream_t st = idf_stream(stream);
-    const int past = op->past_len, fut = T - past;
-    LossK lk;
     OtArgs a{};
-    for (int k = 0; k < 8; ++k) {
-        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 6;
-        const double n = frames * (double)B * width;
-        lk.w[k] = weights8[k];
-        lk.inv_n[k] = (float)(1.0 / n);
-        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
-    }
+    const LossK lk = ft_loss_constants(weights8, op->past_len, T, B, 6, a.coef);
     a.obj_angles = obj_angles; a.obj_trans = obj_trans; a.markers = markers; a.contact = contact; a.d_obj_pred = d_obj_pred;
     a.partials = base + W.partials;
     a.loss_part = base + W.loss_part;
     a.ws_clips = base + W.clips;
     a.initialize = initialize != 0;
-    TrArgs t{};
-    t.params = params;
-    t.statp = reinterpret_cast<double *>(base + W.statp);
-    t.dyp = reinterpret_cast<double *>(base + W.dyp);
-    t.scale = (float)(1.0 / (1.0 - p_drop));
-    t.masks = masks;
     static std::atomic<uint64_t> lds_ok{0};
     if (idf_opt_in_lds(reinterpret_cast<const void *>(objproj_tr_phase_kernel), (int)TR_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
-    idf_prof_mark(IDF_K_OTHER, st);
-    if (!masks && p_drop > 0.0) {                       // the generator's masks go through the same buffer layout as injected ones
-        uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
-        stgcn_tr_launch_masks<NP>(P, TP, B, p_drop, seed, step, mb, st);
-        t.masks = mb;
-    }
-    for (int phase = 0; phase < TR_PHASES; ++phase)
-        hipLaunchKernelGGL(objproj_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, P, TP, a, t, nodes, B, phase);
-    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
-                       lk, grads, out9);
-    if (batch_stats || update_running)
-        hipLaunchKernelGGL((stgcn_tr_stats_kernel<Tr, NP, MAXC>), dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_tr_launch_grads<Tr, NP, MAXC>(P, TP, W, base, B, lk, params, bn, p_drop, masks, seed, step, momentum, update_running, out9, grads, batch_stats, st,
+                                               [&](const TrArgs &t, int phase) {
+                                                   hipLaunchKernelGGL(objproj_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, P, TP, a, t, nodes, B, phase);
+                                               });
 }

@@ -9,7 +9,7 @@
 //      layer saves to the clip's workspace slice: its input planes x, (joint stack) the temporally mixed planes u, the mixed planes g the tcn convolution
 //      reads, and the pre-activation h.  Node selection as the reference's eval branch: initialize -> the mean over the 68 nodes (taken in coefficient space,
 //      it commutes with the IDCT), otherwise node 0 (no contact in the clip) or node 1 + argmax(contact + hand bonus); one IDCT of that column.  Everything
-//      AROUND the stacks -- DCT, skip connections, selection, IDCT -- runs in double (see ot_clip_body).
+//      AROUND the stacks -- DCT, skip connections, selection, IDCT -- runs in double (see ot_dct .. ot_split_relative).
 //   2. LOSS GRADIENT on the clip's [T][9] prediction, in double: the 8 MSE means are over the batch, so their normalisers are constants (coef[k] = 2 w_k / n_k);
 //      the velocity terms couple adjacent frames of the same clip only.  d_obj_pred [T][B][9], when given, is ADDED to it: the gradient of whatever else the
 //      caller's objective reads from the prediction (the seam of the contact / penetration terms, whose kernel is not part of this file).  The clip's 8 sums
@@ -111,30 +111,36 @@ __device__ inline void ot_stack_bwd(float *dy, float *red, const idf_objproj &op
     }
 }
 
-// the whole clip: forward with saves, loss sums, loss gradient, backward.  All NTHR threads call it together; sm: OT_LDS bytes = buf [BUF] floats |
-// keep [KEEP] doubles | the head's vectors [OT_HEAD] doubles | red [OT_RED] floats.
-// The SKIP PATH and the HEAD run in DOUBLE: the DCT matrix (formed here from its definition, get_dct_matrix of model/correction_smpl.py:55-67; its inverse
-// is its transpose), the DCT of the inputs, the three skip connections, the selection, the IDCT, the prediction error and the loss gradient.  The
-// prediction is the (padded) past pose put through DCT and IDCT plus a small correction, and the loss gradient is proportional to prediction - target, a
-// difference ~1e-2 of O(1) values: fp32 roundings of the DCT matrices and of the skip sums alone put the PReLU-slope gradient of st_gcnns.3 at 2e-5 of its
-// fp64 value, twice its gate.  The stacks read the skip path rounded to fp32 once and run in compensated fp32.
-__device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, const FtPlan &plan, const OtArgs &a, int B, int b) {
-    float *buf = sm;
-    double *keep = reinterpret_cast<double *>(sm + BUF), *head = keep + KEEP;
-    double *Dd = head + OT_DCT, *og = head + OT_OG, *col = head + OT_COL, *dcol = head + OT_DCOL, *err = head + OT_ERR, *dres = head + OT_DRES;
-    float *red = reinterpret_cast<float *>(head + OT_HEAD);
-    __shared__ int pick_s;
-    const int tid = threadIdx.x, T = op.T, past = op.past_len;
-    float *ws = a.ws_clips + (size_t)b * plan.ws_clip, *G = ws + plan.ws_clip - 2 * BUF, *X = G + BUF;
-    float *part = a.partials + (size_t)b * plan.n_param;
+// ---- the clip's glue around the stacks, one function per section so that the train-mode phases (csrc/objproj_bn_train.h) can end a launch between any
+// two of them.  sm: the LDS = buf [BUF] floats | keep [KEEP] doubles | the head's vectors [OT_HEAD] doubles | red [OT_RED] floats.
+// The SKIP PATH and the HEAD run in DOUBLE: the DCT matrix (formed from its definition, get_dct_matrix of model/correction_smpl.py:55-67; its inverse is its
+// transpose), the DCT of the inputs, the three skip connections, the selection, the IDCT, the prediction error and the loss gradient.  The prediction is
+// the (padded) past pose put through DCT and IDCT plus a small correction, and the loss gradient is proportional to prediction - target, a difference ~1e-2
+// of O(1) values: fp32 roundings of the DCT matrices and of the skip sums alone put the PReLU-slope gradient of st_gcnns.3 at 2e-5 of its fp64 value, twice
+// its gate.  The stacks read the skip path rounded to fp32 once and run in compensated fp32.
+#define OT_LDS_POINTERS \
+    float *buf = sm; \
+    double *keep = reinterpret_cast<double *>(sm + BUF), *head = keep + KEEP; \
+    double *Dd = head + OT_DCT, *og = head + OT_OG, *col = head + OT_COL, *dcol = head + OT_DCOL, *err = head + OT_ERR, *dres = head + OT_DRES; \
+    const int tid = threadIdx.x, T = op.T, past = op.past_len; \
+    (void)buf; (void)keep; (void)Dd; (void)og; (void)col; (void)dcol; (void)err; (void)dres; (void)tid; (void)T; (void)past;
 
-    // ================= forward =================
-    // the orthonormal DCT-II matrix Dd[k][t], k < NP (numpy's expression order); the IDCT is its transpose
+__device__ __forceinline__ float *ot_red(float *sm) { return reinterpret_cast<float *>(reinterpret_cast<double *>(sm + BUF) + KEEP + OT_HEAD); }
+
+// the orthonormal DCT-II matrix Dd[k][t], k < NP (numpy's expression order); the IDCT is its transpose
+__device__ inline void ot_dct(float *sm, const idf_objproj &op) {
+    OT_LDS_POINTERS
     for (int i = tid; i < NP * T; i += NTHR) {
         const int k = i / T, t = i - k * T;
         Dd[i] = sqrt((k == 0 ? 1.0 : 2.0) / (double)T) * cos(M_PI * ((double)t + 0.5) * (double)k / (double)T);
     }
     __syncthreads();
+}
+
+// the DCT matrix, the object's DCT coefficients og, the relative stack's input -> buf and keep[.][.][1 + p]
+__device__ inline void ot_inputs(float *sm, const idf_objproj &op, const OtArgs &a, int B, int b) {
+    OT_LDS_POINTERS
+    ot_dct(sm, op);
     // object DCT coefficients og[c][k] over the idx_pad frames (the future frames repeat the last past frame)
     for (int i = tid; i < CH * NP; i += NTHR) {
         const int c = i / NP, k = i - c * NP;
@@ -156,8 +162,11 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         keep[c * PLANE + k * MAXN + 1 + p] = v;
     }
     __syncthreads();
-    ot_stack_fwd(buf, op, plan, 0, NM, ws);
-    // keep[.][.][1 + p] = rel + stack(rel) (+ the DCT of the markers over ALL frames in the translation channels)
+}
+
+// buf = the relative stack's output: keep[.][.][1 + p] = rel + stack(rel) (+ the DCT of the markers over ALL frames in the translation channels)
+__device__ inline void ot_join_relative(float *sm, const idf_objproj &op, const OtArgs &a, int B, int b) {
+    OT_LDS_POINTERS
     for (int i = tid; i < CH * NP * NM; i += NTHR) {
         const int c = i / (NP * NM), r = i - c * NP * NM, k = r / NM, p = r - k * NM;
         double *kp = keep + c * PLANE + k * MAXN + 1 + p;
@@ -170,35 +179,52 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         *kp = v;
     }
     __syncthreads();
-    // the object-only stack (1 node): keep[.][.][0] = og + stack(og)
+}
+
+// the object-only stack's input (1 node): buf = og
+__device__ inline void ot_object_input(float *sm, const idf_objproj &op) {
+    OT_LDS_POINTERS
     for (int i = tid; i < CH * NP; i += NTHR) buf[i] = (float)og[i];
     __syncthreads();
-    ot_stack_fwd(buf, op, plan, 1, 1, ws);
+}
+
+// buf = the object-only stack's output: keep[.][.][0] = og + stack(og); then buf = keep, the joint stack's input over the 68 nodes
+__device__ inline void ot_join_object(float *sm, const idf_objproj &op) {
+    OT_LDS_POINTERS
     for (int i = tid; i < CH * NP; i += NTHR) {
         const int c = i / NP, k = i - c * NP;
         keep[c * PLANE + k * MAXN] = og[i] + (double)buf[i];
     }
     __syncthreads();
-    // the joint stack over the 68 nodes and its skip connection
     for (int i = tid; i < KEEP; i += NTHR) buf[i] = (float)keep[i];
     __syncthreads();
-    ot_stack_fwd(buf, op, plan, 2, MAXN, ws);
+}
+
+// buf = the joint stack's output: keep += buf (its skip connection); node selection, one IDCT, the prediction error, the clip's 8 sums of squares and the
+// loss gradient on the prediction -> dres.  nodes: [B] the node of every clip, or null: the reference's eval branch.  -> the node (-1: the mean)
+__device__ inline int ot_head(float *sm, const idf_objproj &op, const OtArgs &a, const int32_t *nodes, int B, int b) {
+    OT_LDS_POINTERS
+    __shared__ int pick_s;
     for (int i = tid; i < KEEP; i += NTHR) keep[i] += (double)buf[i];
-    // node selection (correction_smpl.py:122-136, eval branch): -1 = the mean over the nodes
+    // node selection (correction_smpl.py:122-136): -1 = the mean over the nodes
     if (tid == 0) {
         int pick = -1;
         if (!a.initialize) {
-            const float *bonus = op.arena + op.hand_bonus;
-            long csum = 0;
-            float best = -1.f;
-            int bi = 0;
-            for (int p = 0; p < NM; ++p) {
-                const int cv = a.contact[(size_t)b * NM + p];
-                csum += cv;
-                const float sc = (float)cv + bonus[p];
-                if (sc > best) { best = sc; bi = p; }
+            if (nodes) {
+                pick = min(max(nodes[b], 0), MAXN - 1);
+            } else {
+                const float *bonus = op.arena + op.hand_bonus;
+                long csum = 0;
+                float best = -1.f;
+                int bi = 0;
+                for (int p = 0; p < NM; ++p) {
+                    const int cv = a.contact[(size_t)b * NM + p];
+                    csum += cv;
+                    const float sc = (float)cv + bonus[p];
+                    if (sc > best) { best = sc; bi = p; }
+                }
+                pick = csum > 0 ? 1 + bi : 0;
             }
-            pick = csum > 0 ? 1 + bi : 0;
         }
         pick_s = pick;
     }
@@ -260,8 +286,13 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         dres[i] = g;
     }
     __syncthreads();
-    // ================= backward =================
-    // IDCT transposed: dcol[c][k] = sum_t Dd[k][t] dres[t][c]
+    return pick;
+}
+
+// IDCT transposed: dcol[c][k] = sum_t Dd[k][t] dres[t][c]; the selection: the mean hands every node 1/68, a selected node takes all and the others
+// EXACTLY 0.  -> keep and buf (the joint stack's output gradient)
+__device__ inline void ot_head_bwd(float *sm, const idf_objproj &op, int pick) {
+    OT_LDS_POINTERS
     for (int i = tid; i < CH * NP; i += NTHR) {
         const int c = i / NP, k = i - c * NP;
         double v = 0.0;
@@ -269,7 +300,6 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         dcol[i] = v;
     }
     __syncthreads();
-    // selection: the mean hands every node 1/68, a selected node takes all and the others EXACTLY 0.  -> keep and buf (the joint stack's output gradient)
     for (int i = tid; i < KEEP; i += NTHR) {
         const int c = i / PLANE, r = i - c * PLANE, k = r / MAXN, n = r - k * MAXN;
         const double d = dcol[c * NP + k];
@@ -278,9 +308,14 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         buf[i] = (float)v;
     }
     __syncthreads();
-    ot_stack_bwd(buf, red, op, plan, 2, MAXN, ws, G, X, part);
-    // buf = the joint stack's input gradient: keep += buf (its skip connection); node 0 is the object-only stack's output gradient (that stack's own skip
-    // connection ends at the input), nodes 1.. the relative stack's
+}
+
+// buf = the joint stack's input gradient: keep += buf (its skip connection); then buf = node 0, the object-only stack's output gradient (that stack's own
+// skip connection ends at the input)
+__device__ inline void ot_split_object(float *sm) {
+    float *buf = sm;
+    double *keep = reinterpret_cast<double *>(sm + BUF);
+    const int tid = threadIdx.x;
     for (int i = tid; i < KEEP; i += NTHR) keep[i] += (double)buf[i];
     __syncthreads();
     for (int i = tid; i < CH * NP; i += NTHR) {
@@ -288,13 +323,40 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
         buf[i] = (float)keep[c * PLANE + k * MAXN];
     }
     __syncthreads();
-    ot_stack_bwd(buf, red, op, plan, 1, 1, ws, G, X, part);
+}
+
+// buf = nodes 1.., the relative stack's output gradient
+__device__ inline void ot_split_relative(float *sm) {
+    float *buf = sm;
+    const double *keep = reinterpret_cast<const double *>(sm + BUF);
+    const int tid = threadIdx.x;
     for (int i = tid; i < CH * NP * NM; i += NTHR) {
         const int c = i / (NP * NM), r = i - c * NP * NM, k = r / NM, p = r - k * NM;
         buf[i] = (float)keep[c * PLANE + k * MAXN + 1 + p];
     }
     __syncthreads();
-    ot_stack_bwd(buf, red, op, plan, 0, NM, ws, G, X, part);
 }
+
+// the whole clip: forward with saves, loss sums, loss gradient, backward.  All NTHR threads call it together; sm: OT_LDS bytes.  The node is the
+// reference's eval branch (ot_head with nodes = nullptr).
+__device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, const FtPlan &plan, const OtArgs &a, int B, int b) {
+    float *ws = a.ws_clips + (size_t)b * plan.ws_clip, *G = ws + plan.ws_clip - 2 * BUF, *X = G + BUF;
+    float *part = a.partials + (size_t)b * plan.n_param, *red = ot_red(sm);
+    ot_inputs(sm, op, a, B, b);
+    ot_stack_fwd(sm, op, plan, 0, NM, ws);
+    ot_join_relative(sm, op, a, B, b);
+    ot_object_input(sm, op);
+    ot_stack_fwd(sm, op, plan, 1, 1, ws);
+    ot_join_object(sm, op);
+    ot_stack_fwd(sm, op, plan, 2, MAXN, ws);
+    const int pick = ot_head(sm, op, a, nullptr, B, b);
+    ot_head_bwd(sm, op, pick);
+    ot_stack_bwd(sm, red, op, plan, 2, MAXN, ws, G, X, part);
+    ot_split_object(sm);
+    ot_stack_bwd(sm, red, op, plan, 1, 1, ws, G, X, part);
+    ot_split_relative(sm);
+    ot_stack_bwd(sm, red, op, plan, 0, NM, ws, G, X, part);
+}
+
 
 }  // namespace idf_objproj_train

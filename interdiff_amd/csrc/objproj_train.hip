@@ -15,39 +15,17 @@ __global__ __launch_bounds__(NTHR) void objproj_ft_clip_kernel(const idf_objproj
     ot_clip_body(sm, op, plan, a, B, blockIdx.x);
 }
 
-// workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]
-struct OtWs {
-    size_t partials, loss_part, gsum, clips, total;
-};
-OtWs ot_ws(const FtPlan &P, int B) {
-    OtWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
-    w.partials = take((size_t)B * P.n_param);
-    w.loss_part = take((size_t)B * 8);
-    w.gsum = take((size_t)P.n_param);
-    w.clips = take((size_t)B * P.ws_clip);
-    w.total = o;
-    return w;
-}
-
 }  // namespace
 
 extern "C" int interdiff_correction_finetune_param_table(const idf_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn) {
     if (!table || !n_param || !n_bn || ot_check_widths(op) != IDF_OK) return IDF_E_INVAL;
-    const FtPlan P = ot_plan(op->cin, op->cout);
-    for (int li = 0; li < 12; ++li) {
-        const int32_t *src = reinterpret_cast<const int32_t *>(&P.L[li]);
-        for (int k = 0; k < FT_TABLE_COLS; ++k) table[li * FT_TABLE_COLS + k] = src[k];
-    }
-    *n_param = P.n_param;
-    *n_bn = P.n_bn;
+    ft_export_table(ot_plan(op->cin, op->cout), table, n_param, n_bn);
     return IDF_OK;
 }
 
 extern "C" size_t interdiff_correction_finetune_workspace_bytes(const idf_objproj *op, int32_t B) {
     if (B < 1 || ot_check_widths(op) != IDF_OK) return 0;
-    return ot_ws(ot_plan(op->cin, op->cout), B).total * sizeof(float);
+    return ft_ws(ot_plan(op->cin, op->cout), B).total * sizeof(float);
 }
 
 extern "C" int interdiff_correction_finetune_grads(const idf_objproj *op, const float *params, const float *bn, const float *obj_angles,
@@ -58,20 +36,12 @@ extern "C" int interdiff_correction_finetune_grads(const idf_objproj *op, const 
     if (!initialize && !contact) return IDF_E_INVAL;
     if (ot_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
     const FtPlan P = ot_plan(op->cin, op->cout);
-    const OtWs W = ot_ws(P, B);
+    const FtWs W = ft_ws(P, B);
     if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
     float *base = static_cast<float *>(ws);
     hipStream_t st = idf_stream(stream);
-    const int past = op->past_len, fut = T - past;
-    LossK lk;
     OtArgs a{};
-    for (int k = 0; k < 8; ++k) {
-        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 6;
-        const double n = frames * (double)B * width;
-        lk.w[k] = weights8[k];
-        lk.inv_n[k] = (float)(1.0 / n);
-        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
-    }
+    const LossK lk = ft_loss_constants(weights8, op->past_len, T, B, 6, a.coef);
     a.obj_angles = obj_angles; a.obj_trans = obj_trans; a.markers = markers; a.contact = contact; a.d_obj_pred = d_obj_pred;
     a.partials = base + W.partials;
     a.loss_part = base + W.loss_part;
@@ -79,14 +49,8 @@ extern "C" int interdiff_correction_finetune_grads(const idf_objproj *op, const 
     a.initialize = initialize != 0;
     static std::atomic<uint64_t> lds_ok{0};
     if (idf_opt_in_lds(reinterpret_cast<const void *>(objproj_ft_clip_kernel), (int)OT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
-    idf_prof_mark(IDF_K_OTHER, st);
-    hipLaunchKernelGGL(objproj_ft_clip_kernel, dim3(B), dim3(NTHR), OT_LDS, st, *op, P, a, B);
-    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
-                       lk, base + W.gsum, out9);
-    hipLaunchKernelGGL(stgcn_ft_convert_kernel<NP>, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_ft_launch_grads<NP>(P, W, base, B, lk, params, bn, out9, grads, st,
+                                     [&] { hipLaunchKernelGGL(objproj_ft_clip_kernel, dim3(B), dim3(NTHR), OT_LDS, st, *op, P, a, B); });
 }
 
 extern "C" int interdiff_correction_finetune_step(const idf_objproj *op, float *arena, float *params, const float *bn, const float *grads, float *exp_avg,
@@ -94,13 +58,6 @@ extern "C" int interdiff_correction_finetune_step(const idf_objproj *op, float *
                                                   void *stream) {
     if (!arena || !params || !bn || !grads || !exp_avg || !exp_avg_sq || step < 1 || ot_check(op, 1) != IDF_OK) return IDF_E_INVAL;
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return IDF_E_INVAL;
-    const FtPlan P = ot_plan(op->cin, op->cout);
-    hipStream_t st = idf_stream(stream);
-    const AdamK k = ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay);
-    idf_prof_mark(IDF_K_OTHER, st);
-    hipLaunchKernelGGL(stgcn_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
-    hipLaunchKernelGGL((stgcn_ft_refold_kernel<NP, VP, idf_objproj>), dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_ft_launch_step<NP, VP>(*op, ot_plan(op->cin, op->cout), arena, params, bn, grads, exp_avg, exp_avg_sq,
+                                        ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay), idf_stream(stream));
 }

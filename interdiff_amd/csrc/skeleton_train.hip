@@ -37,33 +37,11 @@ int ft_check(const idf_skel_objproj *op, int B) {
     return IDF_OK;
 }
 
-// workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]
-struct FtWs {
-    size_t partials, loss_part, gsum, clips, total;
-};
-FtWs ft_ws(const FtPlan &P, int B) {
-    FtWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
-    w.partials = take((size_t)B * P.n_param);
-    w.loss_part = take((size_t)B * 8);
-    w.gsum = take((size_t)P.n_param);
-    w.clips = take((size_t)B * P.ws_clip);
-    w.total = o;
-    return w;
-}
-
 }  // namespace
 
 extern "C" int interdiff_skeleton_finetune_param_table(const idf_skel_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn) {
     if (!table || !n_param || !n_bn || ft_check_widths(op) != IDF_OK) return IDF_E_INVAL;
-    const FtPlan P = ft_plan(op->cin, op->cout);
-    for (int li = 0; li < 12; ++li) {
-        const int32_t *src = reinterpret_cast<const int32_t *>(&P.L[li]);
-        for (int k = 0; k < FT_TABLE_COLS; ++k) table[li * FT_TABLE_COLS + k] = src[k];
-    }
-    *n_param = P.n_param;
-    *n_bn = P.n_bn;
+    ft_export_table(ft_plan(op->cin, op->cout), table, n_param, n_bn);
     return IDF_OK;
 }
 
@@ -82,16 +60,8 @@ extern "C" int interdiff_skeleton_finetune_grads(const idf_skel_objproj *op, con
     if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
     float *base = static_cast<float *>(ws);
     hipStream_t st = idf_stream(stream);
-    const int past = op->past_len, fut = T - past;
-    LossK lk;
     FtArgs a{};
-    for (int k = 0; k < 8; ++k) {
-        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 4;
-        const double n = frames * (double)B * width;
-        lk.w[k] = weights8[k];
-        lk.inv_n[k] = (float)(1.0 / n);
-        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
-    }
+    const LossK lk = ft_loss_constants(weights8, op->past_len, T, B, 4, a.coef);
     a.pose_gt = pose_gt;
     a.partials = base + W.partials;
     a.loss_part = base + W.loss_part;
@@ -100,14 +70,8 @@ extern "C" int interdiff_skeleton_finetune_grads(const idf_skel_objproj *op, con
     s.angles = obj_angles; s.trans = obj_trans; s.human = human_points;
     static std::atomic<uint64_t> lds_ok{0};
     if (idf_opt_in_lds(reinterpret_cast<const void *>(skel_ft_clip_kernel), (int)FT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
-    idf_prof_mark(IDF_K_OTHER, st);
-    hipLaunchKernelGGL(skel_ft_clip_kernel, dim3(B), dim3(NTHR), FT_LDS, st, *op, s, P, a, B);
-    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
-                       lk, base + W.gsum, out9);
-    hipLaunchKernelGGL(stgcn_ft_convert_kernel<NP>, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_ft_launch_grads<NP>(P, W, base, B, lk, params, bn, out9, grads, st,
+                                     [&] { hipLaunchKernelGGL(skel_ft_clip_kernel, dim3(B), dim3(NTHR), FT_LDS, st, *op, s, P, a, B); });
 }
 
 extern "C" int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, float *arena, float *params, const float *bn, const float *grads, float *exp_avg,
@@ -115,15 +79,8 @@ extern "C" int interdiff_skeleton_finetune_step(const idf_skel_objproj *op, floa
                                                 void *stream) {
     if (!arena || !params || !bn || !grads || !exp_avg || !exp_avg_sq || step < 1 || ft_check(op, 1) != IDF_OK) return IDF_E_INVAL;
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return IDF_E_INVAL;
-    const FtPlan P = ft_plan(op->cin, op->cout);
-    hipStream_t st = idf_stream(stream);
-    const AdamK k = ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay);
-    idf_prof_mark(IDF_K_OTHER, st);
-    hipLaunchKernelGGL(stgcn_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
-    hipLaunchKernelGGL((stgcn_ft_refold_kernel<NP, VP, idf_skel_objproj>), dim3(12), dim3(FT_THR), 0, st, *op, P, params, bn, arena);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_ft_launch_step<NP, VP>(*op, ft_plan(op->cin, op->cout), arena, params, bn, grads, exp_avg, exp_avg_sq,
+                                        ft_adam_constants(step, lr, beta1, beta2, eps, weight_decay), idf_stream(stream));
 }
 
 // ================= training with batch statistics and dropout =================
@@ -135,30 +92,12 @@ __global__ __launch_bounds__(NTHR) void skel_tr_phase_kernel(const idf_skel_objp
     tr_phase_body(sm, op, s, plan, tp, a, t, B, blockIdx.x, phase);
 }
 
-// workspace (floats): partials [B][n_param] | loss_part [B][8] | clips [B][ws_clip] | statp, dyp [B][TR_SEAM] doubles | masks [B][mask_clip] bytes
-struct TrWs {
-    size_t partials, loss_part, clips, statp, dyp, masks, total;
-};
-TrWs tr_ws(const FtPlan &P, const TrPlan &T, int B) {
-    TrWs w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) / 64 * 64; return at; };
-    w.partials = take((size_t)B * P.n_param);
-    w.loss_part = take((size_t)B * 8);
-    w.clips = take((size_t)B * T.ws_clip);
-    w.statp = take((size_t)B * TR_SEAM * 2);
-    w.dyp = take((size_t)B * TR_SEAM * 2);
-    w.masks = take(((size_t)B * T.mask_clip + 3) / 4);
-    w.total = o;
-    return w;
-}
-
 }  // namespace
 
 extern "C" size_t interdiff_skeleton_train_workspace_bytes(const idf_skel_objproj *op, int32_t B) {
     if (!op || B < 1 || ft_check_widths(op) != IDF_OK) return 0;
     const FtPlan P = ft_plan(op->cin, op->cout);
-    return tr_ws(P, tr_plan(P), B).total * sizeof(float);
+    return tr_ws(P, tr_plan(P), B, TR_SEAM).total * sizeof(float);
 }
 
 extern "C" int interdiff_skeleton_train_masks(const idf_skel_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
@@ -179,47 +118,22 @@ extern "C" int interdiff_skeleton_train_grads(const idf_skel_objproj *op, const 
     if (!(p_drop >= 0.0 && p_drop < 1.0) || !(momentum >= 0.0 && momentum <= 1.0) || (update_running != 0 && update_running != 1)) return IDF_E_INVAL;
     const FtPlan P = ft_plan(op->cin, op->cout);
     const TrPlan TP = tr_plan(P);
-    const TrWs W = tr_ws(P, TP, B);
+    const TrWs W = tr_ws(P, TP, B, TR_SEAM);
     if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
     float *base = static_cast<float *>(ws);
     hipStream_t st = idf_stream(stream);
-    const int past = op->past_len, fut = T - past;
-    LossK lk;
     FtArgs a{};
-    for (int k = 0; k < 8; ++k) {
-        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : fut, width = (k & 1) ? 3 : 4;
-        const double n = frames * (double)B * width;
-        lk.w[k] = weights8[k];
-        lk.inv_n[k] = (float)(1.0 / n);
-        a.coef[k] = (float)(2.0 * (double)weights8[k] / n);
-    }
+    const LossK lk = ft_loss_constants(weights8, op->past_len, T, B, 4, a.coef);
     a.pose_gt = pose_gt;
     a.partials = base + W.partials;
     a.loss_part = base + W.loss_part;
     a.ws_clips = base + W.clips;
     Src s{};
     s.angles = obj_angles; s.trans = obj_trans; s.human = human_points;
-    TrArgs t{};
-    t.params = params;
-    t.statp = reinterpret_cast<double *>(base + W.statp);
-    t.dyp = reinterpret_cast<double *>(base + W.dyp);
-    t.scale = (float)(1.0 / (1.0 - p_drop));
-    t.masks = masks;
     static std::atomic<uint64_t> lds_ok{0};
     if (idf_opt_in_lds(reinterpret_cast<const void *>(skel_tr_phase_kernel), (int)TR_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
-    idf_prof_mark(IDF_K_OTHER, st);
-    if (!masks && p_drop > 0.0) {                       // the generator's masks go through the same buffer layout as injected ones
-        uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
-        stgcn_tr_launch_masks<NP>(P, TP, B, p_drop, seed, step, mb, st);
-        t.masks = mb;
-    }
-    for (int phase = 0; phase < TR_PHASES; ++phase)
-        hipLaunchKernelGGL(skel_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, s, P, TP, a, t, B, phase);
-    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
-                       lk, grads, out9);
-    if (batch_stats || update_running)
-        hipLaunchKernelGGL((stgcn_tr_stats_kernel<Tr, NP, MAXC>), dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
-    idf_prof_mark(-1, st);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    return stgcn_tr_launch_grads<Tr, NP, MAXC>(P, TP, W, base, B, lk, params, bn, p_drop, masks, seed, step, momentum, update_running, out9, grads, batch_stats, st,
+                                               [&](const TrArgs &t, int phase) {
+                                                   hipLaunchKernelGGL(skel_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, s, P, TP, a, t, B, phase);
+                                               });
 }

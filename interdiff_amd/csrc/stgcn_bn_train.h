@@ -365,6 +365,49 @@ inline void stgcn_tr_launch_masks(const FtPlan &P, const TrPlan &T, int B, doubl
     hipLaunchKernelGGL(stgcn_tr_masks_kernel<NP>, dim3((unsigned)((widest + FT_THR - 1) / FT_THR), 12), dim3(FT_THR), 0, st, P, T, B, (float)p, seed, step, out);
 }
 
+// a trainer's workspace (floats): partials [B][n_param] | loss_part [B][8] | clips [B][ws_clip] | statp, dyp [B][seam] doubles | masks [B][mask_clip] bytes
+struct TrWs {
+    size_t partials, loss_part, clips, statp, dyp, masks, total;
+};
+inline TrWs tr_ws(const FtPlan &P, const TrPlan &T, int B, int seam) {
+    TrWs w{};
+    w.partials = ft_ws_take(w.total, (size_t)B * P.n_param);
+    w.loss_part = ft_ws_take(w.total, (size_t)B * 8);
+    w.clips = ft_ws_take(w.total, (size_t)B * T.ws_clip);
+    w.statp = ft_ws_take(w.total, (size_t)B * seam * 2);
+    w.dyp = ft_ws_take(w.total, (size_t)B * seam * 2);
+    w.masks = ft_ws_take(w.total, ((size_t)B * T.mask_clip + 3) / 4);
+    return w;
+}
+
+// a trainer's gradient call: the generator's masks when none are injected, the TR_PHASES launches -- phase(t, k) launches phase k with the TrArgs t on st --
+// the fold over the clips, and the batch statistics / running-buffer update when asked for
+template <class TR, int NP, int MAXC, class Phase>
+inline int stgcn_tr_launch_grads(const FtPlan &P, const TrPlan &TP, const TrWs &W, float *base, int B, const LossK &lk, const float *params, float *bn,
+                                 double p_drop, const uint8_t *masks, uint64_t seed, uint64_t step, double momentum, int update_running, float *out9,
+                                 float *grads, float *batch_stats, hipStream_t st, Phase &&phase) {
+    TrArgs t{};
+    t.params = params;
+    t.statp = reinterpret_cast<double *>(base + W.statp);
+    t.dyp = reinterpret_cast<double *>(base + W.dyp);
+    t.scale = (float)(1.0 / (1.0 - p_drop));
+    t.masks = masks;
+    idf_prof_mark(IDF_K_OTHER, st);
+    if (!masks && p_drop > 0.0) {                       // the generator's masks go through the same buffer layout as injected ones
+        uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
+        stgcn_tr_launch_masks<NP>(P, TP, B, p_drop, seed, step, mb, st);
+        t.masks = mb;
+    }
+    for (int k = 0; k < TR_PHASES; ++k) phase(t, k);
+    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+                       lk, grads, out9);
+    if (batch_stats || update_running)
+        hipLaunchKernelGGL((stgcn_tr_stats_kernel<TR, NP, MAXC>), dim3(12), dim3(2 * MAXC), 0, st, P, t.statp, B, momentum, update_running, bn, batch_stats);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
 }  // namespace
 
 }  // namespace idf_stgcn_train

@@ -4,7 +4,8 @@
 // fold of the per-clip partials in ascending clip order, the conversion of the folded convolutions' gradients to the reference parameters, Adam
 // (torch.optim.Adam's order of operations) on the fp32 master parameters, and the re-fold into the arena the inference kernels read.
 // The layer functions are members of StgcnFt<NP, VP> so that each trainer instantiates them for its own geometry; the kernels sit in an unnamed
-// namespace: every translation unit that includes this header launches its own copy.
+// namespace: every translation unit that includes this header launches its own copy.  Behind them, the host side both predictors' launchers share: the
+// table export, the workspace layout, the loss constants, and the launch sequences around a clip kernel (ft_export_table .. stgcn_ft_launch_step).
 #pragma once
 #include <math.h>
 #include "stgcn.h"
@@ -431,6 +432,77 @@ __global__ __launch_bounds__(FT_THR) void stgcn_ft_refold_kernel(const OP op, co
         blk += coutp;
     }
     if (tid == 0) blk[0] = params[L.pr];
+}
+
+// ---- host: what the launchers of both predictors do around their clip kernel (argument checks stay with each entry point)
+// the first FT_TABLE_COLS ints of every layer of the plan, and its two counts
+inline void ft_export_table(const FtPlan &P, int32_t *table, int32_t *n_param, int32_t *n_bn) {
+    for (int li = 0; li < 12; ++li) {
+        const int32_t *src = reinterpret_cast<const int32_t *>(&P.L[li]);
+        for (int k = 0; k < FT_TABLE_COLS; ++k) table[li * FT_TABLE_COLS + k] = src[k];
+    }
+    *n_param = P.n_param;
+    *n_bn = P.n_bn;
+}
+
+// a workspace region of n floats at the running offset o, regions 64-float aligned
+inline size_t ft_ws_take(size_t &o, size_t n) {
+    const size_t at = o;
+    o += (n + 63) / 64 * 64;
+    return at;
+}
+
+// a fine-tuner's workspace (floats): partials [B][n_param] | loss_part [B][8] | gsum [n_param] | clips [B][ws_clip]
+struct FtWs {
+    size_t partials, loss_part, gsum, clips, total;
+};
+inline FtWs ft_ws(const FtPlan &P, int B) {
+    FtWs w{};
+    w.partials = ft_ws_take(w.total, (size_t)B * P.n_param);
+    w.loss_part = ft_ws_take(w.total, (size_t)B * 8);
+    w.gsum = ft_ws_take(w.total, (size_t)P.n_param);
+    w.clips = ft_ws_take(w.total, (size_t)B * P.ws_clip);
+    return w;
+}
+
+// the 8 MSE means (MSE_KEYS order) as constants: term k averages frames * B * width values -- the past frames for k = 0, 1, 4, 5 and the future ones
+// otherwise, rot_width rotation channels for even k and the 3 translation channels for odd k.  -> the fold's LossK; coef[k] = 2 w_k / n_k for the clip kernel
+inline LossK ft_loss_constants(const float *weights8, int past, int T, int B, int rot_width, float *coef) {
+    LossK lk;
+    for (int k = 0; k < 8; ++k) {
+        const double frames = (k == 0 || k == 1 || k == 4 || k == 5) ? past : T - past, width = (k & 1) ? 3 : rot_width;
+        const double n = frames * (double)B * width;
+        lk.w[k] = weights8[k];
+        lk.inv_n[k] = (float)(1.0 / n);
+        coef[k] = (float)(2.0 * (double)weights8[k] / n);
+    }
+    return lk;
+}
+
+// a fine-tuner's gradient call: clip() launches the clip kernel on st; then the fold over the clips and the conversion to the reference parameters
+template <int NP, class Clip>
+inline int stgcn_ft_launch_grads(const FtPlan &P, const FtWs &W, float *base, int B, const LossK &lk, const float *params, const float *bn, float *out9,
+                                 float *grads, hipStream_t st, Clip &&clip) {
+    idf_prof_mark(IDF_K_OTHER, st);
+    clip();
+    hipLaunchKernelGGL(stgcn_ft_fold_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, base + W.partials, base + W.loss_part, B, P.n_param,
+                       lk, base + W.gsum, out9);
+    hipLaunchKernelGGL(stgcn_ft_convert_kernel<NP>, dim3(12), dim3(FT_THR), 0, st, P, base + W.gsum, params, bn, grads);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+// Adam on the master parameters and the re-fold into the arena
+template <int NP, int VP, class OP>
+inline int stgcn_ft_launch_step(const OP &op, const FtPlan &P, float *arena, float *params, const float *bn, const float *grads, float *exp_avg,
+                                float *exp_avg_sq, const AdamK &k, hipStream_t st) {
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(stgcn_ft_adam_kernel, dim3((P.n_param + FT_THR - 1) / FT_THR), dim3(FT_THR), 0, st, params, grads, exp_avg, exp_avg_sq, P.n_param, k);
+    hipLaunchKernelGGL((stgcn_ft_refold_kernel<NP, VP, OP>), dim3(12), dim3(FT_THR), 0, st, op, P, params, bn, arena);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
 }
 
 }  // namespace
