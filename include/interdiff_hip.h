@@ -378,7 +378,7 @@ int interdiff_objprojector_forward(const idf_objproj *op, const float *obj_angle
 
 /* ---- FINE-TUNING of the correction predictor under the object-pose loss, with FROZEN normalisation statistics (the reference module in eval() with
  * autograd on: BatchNorm uses its running statistics and never writes them, dropout is off, contact clips take the argmax node; the module in train() -- batch statistics,
- * dropout, drawn nodes -- is the TRAINING block below; the gradient of the contact / penetration terms is NOT built).  Device code: csrc/objproj_train.h, launchers
+ * dropout, drawn nodes -- is the TRAINING block below; the gradient of the contact / penetration terms is interdiff_correction_geometry_grads).  Device code: csrc/objproj_train.h, launchers
  * csrc/objproj_train.hip; the layer backward and the fold / Adam / re-fold kernels are shared with the skeleton fine-tuner (csrc/stgcn_train.h).
  * Additive entries: interdiff_abi_version() stays what it was.
  *
@@ -430,7 +430,7 @@ int interdiff_correction_finetune_step(const idf_objproj *op, float *arena, floa
  * every ST_GCNN_layer (model/layers.py:308-318); the contact node of a clip is GIVEN (the caller draws it: torch.multinomial, model/correction_smpl.py:
  * 131-132).  Device code: csrc/objproj_bn_train.h around the fine-tuner's csrc/objproj_train.h, the train-mode layer shared with the skeleton trainer
  * (csrc/stgcn_bn_train.h); launchers csrc/objproj_bn_train.hip.  Additive entries: interdiff_abi_version() stays what it was.  Parameter and buffer
- * layouts: the PARAMETER TABLE above.  NOT built: the gradient of the contact / penetration terms (d_obj_pred stays their seam).
+ * layouts: the PARAMETER TABLE above.  The gradient of the contact / penetration terms: interdiff_correction_geometry_grads (d_obj_pred is its seam).
  *
  * interdiff_correction_train_grads   replaces loss.backward() on LitInteraction.calc_loss (train_correction_smpl.py:60-101) of ObjProjector.forward
  *      (model/correction_smpl.py:69-138) with the module in train(), and the buffer updates torch.nn.BatchNorm2d.forward makes there.  Arguments as
@@ -465,6 +465,27 @@ int interdiff_correction_train_grads(const idf_objproj *op, const float *params,
                                      void *ws, size_t ws_bytes, void *stream);
 int interdiff_correction_train_masks(const idf_objproj *op, int32_t B, double p_drop, uint64_t seed, uint64_t step, uint8_t *masks_out,
                                      void *stream);
+
+/* ---- THE TRAINERS' OWN PREDICTION: obj_pred [T,B,9] as the backward of the two gradient entries above sees it -- what `self(batch, current_epoch < 10)`
+ * returns inside _common_step (train_correction_smpl.py:188) before calc_loss_contact (:189) reads it.  The contact / penetration gradient
+ * (interdiff_correction_geometry_grads) is taken AT this prediction and handed to the gradient entry as d_obj_pred.  Additive entries.
+ *
+ * interdiff_correction_finetune_predict   the forward half of interdiff_correction_finetune_grads alone: the same device functions up to the head
+ *      (csrc/objproj_train.h ot_clip_predict), on op->arena -- `params` and `bn` are the vectors that arena is the fold of and are not read.  Arguments
+ *      as that entry's; ws >= interdiff_correction_finetune_workspace_bytes(op, B).  -> obj_pred_out f32 [T][B][9], the head's double rounded once.
+ * interdiff_correction_train_predict      the forward launches of interdiff_correction_train_grads (phases 0 .. 7) and the head of phase 8 alone:
+ *      batch statistics, dropout and given nodes as there -- the same masks / (seed, step) and nodes give the prediction that entry differentiates.
+ *      It has no `bn` argument: the train-mode forward never reads the running statistics and this entry never updates them.
+ *      ws >= interdiff_correction_train_workspace_bytes(op, B).  9 launches of one workgroup per clip.
+ * Both: IDF_E_INVAL as their gradient entries.  A training step with the geometry terms therefore runs the forward twice.
+ * ---------------------------------------------------------------------------------- */
+int interdiff_correction_finetune_predict(const idf_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                          const float *obj_trans, const float *markers, const int32_t *contact, int32_t B, int32_t T,
+                                          int32_t initialize, float *obj_pred_out, void *ws, size_t ws_bytes, void *stream);
+int interdiff_correction_train_predict(const idf_objproj *op, const float *params, const float *obj_angles, const float *obj_trans,
+                                       const float *markers, const int32_t *contact, const int32_t *nodes, int32_t B, int32_t T,
+                                       int32_t initialize, double p_drop, const uint8_t *masks, uint64_t seed, uint64_t step, float *obj_pred_out,
+                                       void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * denoised_fn, fused   replaces eval_smpl_short.py:84-130 for one gated step.
@@ -855,6 +876,31 @@ size_t interdiff_correction_losses_workspace_bytes(int32_t T, int32_t B, int32_t
 int interdiff_correction_losses(const float *obj_pred, const float *obj_gt, const float *obj_points, int32_t point_stride, const float *human_verts,
                                 int32_t T, int32_t B, int32_t V, int32_t P, int32_t rot_width, int32_t past_len, float *out_terms, float *out_frames,
                                 void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Backward pass of the two geometry terms (csrc/corr_geometry_grad.hip).  Additive: interdiff_abi_version() stays what it was.
+ *  interdiff_correction_geometry_grads  replaces what loss.backward() sends from the contact and penetration terms of
+ *      LitInteraction.calc_loss_contact (interdiff/train_correction_smpl.py:121-153, :159-162) through torch.matmul(obj_points, obj_rot) + trans (:126),
+ *      rotation_6d_to_matrix (:121) and tools.point2point_signed (tools.py:11-76) into obj_pred: d (w_penetration * penetration + w_contact * contact)
+ *      / d obj_pred, every mask and nearest-neighbour index a constant, as autograd treats them.
+ *      obj_pred f32 [T][B][9] (rot6d | translation), obj_points, point_stride, human_verts, T, B, V, P as interdiff_correction_losses takes them.
+ *      w_penetration, w_contact >= 0: the ALREADY ANNEALED factors of the weighted dict (:159-162), a^2 * weight_penetration and a^2 * weight_contact.
+ *      -> d_obj_pred_out f32 [T][B][9]; terms2_out f32 [2] = (penetration, contact), raw means, the terms 0 and 1 of interdiff_correction_losses (to fp32
+ *      rounding); frames_out (nullable) f32 [T*B][4] in that entry's out_frames layout.  With both weights 0 d_obj_pred_out is exact zeros.
+ *      A penetrating point j contributes g = 20 (y_j - x_i(j)) / |y_j - x_i(j)| with p = p_j, a contact vertex i contributes g = -(x_i - y_j(i)) /
+ *      |x_i - y_j(i)| with p = p_j(i); each adds g to dL/dt and g p^T to dL/dM, and dL/dM goes back through the Gram-Schmidt construction of
+ *      rotation_6d_to_matrix (F.normalize's eps 1e-12).  The scan is the forward's (1024 queries of one frame and one direction per workgroup, the
+ *      contract of interdiff_nn_argmin) with the argmin index carried on the human side as well; the unit vectors, the 12 sums per frame and the
+ *      Gram-Schmidt backward are in double, the result is rounded once.  Nothing per point is scattered: a workgroup writes (sum, count) and 12 doubles
+ *      into ws >= interdiff_correction_geometry_grads_workspace_bytes(T, B, V, P), a finishing launch folds them in index order.  One copy + three
+ *      launches whatever T * B is; no float atomics: two calls give the same bits, and the output is linear in the weights to the last bit for a
+ *      scaling by a power of two.  IDF_E_INVAL: null pointer, a size < 1, point_stride < 3, T * B > 65535, a negative or non-finite weight;
+ *      IDF_E_NOMEM: short workspace.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_correction_geometry_grads_workspace_bytes(int32_t T, int32_t B, int32_t V, int32_t P);
+int interdiff_correction_geometry_grads(const float *obj_pred, const float *obj_points, int32_t point_stride, const float *human_verts, int32_t T,
+                                        int32_t B, int32_t V, int32_t P, double w_penetration, double w_contact, float *d_obj_pred_out,
+                                        float *terms2_out, float *frames_out, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Contact-label generation (csrc/contact_labels.hip): the per-frame work of interdiff/data/prepare_behave.py:32-52 (get_contact_labels).  Additive.

@@ -153,6 +153,10 @@ _SIGS = {
     'interdiff_correction_finetune_grads': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, sz, vp]),
     'interdiff_correction_finetune_step': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, i32, C.c_double, C.c_double, C.c_double, C.c_double,
                                                      C.c_double, vp]),
+    'interdiff_correction_finetune_predict': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+    'interdiff_correction_train_predict': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_double, vp, u64, u64, vp, vp, sz, vp]),
+    'interdiff_correction_geometry_grads_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'interdiff_correction_geometry_grads': (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, sz, vp]),
     'interdiff_correction_train_workspace_bytes': (sz, [C.POINTER(ObjProj), i32]),
     'interdiff_correction_train_grads': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), C.c_double, vp, u64, u64,
                                                    C.c_double, i32, vp, vp, vp, vp, sz, vp]),

@@ -8,10 +8,13 @@ convolutions, BatchNorm affine weights, the temporal and adjacency matrices, the
 
 That is the reference's own regime where its schedule starts: ``_common_step`` anneals the contact and penetration terms by
 ``min(1, epoch / second_stage) ** 2``, exactly 0 at epoch 0, so there it trains on the eight MSE terms alone.  From epoch 1 on those two
-terms add a gradient that reaches the network only through ``obj_pred`` [T,B,9]: ``d_obj_pred`` is the seam through which a caller hands
-it in.  Training the way the reference trains -- the module in ``train()``: batch statistics, running-statistics updates, dropout,
-``multinomial`` node selection -- is ``interdiff_amd.correction_train.CorrectionTrainer``, built on this class.  NOT built: the contact /
-penetration gradient itself, learning-rate schedules, the Lightning glue and the dataset.
+terms add a gradient that reaches the network only through ``obj_pred`` [T,B,9]: ``d_obj_pred`` is the seam through which it comes in.
+A batch that also carries ``obj_points`` and ``human_verts`` gets it in the same call -- ``predict`` (this object's own prediction, the forward half
+of the gradient call) -> ``correction_losses.contact_gradient`` (csrc/corr_geometry_grad.hip) -> the gradient call with that ``d_obj_pred`` -- so
+``training_step(batch, current_epoch)`` trains on the reference's full loss at every epoch; the forward runs twice.
+Training the way the reference trains -- the module in ``train()``: batch statistics, running-statistics updates, dropout, ``multinomial``
+node selection -- is ``interdiff_amd.correction_train.CorrectionTrainer``, built on this class.  NOT built: a single-pass
+launcher that splits at the head, learning-rate schedules, the Lightning glue and the dataset.
 
 All arithmetic runs in libinterdiff_hip.so (csrc/objproj_train.h / .hip, csrc/stgcn_train.h): one workgroup per clip for forward, loss
 gradient and backward, a fixed-order fold over clips, Adam on fp32 master parameters in the reference layout, and the re-fold into the
@@ -23,7 +26,7 @@ import torch
 from . import _lib
 from .objprojector import ObjProjector
 from .skeleton import _strip
-from .correction_losses import CorrectionLossWeights
+from .correction_losses import CorrectionLossWeights, GEOMETRY_KEYS, contact_gradient, has_geometry
 from .stgcn_trainer import FlatParameters, param_table            # noqa: F401
 
 N_MARKERS = 67
@@ -88,20 +91,62 @@ class CorrectionFineTuner(FlatParameters):
                    _lib.dptr(grads), _lib.dptr(ws), ws.numel(), _lib.stream())
         return out9, grads
 
-    def loss_and_grads(self, batch, initialize=False, d_obj_pred=None):
+    def predict(self, batch, initialize=False):
+        """``obj_pred`` [T,B,9] (rot6d | translation) as the backward of ``loss_and_grads`` sees it: the forward half of the gradient call alone
+        (``interdiff_correction_finetune_predict``), the head's double rounded once."""
+        B, T, d6, ot, pos, contact, _ = self._inputs(batch)
+        out = torch.empty(T, B, 9, dtype=torch.float32, device=self.device)
+        ws = self._workspace(B)
+        self._call('finetune_predict', _lib.dptr(self.params), _lib.dptr(self.bn), _lib.dptr(d6), _lib.dptr(ot), _lib.dptr(pos),
+                   _lib.dptr(contact, torch.int32), B, T, int(bool(initialize)), _lib.dptr(out), _lib.dptr(ws), ws.numel(), _lib.stream())
+        return out
+
+    def _seam(self, batch, current_epoch, initialize, d_obj_pred, **how):
+        """What the gradient call gets as ``d_obj_pred`` at ``current_epoch`` -> (d_obj_pred or None, the two raw geometry terms or None).  An explicit
+        ``d_obj_pred`` wins; an epoch whose annealed geometry weights are zero needs none; otherwise the batch must carry ``obj_points`` and
+        ``human_verts`` and the gradient is taken at this object's own prediction: predict -> ``correction_losses.contact_gradient``.  ``how``:
+        what the subclass's ``predict`` takes beyond ``initialize``."""
+        geometry = self.weights.vector(current_epoch)[:2]
+        if d_obj_pred is not None or not any(w != 0 for w in geometry):
+            return d_obj_pred, None
+        if not has_geometry(batch):
+            raise ValueError('epoch %d weighs the penetration / contact terms by %r: the batch must carry obj_points [B,P,>=3] and human_verts '
+                             '[T,B,V,7], or their gradient at obj_pred must come in as d_obj_pred [T,B,9]' % (current_epoch, geometry))
+        return contact_gradient(self.predict(batch, initialize, **how), batch, self.weights, current_epoch)
+
+    def _packed10(self, out9, grads, terms, current_epoch):
+        """-> (loss, loss_dict, weighted_loss_dict, grads) with all ten terms under the reference's keys, as ``calc_loss_contact`` orders them."""
+        loss8, ld8, wd8, g = self._packed(out9, grads)
+        w = self.weights.vector(current_epoch)
+        ld = {k: terms[k] for k in GEOMETRY_KEYS}
+        ld.update(ld8)
+        wd = {'contact': terms['contact'] * w[1], 'penetration': terms['penetration'] * w[0]}
+        wd.update(wd8)
+        return loss8 + wd['contact'] + wd['penetration'], ld, wd, g
+
+    def loss_and_grads(self, batch, initialize=None, d_obj_pred=None, current_epoch=None):
         """-> (loss, loss_dict, weighted_loss_dict, grads): 0-dim device tensors under the reference's 8 MSE keys, ``grads`` = {reference
         parameter name: d (loss + <d_obj_pred, obj_pred>) / d parameter} (views of one flat device tensor).  ``d_obj_pred`` [T,B,9]: the gradient
-        at the prediction of any further term of the caller's objective; the returned loss stays that of the 8 terms."""
-        return self._packed(*self._grads(batch, initialize, d_obj_pred))
+        at the prediction of any further term of the caller's objective; the returned loss stays that of the 8 terms.
+        ``current_epoch`` (``initialize`` then defaults to ``current_epoch < 10``, like ``_common_step``): the reference's full objective at that epoch.
+        Where its annealed geometry weights are not zero and no ``d_obj_pred`` is given, the batch must also carry ``obj_points`` and ``human_verts``;
+        the call then runs predict -> ``contact_gradient`` -> gradients and returns all ten terms and the full loss, as ``calc_loss_contact`` does."""
+        if initialize is None:
+            initialize = current_epoch is not None and current_epoch < 10
+        if current_epoch is None:
+            return self._packed(*self._grads(batch, initialize, d_obj_pred))
+        d, terms = self._seam(batch, current_epoch, initialize, d_obj_pred)
+        out9, grads = self._grads(batch, initialize, d)
+        return self._packed(out9, grads) if terms is None else self._packed10(out9, grads, terms, current_epoch)
 
     def training_step(self, batch, current_epoch=0, d_obj_pred=None):
-        """Gradients (``initialize = current_epoch < 10``, like ``_common_step``), Adam, re-fold.  -> the loss of the 8 MSE terms BEFORE the step
-        (0-dim device tensor).  At an epoch whose annealed contact / penetration weights are not zero the reference trains on those terms too:
-        their gradient at the prediction must then come in as ``d_obj_pred`` -- without it this raises instead of training on another loss."""
-        geometry = self.weights.vector(current_epoch)[:2]
-        if any(w != 0 for w in geometry) and d_obj_pred is None:
-            raise ValueError('epoch %d weighs the penetration / contact terms by %r: pass their gradient at obj_pred as d_obj_pred [T,B,9] '
-                             '(their backward is not built here)' % (current_epoch, geometry))
-        out9, grads = self._grads(batch, current_epoch < 10, d_obj_pred)
+        """Gradients (``initialize = current_epoch < 10``, like ``_common_step``), Adam, re-fold.  -> the loss BEFORE the step (0-dim device tensor).
+        At an epoch whose annealed contact / penetration weights are not zero the reference trains on those terms too.  A batch that carries
+        ``obj_points`` and ``human_verts`` gets them here in one call: predict -> ``contact_gradient`` -> gradients with that ``d_obj_pred`` (the
+        forward runs twice), and the returned loss is the full one.  An explicit ``d_obj_pred`` wins (the returned loss is then that of the 8 MSE
+        terms); with neither this raises instead of training on another loss."""
+        initialize = current_epoch < 10
+        d, terms = self._seam(batch, current_epoch, initialize, d_obj_pred)
+        out9, grads = self._grads(batch, initialize, d)
         self.apply_gradients(grads)
-        return out9[0]
+        return out9[0] if terms is None else self._packed10(out9, grads, terms, current_epoch)[0]

@@ -1,10 +1,12 @@
 """Scoring of a correction-predictor checkpoint on the HIP path: the number ``ModelCheckpoint(monitor='val_loss')`` selects
-``correction.ckpt`` by (interdiff/train_correction_smpl.py).  Forward only -- no backward pass, no optimiser, no rendering.
+``correction.ckpt`` by (interdiff/train_correction_smpl.py), and the backward of its two geometry terms (``contact_gradient``, what the
+correction trainers feed their ``d_obj_pred`` seam with).  No optimiser, no rendering.
 
     calc_loss_contact   LitInteraction.calc_loss_contact :103-185  (8 object MSE terms + contact + penetration)
     calc_loss           LitInteraction.calc_loss :60-101           (the 8 MSE terms; rotation width 6, or 4 for the skeleton trainer)
     validation_step     _common_step(mode='valid') :187-189 + validation_step :272-277: ObjProjector.forward with
                         ``initialize = current_epoch < 10``, then calc_loss_contact; the ``visualize`` branch is not built
+    contact_gradient    d (annealed penetration + contact) / d obj_pred :121-162 (csrc/corr_geometry_grad.hip)
     body_records        the ``human_verts`` [T,B,6890,7] / ``markers`` [T,B,67,7] records of a batch from a body model
 
 The batch is the DataLoader's dict of lists (``frames[t]['human_verts']`` [B,V,7] = position | normal | contact label,
@@ -106,6 +108,48 @@ def calc_loss_contact(obj_pred, obj_gt, batch, past_len=10, weights=CorrectionLo
     terms = correction_terms(obj_pred, obj_gt, batch['obj_points'].to(dev), _stack_frames(batch, 'human_verts', dev), past_len)
     loss, loss_dict, weighted = _dicts(terms, LOSS_KEYS, 0, weights.vector(current_epoch))
     return loss, loss_dict, {k: weighted[k] for k in WEIGHTED_KEYS}
+
+
+def has_geometry(batch):
+    """Whether ``batch`` carries what the two geometry terms read: ``obj_points`` and ``human_verts`` (stacked, or in every ``frames[t]``)."""
+    if not isinstance(batch, dict) or 'obj_points' not in batch:
+        return False
+    return 'human_verts' in batch or ('frames' in batch and all('human_verts' in f for f in batch['frames']))
+
+
+def geometry_gradient(obj_pred, obj_points, human_verts, w_penetration, w_contact, return_frames=False):
+    """``interdiff_correction_geometry_grads``: d (w_penetration * penetration + w_contact * contact) / d obj_pred -> (f32 [T,B,9], f32 [2] the two raw
+    terms[, per-frame partials [T*B,4] as ``correction_terms`` returns them]).  The weights are the already annealed factors."""
+    lib = _lib.load()
+    x = obj_pred.contiguous().float()
+    if x.dim() != 3 or x.shape[2] != 9:
+        raise ValueError('obj_pred must be [T,B,9] (rot6d | translation)')
+    T, B = x.shape[:2]
+    pts, hv = obj_points.to(x.device).float(), human_verts.to(x.device).float()
+    if not pts.is_contiguous():
+        pts = pts.contiguous()
+    if not hv.is_contiguous():
+        hv = hv.contiguous()
+    if pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] < 3 or hv.dim() != 4 or tuple(hv.shape[:2]) != (T, B) or hv.shape[3] != 7:
+        raise ValueError('obj_points must be [B,P,>=3] and human_verts [T,B,V,7] (position | normal | contact label)')
+    P, V = pts.shape[1], hv.shape[2]
+    ws = torch.empty(lib.interdiff_correction_geometry_grads_workspace_bytes(T, B, V, P), dtype=torch.uint8, device=x.device)
+    out, terms = torch.empty_like(x), torch.empty(2, dtype=torch.float32, device=x.device)
+    frames = torch.empty(T * B, 4, dtype=torch.float32, device=x.device) if return_frames else None
+    _lib.check(lib.interdiff_correction_geometry_grads(_lib.dptr(x), _lib.dptr(pts), pts.shape[2], _lib.dptr(hv), T, B, V, P, float(w_penetration),
+                                                       float(w_contact), _lib.dptr(out), _lib.dptr(terms), _lib.dptr(frames, allow_none=True), _lib.dptr(ws),
+                                                       ws.numel(), _lib.stream()), 'correction_geometry_grads')
+    return (out, terms, frames) if return_frames else (out, terms)
+
+
+def contact_gradient(obj_pred, batch, weights=CorrectionLossWeights(), current_epoch=0):
+    """The gradient at ``obj_pred`` [T,B,9] of the two annealed geometry terms of ``calc_loss_contact`` (what ``loss.backward()`` sends into the
+    prediction from train_correction_smpl.py:121-162) -> (d_obj_pred [T,B,9], {'penetration', 'contact'}: the raw terms, 0-dim device tensors).
+    ``batch`` as ``calc_loss_contact`` takes it.  This is the ``d_obj_pred`` of the trainers' gradient calls."""
+    dev = obj_pred.device
+    w = weights.vector(current_epoch)
+    d, terms = geometry_gradient(obj_pred, batch['obj_points'].to(dev), _stack_frames(batch, 'human_verts', dev), w[0], w[1])
+    return d, {k: terms[i] for i, k in enumerate(GEOMETRY_KEYS)}
 
 
 def calc_loss(obj_pred, obj_gt, batch=None, past_len=10, weights=CorrectionLossWeights()):

@@ -17,8 +17,9 @@ Departure from the reference: the 24 convolution biases cancel inside a batch no
 reference computes fp32 rounding noise there, which Adam turns into a +-lr random walk of parameters that cannot influence the
 train-mode output; here those gradients are exact 0.0, and with ``weight_decay = 0`` the biases do not move.
 
-NOT built: the contact / penetration gradient (``d_obj_pred`` stays its seam, as in the fine-tuner), learning-rate schedules, the
-Lightning glue, the dataset.
+The contact / penetration terms come in as in the fine-tuner: ``predict`` (the forward launches alone, same masks, nodes and (seed, step)) ->
+``correction_losses.contact_gradient`` -> the gradient call; the running statistics are updated once.  NOT built: a single-pass launcher,
+learning-rate schedules, the Lightning glue, the dataset.
 
 All arithmetic but the draw runs in libinterdiff_hip.so (csrc/objproj_bn_train.h around csrc/objproj_train.h, the train-mode layer in
 csrc/stgcn_bn_train.h; launchers csrc/objproj_bn_train.hip).
@@ -112,23 +113,40 @@ class CorrectionTrainer(TrainMode, CorrectionFineTuner):
         out9, grads, _ = self._train_grads(batch, initialize, d_obj_pred=d_obj_pred)
         return out9, grads
 
-    def loss_and_grads(self, batch, initialize=False, masks=None, nodes=None, d_obj_pred=None):
-        """As ``CorrectionFineTuner.loss_and_grads`` with the module in train().  Touches neither the running statistics nor the step counter."""
-        out9, grads, _ = self._train_grads(batch, initialize, masks, nodes, d_obj_pred)
-        return self._packed(out9, grads)
+    def predict(self, batch, initialize=False, masks=None, nodes=None):
+        """``obj_pred`` [T,B,9] as the backward of ``loss_and_grads`` with the same ``masks`` / ``nodes`` (None: those of (seed, step)) sees it: the forward
+        launches of the gradient call alone (``interdiff_correction_train_predict``).  Touches neither the running statistics nor the step counter."""
+        B, T, d6, ot, pos, contact, _ = self._inputs(batch)
+        m = self._mask_buffer(masks, B)
+        picked = self.select_nodes(contact, initialize, nodes)
+        out = torch.empty(T, B, 9, dtype=torch.float32, device=self.device)
+        ws = self._train_workspace(B)
+        self._call('train_predict', _lib.dptr(self.params), _lib.dptr(d6), _lib.dptr(ot), _lib.dptr(pos), _lib.dptr(contact, torch.int32),
+                   _lib.dptr(picked, torch.int32) if picked is not None else None, B, T, int(bool(initialize)), self.dropout,
+                   _lib.dptr(m) if m is not None else None, self.seed, self.step, _lib.dptr(out), _lib.dptr(ws), ws.numel(), _lib.stream())
+        return out
+
+    def loss_and_grads(self, batch, initialize=None, masks=None, nodes=None, d_obj_pred=None, current_epoch=None):
+        """As ``CorrectionFineTuner.loss_and_grads`` with the module in train(); with ``current_epoch`` and the geometry operands in the batch both
+        passes read the same masks and nodes.  Touches neither the running statistics nor the step counter."""
+        if initialize is None:
+            initialize = current_epoch is not None and current_epoch < 10
+        d, terms = (d_obj_pred, None) if current_epoch is None else self._seam(batch, current_epoch, initialize, d_obj_pred, masks=masks, nodes=nodes)
+        out9, grads, _ = self._train_grads(batch, initialize, masks, nodes, d)
+        return self._packed(out9, grads) if terms is None else self._packed10(out9, grads, terms, current_epoch)
 
     def training_step(self, batch, current_epoch=0, masks=None, nodes=None, d_obj_pred=None):
         """Gradients (``initialize = current_epoch < 10``, like ``_common_step``), the running-statistics update, ``num_batches_tracked += 1``,
-        Adam, the re-fold.  -> the loss of the 8 MSE terms BEFORE the step.  At an epoch whose annealed contact / penetration weights are not
-        zero their gradient at the prediction must come in as ``d_obj_pred``, as in the fine-tuner: without it this raises."""
-        geometry = self.weights.vector(current_epoch)[:2]
-        if any(w != 0 for w in geometry) and d_obj_pred is None:
-            raise ValueError('epoch %d weighs the penetration / contact terms by %r: pass their gradient at obj_pred as d_obj_pred [T,B,9] '
-                             '(their backward is not built here)' % (current_epoch, geometry))
-        out9, grads, _ = self._train_grads(batch, current_epoch < 10, masks, nodes, d_obj_pred, update=True)
+        Adam, the re-fold.  -> the loss BEFORE the step.  At an epoch whose annealed contact / penetration weights are not zero a batch that carries
+        ``obj_points`` and ``human_verts`` gets those terms here, as in the fine-tuner: the prediction pass and the gradient pass read the same masks,
+        nodes and (seed, step), and the running statistics are updated once, by the gradient pass.  An explicit ``d_obj_pred`` wins; with neither this
+        raises."""
+        initialize = current_epoch < 10
+        d, terms = self._seam(batch, current_epoch, initialize, d_obj_pred, masks=masks, nodes=nodes)
+        out9, grads, _ = self._train_grads(batch, initialize, masks, nodes, d, update=True)
         self._count_batch()
         self.apply_gradients(grads)
-        return out9[0]
+        return out9[0] if terms is None else self._packed10(out9, grads, terms, current_epoch)[0]
 
     def batch_statistics(self, batch):
         """{buffer name: tensor} under the ``running_mean`` / ``running_var`` key names: mean and BIASED variance of this batch at every

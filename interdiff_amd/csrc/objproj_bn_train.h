@@ -16,6 +16,7 @@
 //             12       B(8), the skip connections; A(7), A(3)
 //             13..15   B(l), A(l-1) for l = 20 - phase and 16 - phase
 //             16       B(4), B(0)
+//   predict   17       after 0 .. 7 in place of 8: FIN(11) and the head up to the prediction, which goes out rounded once (a.obj_pred_out)
 // The glue around the stacks -- the DCT, the skip connections and the head, in DOUBLE -- is the fine-tuner's (csrc/objproj_train.h ot_dct ..
 // ot_split_relative): its clip body and the phases below call the same functions.  keep (double) crosses the launches 4 -> 8 and 8 -> 12 through the clip's
 // workspace slice.
@@ -35,6 +36,7 @@ using idf_stgcn_train::TrPlan;
 using Tr = idf_stgcn_train::StgcnTr<NP, VP, MAXC, BUF>;
 
 constexpr int TR_SEAM = Tr::SEAM;
+constexpr int TR_PHASE_PREDICT = TR_PHASES;            // after the forward phases 0 .. 7: the head without the backward (interdiff_correction_train_predict)
 constexpr size_t TR_LDS = OT_LDS + (size_t)Tr::STAT * sizeof(double);
 static_assert(OT_LDS % 8 == 0, "the statistics region of the LDS is read as doubles");
 static_assert(TR_LDS + 64 <= 160 * 1024, "one workgroup per CU");
@@ -84,6 +86,11 @@ __device__ __forceinline__ void tr_phase_body(float *sm, const idf_objproj &op, 
         ot_head_bwd(sm, op, pick);
         tr_keep_copy(keepb, keep);
         Tr::tr_bwd_a(c, 11);
+    } else if (phase == TR_PHASE_PREDICT) {            // phase 8's forward half alone: the prediction -> a.obj_pred_out
+        tr_keep_copy(keep, keepf);
+        ot_dct(sm, op);
+        Tr::tr_fin(c, 11);
+        ot_head(sm, op, a, nodes, B, b);
     } else if (phase <= 11) {
         Tr::tr_bwd_b(c, 20 - phase);
         Tr::tr_bwd_a(c, 19 - phase);

@@ -61,3 +61,45 @@ extern "C" int interdiff_correction_train_grads(const idf_objproj *op, const flo
                                                    hipLaunchKernelGGL(objproj_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, P, TP, a, t, nodes, B, phase);
                                                });
 }
+
+extern "C" int interdiff_correction_train_predict(const idf_objproj *op, const float *params, const float *obj_angles, const float *obj_trans,
+                                                  const float *markers, const int32_t *contact, const int32_t *nodes, int32_t B, int32_t T,
+                                                  int32_t initialize, double p_drop, const uint8_t *masks, uint64_t seed, uint64_t step, float *obj_pred_out,
+                                                  void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !obj_angles || !obj_trans || !markers || !obj_pred_out || !ws) return IDF_E_INVAL;
+    if (!initialize && !contact && !nodes) return IDF_E_INVAL;
+    if (ot_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
+    if (!(p_drop >= 0.0 && p_drop < 1.0)) return IDF_E_INVAL;
+    const FtPlan P = ot_plan(op->cin, op->cout);
+    const TrPlan TP = tr_plan(P);
+    const TrWs W = tr_ws(P, TP, B, TR_SEAM);
+    if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
+    float *base = static_cast<float *>(ws);
+    hipStream_t st = idf_stream(stream);
+    OtArgs a{};                                        // coef stays 0: the head's loss gradient is not read
+    a.obj_angles = obj_angles; a.obj_trans = obj_trans; a.markers = markers; a.contact = contact;
+    a.partials = base + W.partials;
+    a.loss_part = base + W.loss_part;
+    a.ws_clips = base + W.clips;
+    a.initialize = initialize != 0;
+    a.obj_pred_out = obj_pred_out;
+    TrArgs t{};                                        // as stgcn_tr_launch_grads sets them: the same masks, the same scale
+    t.params = params;
+    t.statp = reinterpret_cast<double *>(base + W.statp);
+    t.dyp = reinterpret_cast<double *>(base + W.dyp);
+    t.scale = (float)(1.0 / (1.0 - p_drop));
+    t.masks = masks;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (idf_opt_in_lds(reinterpret_cast<const void *>(objproj_tr_phase_kernel), (int)TR_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
+    idf_prof_mark(IDF_K_OTHER, st);
+    if (!masks && p_drop > 0.0) {
+        uint8_t *mb = reinterpret_cast<uint8_t *>(base + W.masks);
+        stgcn_tr_launch_masks<NP>(P, TP, B, p_drop, seed, step, mb, st);
+        t.masks = mb;
+    }
+    for (int k = 0; k <= 8; ++k)                       // the forward phases 0 .. 7, then the head alone
+        hipLaunchKernelGGL(objproj_tr_phase_kernel, dim3(B), dim3(NTHR), TR_LDS, st, *op, P, TP, a, t, nodes, B, k < 8 ? k : TR_PHASE_PREDICT);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}

@@ -82,6 +82,7 @@ struct OtArgs {
     float *ws_clips;           // [B][ws_clip]
     float coef[8];             // 2 w_k / n_k, MSE_KEYS order: rot_past, nonrot_past, rot_future, nonrot_future, then the four velocity terms
     int32_t initialize;
+    float *obj_pred_out;       // [T][B][9] the prediction the loss reads, rounded once to fp32, or null (the predict entries set it)
 };
 
 __device__ __forceinline__ float ot_pose_at(const OtArgs &a, int B, int b, int t, int c) {
@@ -247,6 +248,7 @@ __device__ inline int ot_head(float *sm, const idf_objproj &op, const OtArgs &a,
         const int t = i / CH, c = i - t * CH;
         double v = 0.0;
         for (int k = 0; k < NP; ++k) v += Dd[k * T + t] * col[c * NP + k];
+        if (a.obj_pred_out) a.obj_pred_out[((size_t)t * B + b) * CH + c] = (float)v;
         err[i] = v - (double)ot_pose_at(a, B, b, t, c);
     }
     __syncthreads();
@@ -358,5 +360,18 @@ __device__ __forceinline__ void ot_clip_body(float *sm, const idf_objproj &op, c
     ot_stack_bwd(sm, red, op, plan, 0, NM, ws, G, X, part);
 }
 
+// the forward half of ot_clip_body alone, up to the head: the prediction goes to a.obj_pred_out (interdiff_correction_finetune_predict).  The saves and the
+// clip's loss sums land in the workspace as in the gradient call; no parameter gradient is written.
+__device__ __forceinline__ void ot_clip_predict(float *sm, const idf_objproj &op, const FtPlan &plan, const OtArgs &a, int B, int b) {
+    float *ws = a.ws_clips + (size_t)b * plan.ws_clip;
+    ot_inputs(sm, op, a, B, b);
+    ot_stack_fwd(sm, op, plan, 0, NM, ws);
+    ot_join_relative(sm, op, a, B, b);
+    ot_object_input(sm, op);
+    ot_stack_fwd(sm, op, plan, 1, 1, ws);
+    ot_join_object(sm, op);
+    ot_stack_fwd(sm, op, plan, 2, MAXN, ws);
+    ot_head(sm, op, a, nullptr, B, b);
+}
 
 }  // namespace idf_objproj_train

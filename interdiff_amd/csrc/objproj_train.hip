@@ -15,7 +15,39 @@ __global__ __launch_bounds__(NTHR) void objproj_ft_clip_kernel(const idf_objproj
     ot_clip_body(sm, op, plan, a, B, blockIdx.x);
 }
 
+__global__ __launch_bounds__(NTHR) void objproj_ft_predict_kernel(const idf_objproj op, const FtPlan plan, const OtArgs a, int B) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    ot_clip_predict(sm, op, plan, a, B, blockIdx.x);
+}
+
 }  // namespace
+
+extern "C" int interdiff_correction_finetune_predict(const idf_objproj *op, const float *params, const float *bn, const float *obj_angles,
+                                                     const float *obj_trans, const float *markers, const int32_t *contact, int32_t B, int32_t T,
+                                                     int32_t initialize, float *obj_pred_out, void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !bn || !obj_angles || !obj_trans || !markers || !obj_pred_out || !ws) return IDF_E_INVAL;
+    if (!initialize && !contact) return IDF_E_INVAL;
+    if (ot_check(op, B) != IDF_OK || T != op->T) return IDF_E_INVAL;
+    const FtPlan P = ot_plan(op->cin, op->cout);
+    const FtWs W = ft_ws(P, B);
+    if (ws_bytes < W.total * sizeof(float)) return IDF_E_INVAL;
+    float *base = static_cast<float *>(ws);
+    hipStream_t st = idf_stream(stream);
+    OtArgs a{};                                        // coef stays 0: the head's loss gradient is not read
+    a.obj_angles = obj_angles; a.obj_trans = obj_trans; a.markers = markers; a.contact = contact;
+    a.partials = base + W.partials;
+    a.loss_part = base + W.loss_part;
+    a.ws_clips = base + W.clips;
+    a.initialize = initialize != 0;
+    a.obj_pred_out = obj_pred_out;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (idf_opt_in_lds(reinterpret_cast<const void *>(objproj_ft_predict_kernel), (int)OT_LDS, lds_ok) != IDF_OK) return IDF_E_LAUNCH;
+    idf_prof_mark(IDF_K_OTHER, st);
+    hipLaunchKernelGGL(objproj_ft_predict_kernel, dim3(B), dim3(NTHR), OT_LDS, st, *op, P, a, B);
+    idf_prof_mark(-1, st);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
 
 extern "C" int interdiff_correction_finetune_param_table(const idf_objproj *op, int32_t *table, int32_t *n_param, int32_t *n_bn) {
     if (!table || !n_param || !n_bn || ot_check_widths(op) != IDF_OK) return IDF_E_INVAL;
