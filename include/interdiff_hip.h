@@ -821,6 +821,48 @@ int interdiff_sample_losses(const float *samples, const float *gt, const float *
                             int32_t variant, float *out_terms, float *out_per_clip, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * TRAINING of the SMPL denoiser's decoder (csrc/mdm_train.h, launchers csrc/mdm_train.hip): the backward of MDM.forward(x, timesteps, y)
+ * (model/diffusion_smpl.py:226-246) under the loss of LitInteraction.forward_backward (train_diffusion_smpl.py:60-166), and AdamW (:177-183).
+ * Additive entries: interdiff_abi_version() stays what it was.  dropout 0, cond_mask_prob 0, stochastic depth at rate 0 (the reference's defaults):
+ * train() and eval() compute the same function.  Exact fp32 throughout (v_mfma_f32_16x16x4_f32 and VALU, no f16 MFMA), no float atomics: two
+ * calls give the same bits.
+ *
+ * PARAMETER TABLE.  `params`, `grads`, `exp_avg`, `exp_avg_sq` are flat fp32 vectors of n_param = 7 069 900 floats, the 144 tensors MDM.forward
+ * reads, packed without padding in this order (state_dict names, shapes as the reference's):
+ *     bodyEmbedding.{weight,bias}, objEmbedding.{weight,bias}, embedTimeStep.time_embed.0.{weight,bias}, embedTimeStep.time_embed.2.{weight,bias},
+ *     per decoder layer 0..7:  layers 0, 7: self_attn.in_proj_weight, self_attn.in_proj_bias, self_attn.out_proj.weight, self_attn.out_proj.bias;
+ *                              layers 1..6: queries, wk;
+ *                              then multihead_attn.in_proj_weight, .in_proj_bias, .out_proj.weight, .out_proj.bias, linear1.{weight,bias},
+ *                              linear2.{weight,bias}, norm1.{weight,bias}, norm2.{weight,bias}, norm3.{weight,bias},
+ *     bodyFinalLinear.{weight,bias}, objFinalLinear.{weight,bias}.
+ * bodyEmbedding / objEmbedding are shared with the encoder; their gradient here is the decoder path's alone (cond is an input of this pass).
+ *
+ *  interdiff_denoising_loss_grad     replaces autograd through the 16 terms of forward_backward (:72-134): d_pred [B,1,144,T] = d/d pred of
+ *      mean_b sum_i weights16[i] * term_i[b], the terms of interdiff_denoising_losses (velocity terms as the reference writes them: the
+ *      ground-truth operand is zero).  weights16: HOST pointer, term order of interdiff_denoising_losses.  One launch, one thread per element.
+ *  interdiff_mdm_train_param_table   offsets / sizes (HOST int64 [144], nullable) of the tensors in the flat vectors, their count and n_param.
+ *  interdiff_mdm_train_workspace_bytes   workspace of interdiff_mdm_train_grads; 0 for an unsupported shape (T > 128, mem_len > 16).
+ *  interdiff_mdm_train_grads         replaces MDM.forward + loss.backward() of forward_backward for the 144 tensors.  x_t [B,1,144,T] (what
+ *      interdiff_q_sample made), ts int64 [B], cond [mem_len][B][256], target [B,1,144,T] (x_start), pe [pe_rows][256] the sinusoidal table
+ *      (PositionalEmbedding.pe; pe_rows > every timestep and >= T).  -> pred [B,1,144,T] (the model output), terms [16][B] (as
+ *      interdiff_denoising_losses), grads [n_param], d_cond [mem_len][B][256] (summed over the eight layers, 7 .. 0).  d_pred_in NULL: the
+ *      gradient of the weighted loss (interdiff_denoising_loss_grad); else [B,1,144,T], the gradient of any other objective with respect to
+ *      pred, taken instead.  ws 256-byte aligned.  T <= 128 (one workgroup holds a head's keys), mem_len <= 16, past_len >= 2, T >= past_len + 2.
+ *  interdiff_mdm_train_step          replaces optimizer.step() of torch.optim.AdamW (decoupled decay, then Adam with bias correction, torch's
+ *      order of operations) on the flat vectors, in place; `step` = 1 for the first step.
+ * ---------------------------------------------------------------------------------- */
+int interdiff_denoising_loss_grad(const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16,
+                                  float *d_pred, void *stream);
+int interdiff_mdm_train_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param);
+size_t interdiff_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t mem_len);
+int interdiff_mdm_train_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *cond,
+                              const float *target, int32_t B, int32_t T, int32_t mem_len, int32_t past_len, const float *weights16,
+                              const float *d_pred_in, float *grads, float *d_cond, float *pred, float *terms, void *ws, size_t ws_bytes,
+                              void *stream);
+int interdiff_mdm_train_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, double lr,
+                             double beta1, double beta2, double eps, double weight_decay, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Scoring of a skeleton diffusion checkpoint (csrc/skeleton_losses.hip): the forward, scoring side of interdiff/train_diffusion_skeleton.py.
  * Forward only, additive.  Tokens [B,1,C,T] with C = n_body + 3 * n_points + 7 (63 + 36 + 7 = 106): body | object keypoints | object
  * translation 3 | object quaternion xyzw 4.  The keypoint channels are the prediction's own (the denoiser's keypoint head wrote them): nothing is

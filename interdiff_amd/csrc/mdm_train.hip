@@ -1,0 +1,363 @@
+// Training of the SMPL denoiser's decoder (launchers; device code and the arithmetic contract: csrc/mdm_train.h).  Replaces, for the 144 tensors MDM.forward reads,
+// loss.backward() on LitInteraction.forward_backward (train_diffusion_smpl.py:60-166) and torch.optim.AdamW's step (:177-183).  `cond` is an input: its gradient
+// d_cond is returned for a later backward of MDM._get_embeddings.  The sampler's kernels and arena are not touched.
+//
+// Stored by the forward, per layer: the layer input, q|k|v and the attention output with its per-row log-sum-exp (layers 0, 7), the three normalised rows + 1/sigma
+// and LayerNorm outputs, the cross-attention query, memory k|v and output, the feed-forward pre-activation.  Recomputed by the backward: every softmax probability
+// (self-attention, cross-attention, QaN block) and the GELU output.
+#include "mdm_train.h"
+
+using namespace mdmtrain;
+
+namespace {
+
+constexpr int N_LAYERS = 8, N_TENSORS = 144;
+
+struct LayerOff {
+    int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, ca_in_w, ca_in_b, ca_out_w, ca_out_b, l1_w, l1_b, l2_w, l2_b, ln_w[3], ln_b[3];
+};
+struct Layout {
+    int64_t body_w, body_b, obj_w, obj_b, t0_w, t0_b, t2_w, t2_b, bodyf_w, bodyf_b, objf_w, objf_b, total;
+    LayerOff layer[N_LAYERS];
+    int64_t off[N_TENSORS], size[N_TENSORS];
+};
+inline bool is_qan(int l) { return l >= 1 && l <= 6; }
+
+// the flat master vector: the tensors in the order of interdiff_amd/mdm_train.py PARAM_NAMES, packed without padding
+const Layout &layout() {
+    static const Layout L = [] {
+        Layout o{};
+        int64_t at = 0;
+        int n = 0;
+        auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
+        take(o.body_w, (int64_t)D * NBODY); take(o.body_b, D); take(o.obj_w, (int64_t)D * (CTOK - NBODY)); take(o.obj_b, D);
+        take(o.t0_w, (int64_t)D * D); take(o.t0_b, D); take(o.t2_w, (int64_t)D * D); take(o.t2_b, D);
+        for (int l = 0; l < N_LAYERS; ++l) {
+            LayerOff &y = o.layer[l];
+            if (is_qan(l)) {
+                take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
+                y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
+            } else {
+                take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
+                y.queries = y.wk = -1;
+            }
+            take(y.ca_in_w, (int64_t)3 * D * D); take(y.ca_in_b, 3 * D); take(y.ca_out_w, (int64_t)D * D); take(y.ca_out_b, D);
+            take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
+            for (int i = 0; i < 3; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
+        }
+        take(o.bodyf_w, (int64_t)NBODY * D); take(o.bodyf_b, NBODY); take(o.objf_w, (int64_t)(CTOK - NBODY) * D); take(o.objf_b, CTOK - NBODY);
+        o.total = at;
+        return o;
+    }();
+    return L;
+}
+
+// ---- workspace plan (floats) ---------------------------------------------------------------------------------------------------------------------------
+struct LayerWs {
+    float *qkv, *ao, *lse, *xh[3], *rs[3], *x1, *x2, *q2, *kv, *o2, *z, *G;
+};
+struct Ws {
+    float *X, *Y, *dY, *tin, *z0, *sz, *temb, *h[N_LAYERS + 1];
+    LayerWs layer[N_LAYERS];
+    float *g, *dz, *t[4], *dqkv, *P, *dS, *Pc, *dSc, *dkv, *dG, *dsim, *cj, *dwk_tok, *partial, *dtemb, *dsz;
+    size_t floats;
+};
+Ws plan(float *base, int B, int T, int S) {
+    Ws w{};
+    size_t at = 0;
+    const size_t M = (size_t)B * T;
+    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    w.X = take(M * CTOK); w.Y = take(M * CTOK); w.dY = take(M * CTOK);
+    w.tin = take((size_t)B * D); w.z0 = take((size_t)B * D); w.sz = take((size_t)B * D); w.temb = take((size_t)B * D);
+    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
+    for (int l = 0; l < N_LAYERS; ++l) {
+        LayerWs &y = w.layer[l];
+        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
+        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * T); }
+        for (int i = 0; i < 3; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
+        y.x1 = take(M * D); y.x2 = take(M * D); y.q2 = take(M * D); y.kv = take((size_t)S * B * 2 * D); y.o2 = take(M * D); y.z = take(M * FF);
+    }
+    w.g = take(M * FF); w.dz = take(M * FF);
+    for (int i = 0; i < 4; ++i) w.t[i] = take(M * D);
+    w.dqkv = take(M * 3 * D);
+    w.P = take((size_t)B * HEADS * T * T); w.dS = take((size_t)B * HEADS * T * T);
+    w.Pc = take(M * HEADS * MAX_MEM); w.dSc = take(M * HEADS * MAX_MEM);
+    w.dkv = take((size_t)S * B * 2 * D);
+    w.dG = take((size_t)SLOTS * NQ * D); w.dsim = take(M * NQ * SLOTS); w.cj = take(M * SLOTS); w.dwk_tok = take(M * NQ);
+    w.partial = take(((M + 63) / 64 + 1) * FF);
+    w.dtemb = take((size_t)B * D); w.dsz = take((size_t)B * D);
+    w.floats = at;
+    return w;
+}
+
+// ---- launch helpers: every one returns IDF_OK or IDF_E_LAUNCH ----------------------------------------------------------------------------------------------
+#define MT_TRY(x)                  \
+    do {                           \
+        const int mt_rc_ = (x);    \
+        if (mt_rc_ != IDF_OK) return mt_rc_; \
+    } while (0)
+
+int gemm(hipStream_t st, const float *A, int64_t sam, int64_t sak, const float *Bm, int64_t sbk, int64_t sbn, float *C, int64_t ldc, const float *bias, const float *R,
+         int64_t ldr, int M, int N, int K) {
+    const Gemm g{A, sam, sak, Bm, sbk, sbn, C, ldc, bias, R, ldr, M, N, K};
+    hipLaunchKernelGGL(mt_gemm_kernel, dim3((unsigned)idf_cdiv(N, 32), (unsigned)idf_cdiv(M, 32)), dim3(64), 0, st, g);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+// Y[M,N] = X[M,K] W[N,K]^T + b (+ R)
+int lin_fwd(hipStream_t st, const float *X, int64_t ldx, const float *W, const float *b, float *Y, int64_t ldy, const float *R, int64_t ldr, int M, int N, int K) {
+    return gemm(st, X, ldx, 1, W, 1, K, Y, ldy, b, R, ldr, M, N, K);
+}
+// dX[M,K] = dY[M,N] W[N,K] (+ R)
+int lin_dx(hipStream_t st, const float *dY, int64_t ldy, const float *W, float *dX, int64_t ldx, const float *R, int64_t ldr, int M, int N, int K) {
+    return gemm(st, dY, ldy, 1, W, K, 1, dX, ldx, nullptr, R, ldr, M, K, N);
+}
+// dW[N,K] = dY[M,N]^T X[M,K]
+int lin_dw(hipStream_t st, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, int M, int N, int K) {
+    return gemm(st, dY, 1, ldy, X, ldx, 1, dW, K, nullptr, nullptr, 0, N, K, M);
+}
+// out[N] = column sums of A[M,N] (* Bm), two-stage
+int colsum(hipStream_t st, const float *A, int64_t lda, const float *Bm, int64_t ldb, int M, int N, float *partial, float *out) {
+    const int slabs = (int)idf_cdiv(M, 64);
+    hipLaunchKernelGGL(mt_colsum_partial_kernel, dim3((unsigned)idf_cdiv(N, 64), (unsigned)slabs), dim3(256), 0, st, A, lda, Bm, ldb, M, N, partial);
+    IDF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mt_colsum_reduce_kernel, dim3((unsigned)idf_cdiv(N, 256)), dim3(256), 0, st, partial, slabs, N, out);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+inline unsigned blocks256(int64_t n) { return (unsigned)idf_cdiv(n, 256); }
+
+int ln_fwd(hipStream_t st, const float *s, const float *gw, const float *gb, float *xh, float *rs, float *y, int M) {
+    hipLaunchKernelGGL(mt_ln_fwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, s, gw, gb, xh, rs, y, M);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+// LayerNorm backward: d gamma, d beta (two-stage column sums) and dx
+int ln_bwd(hipStream_t st, const float *dy, const float *xh, const float *rs, const float *gw, float *dgw, float *dgb, float *dx, float *partial, int M) {
+    MT_TRY(colsum(st, dy, D, xh, D, M, D, partial, dgw));
+    MT_TRY(colsum(st, dy, D, nullptr, 0, M, D, partial, dgb));
+    hipLaunchKernelGGL(mt_ln_bwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, dy, xh, rs, gw, dx, M);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+Weights16 weights_of(const float *w16) {
+    Weights16 W;
+    for (int i = 0; i < 16; ++i) W.w[i] = w16[i];
+    return W;
+}
+int loss_grad(hipStream_t st, const float *pred, const float *target, int B, int T, int P, const float *w16, float *dpred) {
+    hipLaunchKernelGGL(mt_loss_grad_kernel, dim3(blocks256((int64_t)B * CTOK * T)), dim3(256), 0, st, pred, target, B, T, P, weights_of(w16), dpred);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+// ---- forward with saves ---------------------------------------------------------------------------------------------------------------------------------
+int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *pe, int pe_rows, const float *x_t, const int64_t *ts, const float *cond, int B, int T,
+            int S, float *pred) {
+    const int M = B * T, SB = S * B;
+    hipLaunchKernelGGL(mt_tokens_to_rows_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, x_t, w.X, B, T);
+    IDF_CHECK_LAUNCH();
+    // timestep MLP (layers.py:42-43)
+    hipLaunchKernelGGL(mt_gather_pe_kernel, dim3((unsigned)B), dim3(256), 0, st, pe, pe_rows, ts, w.tin);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_fwd(st, w.tin, D, th + L.t0_w, th + L.t0_b, w.z0, D, nullptr, 0, B, D, D));
+    hipLaunchKernelGGL(mt_silu_kernel, dim3(blocks256((int64_t)B * D)), dim3(256), 0, st, w.z0, w.sz, (int64_t)B * D);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_fwd(st, w.sz, D, th + L.t2_w, th + L.t2_b, w.temb, D, nullptr, 0, B, D, D));
+    // embedding: bodyEmbedding(x[:135]) + objEmbedding(x[135:]) + temb + pe[t]
+    MT_TRY(lin_fwd(st, w.X, CTOK, th + L.body_w, th + L.body_b, w.h[0], D, nullptr, 0, M, D, NBODY));
+    MT_TRY(lin_fwd(st, w.X + NBODY, CTOK, th + L.obj_w, th + L.obj_b, w.h[0], D, w.h[0], D, M, D, CTOK - NBODY));
+    hipLaunchKernelGGL(mt_add_temb_pe_kernel, dim3((unsigned)M), dim3(256), 0, st, w.h[0], w.temb, pe, T);
+    IDF_CHECK_LAUNCH();
+    for (int l = 0; l < N_LAYERS; ++l) {
+        const LayerOff &o = L.layer[l];
+        const LayerWs &y = w.layer[l];
+        const float *xin = w.h[l];
+        float *s = w.t[0];                                        // the pre-LayerNorm sums live only until their LayerNorm has run
+        if (is_qan(l)) {
+            hipLaunchKernelGGL(mt_qan_prep_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, y.G);
+            IDF_CHECK_LAUNCH();
+            hipLaunchKernelGGL(mt_qan_fwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, y.G, th + o.wk, s, M, T);
+            IDF_CHECK_LAUNCH();
+        } else {
+            MT_TRY(lin_fwd(st, xin, D, th + o.sa_in_w, th + o.sa_in_b, y.qkv, 3 * D, nullptr, 0, M, 3 * D, D));
+            hipLaunchKernelGGL(mt_self_attn_fwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, y.qkv, y.ao, y.lse, T);
+            IDF_CHECK_LAUNCH();
+            MT_TRY(lin_fwd(st, y.ao, D, th + o.sa_out_w, th + o.sa_out_b, s, D, xin, D, M, D, D));
+        }
+        MT_TRY(ln_fwd(st, s, th + o.ln_w[0], th + o.ln_b[0], y.xh[0], y.rs[0], y.x1, M));
+        // cross-attention on the memory
+        MT_TRY(lin_fwd(st, y.x1, D, th + o.ca_in_w, th + o.ca_in_b, y.q2, D, nullptr, 0, M, D, D));
+        MT_TRY(lin_fwd(st, cond, D, th + o.ca_in_w + (int64_t)D * D, th + o.ca_in_b + D, y.kv, 2 * D, nullptr, 0, SB, 2 * D, D));
+        hipLaunchKernelGGL(mt_cross_attn_fwd_kernel, dim3(blocks256((int64_t)M * HEADS)), dim3(256), 0, st, y.q2, y.kv, y.o2, B, T, S);
+        IDF_CHECK_LAUNCH();
+        MT_TRY(lin_fwd(st, y.o2, D, th + o.ca_out_w, th + o.ca_out_b, s, D, y.x1, D, M, D, D));
+        MT_TRY(ln_fwd(st, s, th + o.ln_w[1], th + o.ln_b[1], y.xh[1], y.rs[1], y.x2, M));
+        // feed-forward
+        MT_TRY(lin_fwd(st, y.x2, D, th + o.l1_w, th + o.l1_b, y.z, FF, nullptr, 0, M, FF, D));
+        hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.g, (int64_t)M * FF);
+        IDF_CHECK_LAUNCH();
+        MT_TRY(lin_fwd(st, w.g, FF, th + o.l2_w, th + o.l2_b, s, D, y.x2, D, M, D, FF));
+        if (is_qan(l)) {
+            MT_TRY(ln_fwd(st, s, th + o.ln_w[2], th + o.ln_b[2], y.xh[2], y.rs[2], w.t[1], M));
+            hipLaunchKernelGGL(mt_round_trip_kernel, dim3(blocks256((int64_t)M * D)), dim3(256), 0, st, xin, w.t[1], w.h[l + 1], (int64_t)M * D);
+            IDF_CHECK_LAUNCH();
+        } else {
+            MT_TRY(ln_fwd(st, s, th + o.ln_w[2], th + o.ln_b[2], y.xh[2], y.rs[2], w.h[l + 1], M));
+        }
+    }
+    MT_TRY(lin_fwd(st, w.h[N_LAYERS], D, th + L.bodyf_w, th + L.bodyf_b, w.Y, CTOK, nullptr, 0, M, NBODY, D));
+    MT_TRY(lin_fwd(st, w.h[N_LAYERS], D, th + L.objf_w, th + L.objf_b, w.Y + NBODY, CTOK, nullptr, 0, M, CTOK - NBODY, D));
+    hipLaunchKernelGGL(mt_rows_to_tokens_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, w.Y, pred, B, T);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+// a linear layer's parameter gradients: dW = dY^T X, db = column sums of dY
+int lin_param_grads(hipStream_t st, const Ws &w, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, float *db, int M, int N, int K) {
+    MT_TRY(lin_dw(st, dY, ldy, X, ldx, dW, M, N, K));
+    return colsum(st, dY, ldy, nullptr, 0, M, N, w.partial, db);
+}
+
+// ---- backward: d_pred [B,1,144,T] -> grads [n_param], d_cond [S][B][256] ------------------------------------------------------------------------------------
+int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *cond, const float *d_pred, int B, int T, int S, float *gr, float *d_cond) {
+    const int M = B * T, SB = S * B;
+    hipLaunchKernelGGL(mt_tokens_to_rows_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, d_pred, w.dY, B, T);
+    IDF_CHECK_LAUNCH();
+    float *Dh = w.t[0], *E = w.t[1], *F = w.t[2], *Gq = w.t[3];
+    // the two output heads
+    MT_TRY(lin_param_grads(st, w, w.dY, CTOK, w.h[N_LAYERS], D, gr + L.bodyf_w, gr + L.bodyf_b, M, NBODY, D));
+    MT_TRY(lin_param_grads(st, w, w.dY + NBODY, CTOK, w.h[N_LAYERS], D, gr + L.objf_w, gr + L.objf_b, M, CTOK - NBODY, D));
+    MT_TRY(lin_dx(st, w.dY, CTOK, th + L.bodyf_w, Dh, D, nullptr, 0, M, NBODY, D));
+    MT_TRY(lin_dx(st, w.dY + NBODY, CTOK, th + L.objf_w, Dh, D, Dh, D, M, CTOK - NBODY, D));
+    bool first_cond = true;
+    for (int l = N_LAYERS - 1; l >= 0; --l) {
+        const LayerOff &o = L.layer[l];
+        const LayerWs &y = w.layer[l];
+        const float *xin = w.h[l];
+        // Dh = d (LayerNorm3 output): for a QaN layer the backward of tgt + (x - tgt) is the identity on x and nothing on tgt
+        MT_TRY(ln_bwd(st, Dh, y.xh[2], y.rs[2], th + o.ln_w[2], gr + o.ln_w[2], gr + o.ln_b[2], E, w.partial, M));            // E = d s3 = d ffn-out = d x2 (residual)
+        // feed-forward
+        hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.g, (int64_t)M * FF);
+        IDF_CHECK_LAUNCH();
+        MT_TRY(lin_param_grads(st, w, E, D, w.g, FF, gr + o.l2_w, gr + o.l2_b, M, D, FF));
+        MT_TRY(lin_dx(st, E, D, th + o.l2_w, w.dz, FF, nullptr, 0, M, D, FF));
+        hipLaunchKernelGGL(mt_gelu_bwd_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.dz, (int64_t)M * FF);
+        IDF_CHECK_LAUNCH();
+        MT_TRY(lin_param_grads(st, w, w.dz, FF, y.x2, D, gr + o.l1_w, gr + o.l1_b, M, FF, D));
+        MT_TRY(lin_dx(st, w.dz, FF, th + o.l1_w, F, D, E, D, M, FF, D));                                                        // F = d x2
+        MT_TRY(ln_bwd(st, F, y.xh[1], y.rs[1], th + o.ln_w[1], gr + o.ln_w[1], gr + o.ln_b[1], E, w.partial, M));              // E = d s2 = d x1 (residual)
+        // cross-attention
+        MT_TRY(lin_param_grads(st, w, E, D, y.o2, D, gr + o.ca_out_w, gr + o.ca_out_b, M, D, D));
+        MT_TRY(lin_dx(st, E, D, th + o.ca_out_w, F, D, nullptr, 0, M, D, D));                                                    // F = d o2
+        hipLaunchKernelGGL(mt_cross_attn_bwd_q_kernel, dim3(blocks256((int64_t)M * HEADS)), dim3(256), 0, st, y.q2, y.kv, F, Gq, w.Pc, w.dSc, B, T, S);
+        IDF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(mt_cross_attn_bwd_kv_kernel, dim3(blocks256((int64_t)SB * 2 * D)), dim3(256), 0, st, y.q2, F, w.Pc, w.dSc, w.dkv, B, T, S);
+        IDF_CHECK_LAUNCH();
+        MT_TRY(lin_param_grads(st, w, Gq, D, y.x1, D, gr + o.ca_in_w, gr + o.ca_in_b, M, D, D));
+        MT_TRY(lin_param_grads(st, w, w.dkv, 2 * D, cond, D, gr + o.ca_in_w + (int64_t)D * D, gr + o.ca_in_b + D, SB, 2 * D, D));
+        MT_TRY(lin_dx(st, w.dkv, 2 * D, th + o.ca_in_w + (int64_t)D * D, d_cond, D, first_cond ? nullptr : d_cond, D, SB, 2 * D, D));   // layers 7 .. 0 in this order
+        first_cond = false;
+        MT_TRY(lin_dx(st, Gq, D, th + o.ca_in_w, F, D, E, D, M, D, D));                                                          // F = d x1
+        MT_TRY(ln_bwd(st, F, y.xh[0], y.rs[0], th + o.ln_w[0], gr + o.ln_w[0], gr + o.ln_b[0], E, w.partial, M));              // E = d s1
+        if (is_qan(l)) {
+            hipLaunchKernelGGL(mt_qan_bwd_token_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, y.G, th + o.wk, E, w.dsim, w.cj, w.dwk_tok, M, T);
+            IDF_CHECK_LAUNCH();
+            hipLaunchKernelGGL(mt_qan_bwd_gather_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, E, y.G, w.dsim, w.cj, Dh, M, T);
+            IDF_CHECK_LAUNCH();
+            // dG[j][n] = sum_t dsim[t][n][j] x[t-1+j]: slot 0 pairs token t with frame t-1 (rows 1.., a clip's first token is masked: dsim = 0), slot 2 with t+1
+            MT_TRY(gemm(st, w.dsim + NQ * SLOTS, SLOTS, NQ * SLOTS, xin, D, 1, w.dG, D, nullptr, nullptr, 0, NQ, D, M - 1));
+            MT_TRY(gemm(st, w.dsim + 1, SLOTS, NQ * SLOTS, xin, D, 1, w.dG + (int64_t)NQ * D, D, nullptr, nullptr, 0, NQ, D, M));
+            MT_TRY(gemm(st, w.dsim + 2, SLOTS, NQ * SLOTS, xin + D, D, 1, w.dG + (int64_t)2 * NQ * D, D, nullptr, nullptr, 0, NQ, D, M - 1));
+            hipLaunchKernelGGL(mt_qan_dqueries_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, w.dG, gr + o.queries);
+            IDF_CHECK_LAUNCH();
+            MT_TRY(colsum(st, w.dwk_tok, NQ, nullptr, 0, M, NQ, w.partial, gr + o.wk));
+        } else {
+            MT_TRY(lin_param_grads(st, w, E, D, y.ao, D, gr + o.sa_out_w, gr + o.sa_out_b, M, D, D));
+            MT_TRY(lin_dx(st, E, D, th + o.sa_out_w, F, D, nullptr, 0, M, D, D));                                                // F = d (attention output)
+            hipLaunchKernelGGL(mt_self_attn_bwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, y.qkv, y.ao, y.lse, F, w.dqkv, w.P,
+                               w.dS, T);
+            IDF_CHECK_LAUNCH();
+            MT_TRY(lin_param_grads(st, w, w.dqkv, 3 * D, xin, D, gr + o.sa_in_w, gr + o.sa_in_b, M, 3 * D, D));
+            MT_TRY(lin_dx(st, w.dqkv, 3 * D, th + o.sa_in_w, Dh, D, E, D, M, 3 * D, D));
+        }
+    }
+    // embedding and the timestep MLP: Dh = d h0
+    MT_TRY(lin_param_grads(st, w, Dh, D, w.X, CTOK, gr + L.body_w, gr + L.body_b, M, D, NBODY));
+    MT_TRY(lin_param_grads(st, w, Dh, D, w.X + NBODY, CTOK, gr + L.obj_w, gr + L.obj_b, M, D, CTOK - NBODY));
+    hipLaunchKernelGGL(mt_sum_frames_kernel, dim3((unsigned)B), dim3(256), 0, st, Dh, w.dtemb, T);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, w.dtemb, D, w.sz, D, gr + L.t2_w, gr + L.t2_b, B, D, D));
+    MT_TRY(lin_dx(st, w.dtemb, D, th + L.t2_w, w.dsz, D, nullptr, 0, B, D, D));
+    hipLaunchKernelGGL(mt_silu_bwd_kernel, dim3(blocks256((int64_t)B * D)), dim3(256), 0, st, w.z0, w.dsz, (int64_t)B * D);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, w.dsz, D, w.tin, D, gr + L.t0_w, gr + L.t0_b, B, D, D));
+    return IDF_OK;
+}
+
+bool shape_ok(int B, int T, int S, int past_len) {
+    return B > 0 && T > 0 && T <= MAX_T && S > 0 && S <= MAX_MEM && past_len >= 2 && T >= past_len + 2 && (int64_t)B * T * FF < 0x7FFFFFFF;
+}
+
+}  // namespace
+
+extern "C" int interdiff_denoising_loss_grad(const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, float *d_pred,
+                                             void *stream) {
+    if (!pred || !target || !weights16 || !d_pred || B <= 0 || past_len < 2 || T < past_len + 2) return IDF_E_INVAL;
+    return loss_grad(idf_stream(stream), pred, target, B, T, past_len, weights16, d_pred);
+}
+
+extern "C" int interdiff_mdm_train_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
+    const Layout &L = layout();
+    for (int i = 0; i < N_TENSORS; ++i) {
+        if (offsets) offsets[i] = L.off[i];
+        if (sizes) sizes[i] = L.size[i];
+    }
+    if (n_tensors) *n_tensors = N_TENSORS;
+    if (n_param) *n_param = L.total;
+    return IDF_OK;
+}
+
+extern "C" size_t interdiff_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t mem_len) {
+    if (B <= 0 || T <= 0 || T > MAX_T || mem_len <= 0 || mem_len > MAX_MEM || (int64_t)B * T * FF >= 0x7FFFFFFF) return 0;
+    return plan(nullptr, B, T, mem_len).floats * sizeof(float);
+}
+
+extern "C" int interdiff_mdm_train_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *cond, const float *target,
+                                         int32_t B, int32_t T, int32_t mem_len, int32_t past_len, const float *weights16, const float *d_pred_in, float *grads,
+                                         float *d_cond, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !pe || !x_t || !ts || !cond || !target || !weights16 || !grads || !d_cond || !pred || !terms || !ws) return IDF_E_INVAL;
+    if (!shape_ok(B, T, mem_len, past_len) || pe_rows < T) return IDF_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
+    if (ws_bytes < interdiff_mdm_train_workspace_bytes(B, T, mem_len)) return IDF_E_NOMEM;
+    hipStream_t st = idf_stream(stream);
+    const Layout &L = layout();
+    const Ws w = plan(static_cast<float *>(ws), B, T, mem_len);
+    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, mem_len, pred));
+    MT_TRY(interdiff_denoising_losses(pred, target, B, T, past_len, terms, stream));
+    const float *dp = d_pred_in;
+    if (!dp) {
+        float *mine = w.g;                                        // (free between the forward and the backward; M * 1024 >= B * 144 * T floats)
+        MT_TRY(loss_grad(st, pred, target, B, T, past_len, weights16, mine));
+        dp = mine;
+    }
+    return backward(st, L, w, params, cond, dp, B, T, mem_len, grads, d_cond);
+}
+
+extern "C" int interdiff_mdm_train_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, double lr, double beta1,
+                                        double beta2, double eps, double weight_decay, void *stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return IDF_E_INVAL;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    AdamWK k;
+    k.decay = (float)(1.0 - lr * weight_decay);
+    k.w1 = (float)(1.0 - beta1);
+    k.beta2 = (float)beta2;
+    k.w2 = (float)(1.0 - beta2);
+    k.step_size = (float)(lr / bc1);
+    k.bc2_sqrt = (float)sqrt(bc2);
+    k.eps = (float)eps;
+    hipLaunchKernelGGL(mt_adamw_kernel, dim3(blocks256(n)), dim3(256), 0, idf_stream(stream), params, grads, exp_avg, exp_avg_sq, n, k);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}

@@ -1,0 +1,317 @@
+"""The denoiser trainer (interdiff_amd/mdm_train.py, csrc/mdm_train.h / .hip): the backward of MDM.forward under the loss of forward_backward, and AdamW,
+against the fp64 oracle tests/mdm_train_oracle.py and the reference's OWN fp32 run recorded by tests/golden/make_golden_mdm_train.py
+(tests/golden/mdm_train_{A,B,traj}.npz: the reference module under its own forward_backward with autograd on, torch.optim.AdamW).
+
+Gradient gate (the project's): per tensor max|g - g64| / max|g64| <= max(4 e_ref, 1e-5), e_ref = the same measure of the reference's fp32 gradient against
+the fp64 oracle, recorded per tensor; the recorder asserts 4 e_ref <= 1e-4 everywhere.  Loss and terms: 1e-5 relative to fp64.  pred: the flat 1e-4 against
+MDM.forward.  Trajectory: 6 AdamW steps, losses 1e-5 relative, at most 0.1 % of the 7,069,900 parameters further than 8 y_traj from the fp64 trajectory
+(y_traj = the reference's own fp32 distance; a cap, not a measurement).  Bit-identity claims are ``torch.equal``.  Every figure is printed before it is asserted.
+
+Points: A  B = 4, T = 35, t = [37, 412, 655, 999] (M = 140 rows);  B  B = 3, T = 100, t = [0, 500, 999] (M = 300: self-attention over more than one 64-key tile,
+t = 0, an odd batch).  Weights: fixtures.mdm_weights_wc(), with the rows of the sinusoidal table that the reference runs read taken from the recordings (``weights()``:
+sin / cos of fp32 arguments differ in the last bits between CPUs, and e_ref is that small).  Without the feature this module fails at import (interdiff_amd.mdm_train does not exist).
+"""
+import os
+import re
+import numpy as np
+import pytest
+import torch
+from tests import fixtures as fx
+from tests import losses_oracle as lo
+from tests import mdm_train_oracle as mo
+from interdiff_amd.mdm_train import PARAM_NAMES
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
+DEV = 'cuda'
+N_PARAM = 7069900
+FLOOR = 1e-5
+NEW_SYMBOLS = {
+    'interdiff_denoising_loss_grad': 'const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, float *d_pred, void *stream',
+    'interdiff_mdm_train_param_table': 'int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param',
+    'interdiff_mdm_train_workspace_bytes': 'int32_t B, int32_t T, int32_t mem_len',
+    'interdiff_mdm_train_grads': 'const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *cond, const float *target, '
+                                 'int32_t B, int32_t T, int32_t mem_len, int32_t past_len, const float *weights16, const float *d_pred_in, float *grads, float *d_cond, '
+                                 'float *pred, float *terms, void *ws, size_t ws_bytes, void *stream',
+    'interdiff_mdm_train_step': 'float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, double lr, double beta1, double beta2, '
+                                'double eps, double weight_decay, void *stream',
+}
+
+
+def tn(a):
+    return torch.from_numpy(np.asarray(a))
+
+
+def rel(a, b):
+    a, b = (x.detach().cpu().double() if isinstance(x, torch.Tensor) else tn(x).double() for x in (a, b))
+    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
+
+
+def betas():
+    from interdiff_amd.diffusion import get_named_beta_schedule
+    return get_named_beta_schedule('cosine', 1000, 1.)
+
+
+_POINTS = {}
+
+
+def weights():
+    """fixtures.mdm_weights_wc() with the positional-table rows the reference runs read (all three recordings; they agree where they overlap)."""
+    files = [fx.golden('mdm_train_%s.npz' % n) for n in ('A', 'B', 'traj')]
+    return mo.with_pe_rows(fx.mdm_weights_wc(), *[(z['pe_idx'], z['pe_val']) for z in files])
+
+
+def point(name):
+    """The recorded inputs of a point and the fp64 oracle on them, computed once per process and never modified."""
+    if name not in _POINTS:
+        z = fx.golden('mdm_train_%s.npz' % name)
+        z = {k: z[k] for k in z.files}
+        x0, cond, t, eps = tn(z['x0']), tn(z['cond']), tn(z['t']), tn(z['eps'])
+        x_t = lo.q_sample(betas(), x0, t, eps)
+        ref = mo.grads(weights(), x_t, t, cond, x0, int(z['past_len']))
+        e_ref = dict(zip([str(k) for k in z['names']], z['e_ref']))
+        _POINTS[name] = dict(z=z, x0=x0, cond=cond, t=t, eps=eps, x_t=x_t, ref=ref, e_ref=e_ref)
+    return _POINTS[name]
+
+
+def gate(e_ref):
+    return max(4.0 * float(e_ref), FLOOR)
+
+
+# ------------------------------------------------------------------------------------------------------------ CPU
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_oracle_vs_reference_samples(name):
+    """The fp64 oracle against every 64th entry of the reference's own fp32 gradients, within the recorded e_ref (which is the reference's distance over ALL
+    entries, so the sampled distance cannot exceed it but for the rounding of the two products below), and the recorded fp32 loss."""
+    p = point(name)
+    z, ref, stride = p['z'], p['ref'], int(p['z']['stride'])
+    assert [str(k) for k in z['names']] == list(PARAM_NAMES) + ['d_cond', 'd_pred']
+    assert 4 * float(z['e_ref'].max()) <= 1e-4
+    at, worst = 0, 0.0
+    for k in PARAM_NAMES:
+        g = ref['grads'][k].reshape(-1)[::stride]
+        s = tn(z['ref_grad_samples'][at:at + g.numel()]).double()
+        at += g.numel()
+        e = float((s - g).abs().max() / ref['grads'][k].abs().max())
+        worst = max(worst, e / p['e_ref'][k])
+        assert e <= 1.01 * p['e_ref'][k], k                                 # (1.01: the recorder's own assertion; fp64 sums differ in the last bits between machines)
+        assert float(ref['grads'][k].abs().max()) > 0
+    assert at == len(z['ref_grad_samples'])
+    for key, samples in (('d_cond', 'ref_d_cond_samples'), ('d_pred', 'ref_d_pred_samples')):
+        g = ref[key].reshape(-1)
+        e = float((tn(z[samples]).double() - g[::stride]).abs().max() / g.abs().max())
+        assert e <= 1.01 * p['e_ref'][key], key
+    el = abs(float(ref['loss']) - float(z['ref_loss'])) / float(ref['loss'])
+    w = torch.tensor(lo.weight_vector(), dtype=torch.float64)[:, None]
+    ew = rel(tn(z['ref_weighted']), ref['terms'] * w)
+    print('point %s: sampled reference vs oracle: worst e / e_ref %.3f; loss %.2e, weighted terms %.2e' % (name, worst, el, ew))
+    assert el <= 1e-5 and ew <= 1e-5
+
+
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_closed_form_d_pred_vs_autograd(name):
+    p = point(name)
+    e = rel(mo.d_pred_closed_form(p['ref']['pred'], p['x0'].double(), 10), p['ref']['d_pred'])
+    print('point %s: closed-form d_pred vs autograd (fp64): %.2e' % (name, e))
+    assert e <= 1e-12
+    # other weights and another past length take the same form
+    g = torch.Generator().manual_seed(5)
+    gt = torch.randn(2, 1, 144, 17, generator=g, dtype=torch.float64)
+    pred = gt + 0.3 * torch.randn(2, 1, 144, 17, generator=g, dtype=torch.float64)
+    wts = dict(weight_smplx_rot=0.7, weight_smplx_nonrot=1.3, weight_obj_rot=0.4, weight_obj_nonrot=2.0, weight_past=0.5, weight_v=3.0)
+    with torch.enable_grad():
+        pr = pred.clone().requires_grad_(True)
+        auto = torch.autograd.grad(mo.loss_of(pr, gt, 4, wts)[0], pr)[0]
+    assert rel(mo.d_pred_closed_form(pred, gt, 4, wts), auto) <= 1e-12
+
+
+def test_new_symbols_declared_typed_and_exported():
+    """Fails on the parent commit: the entries do not exist there."""
+    from interdiff_amd import _lib
+    src = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'include', 'interdiff_hip.h')).read())
+    for name, args in NEW_SYMBOLS.items():
+        assert '%s(%s);' % (name, args) in src, name
+        assert name in _lib._SIGS and len(_lib._SIGS[name][1]) == args.count(',') + 1, name
+    lib = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert hasattr(lib, name)
+    assert lib.interdiff_abi_version() == _lib.ABI_VERSION == 17          # additive entries: the ABI version does not move
+    assert 'mdm_train.hip' in __import__('interdiff_amd.csrc.build', fromlist=['sources']).sources()
+
+
+def test_param_table_covers_the_144_names():
+    from interdiff_amd.mdm_train import param_table
+    sd = fx.mdm_weights()
+    carried = ('finalLinear.', 'bodyFutureEmbedding.', 'objFutureEmbedding.', 'PositionalEmbedding.', 'encoder.', 'pcEmbedding.')
+    assert sorted(PARAM_NAMES) == sorted(k for k in sd if not k.startswith(carried))
+    assert len(PARAM_NAMES) == len(set(PARAM_NAMES)) == 144
+    off, size, n = param_table()
+    assert n == N_PARAM == sum(sd[k].numel() for k in PARAM_NAMES)
+    at = 0
+    for k, o, s in zip(PARAM_NAMES, off, size):                            # in order, back to back: no overlap, no gap
+        assert o == at and s == sd[k].numel(), k
+        at += s
+    assert at == n
+
+
+def test_constructor_refuses_dropout_and_condition_masking():
+    from interdiff_amd.mdm_train import DenoiserTrainer
+    for kw in (dict(dropout=0.1), dict(cond_mask_prob=0.1)):
+        with pytest.raises(ValueError):
+            DenoiserTrainer(fx.mdm_weights_wc(), device='cpu', **kw)
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU
+
+def new_trainer(**kw):
+    from interdiff_amd.mdm_train import DenoiserTrainer
+    return DenoiserTrainer(weights(), device=DEV, **kw)
+
+
+@pytest.fixture(scope='module')
+def trainer(lib):
+    return new_trainer()                                                   # never stepped: every test that steps builds its own
+
+
+def on_dev(p):
+    return {k: p[k].to(DEV) for k in ('x0', 'cond', 't', 'eps', 'x_t')}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_loss_grad_entry_vs_closed_form(trainer, name):
+    p = point(name)
+    want = mo.d_pred_closed_form(p['ref']['pred'], p['x0'].double(), 10)
+    got = trainer.loss_grad(p['ref']['pred'].float().to(DEV), p['x0'].to(DEV))
+    e, g = rel(got, want), gate(p['e_ref']['d_pred'])
+    print('point %s: interdiff_denoising_loss_grad vs the fp64 closed form: %.3e (gate %.1e)' % (name, e, g))
+    assert e <= g
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['A', 'B'])
+def test_gradients_vs_fp64(trainer, name):
+    from interdiff_amd.mdm import MDM
+    p, d = point(name), on_dev(point(name))
+    ref = p['ref']
+    loss, ld, wd, grads, d_cond = trainer.loss_and_grads(dict(gt=d['x0'], cond=d['cond']), t=d['t'], noise=d['eps'])
+    worst, worst_frac, bad = 0.0, 0.0, []
+    for k in PARAM_NAMES:
+        e, g = rel(grads[k], ref['grads'][k]), gate(p['e_ref'][k])
+        worst, worst_frac = max(worst, e), max(worst_frac, e / g)
+        if e > g:
+            bad.append('%s %.3e > %.1e' % (k, e, g))
+    ec, gc = rel(d_cond, ref['d_cond']), gate(p['e_ref']['d_cond'])
+    print('point %s: 144 gradient tensors: worst rel err %.3e, worst fraction of its gate %.3f; d_cond %.3e (gate %.1e)' % (name, worst, worst_frac, ec, gc))
+    assert not bad, bad
+    assert ec <= gc
+    el = abs(float(loss.double().mean()) - float(ref['loss'])) / float(ref['loss'])
+    terms = torch.stack([ld[k] for k in lo.LOSS_KEYS])
+    et = max(rel(terms[i], ref['terms'][i]) for i in range(16))
+    print('point %s: loss %.3e, worst of 16 terms %.3e (gate 1e-5)' % (name, el, et))
+    assert el <= 1e-5 and et <= 1e-5
+    w = torch.tensor(lo.weight_vector(), dtype=torch.float64)
+    assert rel(torch.stack([wd[k] for k in lo.LOSS_KEYS]), ref['terms'] * w[:, None]) <= 1e-5
+    fwd = MDM(weights(), device=DEV)(trainer.diffusion.q_sample(d['x0'], d['t'], noise=d['eps']), d['t'], y={'cond': d['cond']})
+    ep, e64 = rel(trainer.pred, fwd), rel(trainer.pred, ref['pred'])
+    print('point %s: pred vs MDM.forward %.3e (gate 1e-4), vs fp64 %.3e' % (name, ep, e64))
+    assert ep <= 1e-4
+
+
+@pytest.mark.gpu
+def test_two_calls_give_identical_bits(trainer):
+    d = on_dev(point('B'))
+    a = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'])
+    ga = trainer.grads.clone()
+    b = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'])
+    assert torch.equal(ga, trainer.grads) and all(torch.equal(x, y) for x, y in zip(a, b))        # flat gradient; pred, terms, d_cond
+
+
+@pytest.mark.gpu
+def test_d_pred_seam(trainer):
+    d = on_dev(point('A'))
+    pred, _, dc0 = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'])
+    g0 = trainer.grads.clone()
+    dp = trainer.loss_grad(pred, d['x0'])
+    _, _, dc1 = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'], d_pred=dp)
+    assert torch.equal(g0, trainer.grads) and torch.equal(dc0, dc1)        # the default path IS the loss-gradient entry's output fed to the seam
+    _, _, dc2 = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'], d_pred=2 * dp)
+    assert torch.equal(2 * g0, trainer.grads) and torch.equal(2 * dc0, dc2)                        # the backward is linear in d_pred, bit for bit
+
+
+@pytest.fixture(scope='module')
+def traj():
+    """The recorded per-step t / noise and the fp64 oracle's trajectory on them, computed once."""
+    z = fx.golden('mdm_train_traj.npz')
+    z = {k: z[k] for k in z.files}
+    p = point('A')
+    ts, noises = [tn(t) for t in z['t']], [tn(e) for e in z['noise']]
+    losses, theta = mo.trajectory(weights(), betas(), p['x0'], p['cond'], ts, noises, 10, lr=float(z['lr']))
+    return dict(z=z, ts=ts, noises=noises, losses=losses, theta=theta)
+
+
+def test_oracle_trajectory_vs_reference_samples(traj):
+    """CPU: the fp64 trajectory against every 64th entry of the reference's final fp32 parameters, within the recorded y_traj, and its losses."""
+    z, stride = traj['z'], int(traj['z']['stride'])
+    flat = torch.cat([traj['theta'][k].reshape(-1)[::stride] for k in PARAM_NAMES])
+    d = float((tn(z['ref_theta_samples']).double() - flat).abs().max())
+    el = max(abs(a - float(b)) / a for a, b in zip(traj['losses'], z['ref_losses']))
+    print('trajectory: sampled reference theta vs fp64 %.3e (y_traj %.3e); losses %.2e' % (d, float(z['y_traj']), el))
+    assert d <= 1.01 * float(z['y_traj']) and el <= 1e-5
+
+
+@pytest.mark.gpu
+def test_trajectory_vs_fp64(lib, traj):
+    p, z = on_dev(point('A')), traj['z']
+    tr = new_trainer(lr=float(z['lr']))
+    batch = dict(gt=p['x0'], cond=p['cond'])
+    for k, (t, eps) in enumerate(zip(traj['ts'], traj['noises'])):
+        loss = tr.training_step(batch, t=t.to(DEV), noise=eps.to(DEV))[0]
+        e = abs(float(loss.double().mean()) - traj['losses'][k]) / traj['losses'][k]
+        print('step %d: loss %.6f, rel err vs fp64 %.2e (gate 1e-5)' % (k + 1, float(loss.mean()), e))
+        assert e <= 1e-5
+    got = tr.state_dict()
+    y = float(z['y_traj'])
+    far, worst = 0, 0.0
+    for k in PARAM_NAMES:
+        d = (got[k].cpu().double() - traj['theta'][k]).abs()
+        far += int((d > 8 * y).sum())
+        worst = max(worst, float(d.max()))
+    print('trajectory: %d of %d parameters further than 8 y_traj = %.3e from fp64 (cap %d); max distance %.3e' % (far, N_PARAM, 8 * y, N_PARAM // 1000, worst))
+    assert far <= N_PARAM // 1000
+
+
+@pytest.mark.gpu
+def test_plumbing(lib, traj):
+    from interdiff_amd.mdm_train import DenoiserTrainer
+    p = on_dev(point('A'))
+    sd = weights()
+    batch = dict(gt=p['x0'], cond=p['cond'])
+    step = lambda tr, k: tr.training_step(batch, t=traj['ts'][k].to(DEV), noise=traj['noises'][k].to(DEV))
+    a = new_trainer()
+    step(a, 0), step(a, 1)
+    # state + optimizer state continue the trajectory bit for bit
+    b = DenoiserTrainer(a.state_dict(), device=DEV)
+    b.load_optimizer_state(a.optimizer_state())
+    assert b.step == 2 and torch.equal(a.params, b.params)
+    step(a, 2), step(b, 2)
+    assert torch.equal(a.params, b.params) and torch.equal(a.exp_avg, b.exp_avg) and torch.equal(a.exp_avg_sq, b.exp_avg_sq)
+    assert not torch.equal(a.params, new_trainer().params)
+    # the untouched tensors come back with identical bits, the trained ones under the reference's names and shapes
+    out = a.state_dict()
+    assert set(out) == set(sd)
+    carried = [k for k in sd if k not in PARAM_NAMES]
+    assert 'encoder.layers.3.queries' in carried and 'pcEmbedding.Linear.weight' in carried
+    for k in carried:
+        assert torch.equal(out[k], sd[k]), k
+    assert all(out[k].shape == sd[k].shape for k in PARAM_NAMES)
+    # the exported sampler model computes what the trainer's forward computes
+    loss = a.loss_and_grads(batch, t=p['t'], noise=p['eps'])[0]
+    fwd = a.export_mdm()(a.diffusion.q_sample(p['x0'], p['t'], noise=p['eps']), p['t'], y={'cond': p['cond']})
+    e = rel(a.pred, fwd)
+    print('export_mdm().forward vs the trainer\'s pred after 3 steps: %.3e (gate 1e-4); loss %.4f' % (e, float(loss.mean())))
+    assert e <= 1e-4
+    # T > 128 is refused
+    big = torch.zeros(1, 1, 144, 129, device=DEV)
+    with pytest.raises(ValueError):
+        a.loss_and_grads(dict(gt=big, cond=torch.zeros(10, 1, 256, device=DEV)), t=torch.zeros(1, dtype=torch.int64))
