@@ -863,6 +863,37 @@ int interdiff_mdm_train_step(float *params, const float *grads, float *exp_avg, 
                              double beta1, double beta2, double eps, double weight_decay, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * TRAINING of the SMPL denoiser's ENCODER as well (same files): the backward of MDM._get_embeddings from pc_embedding on
+ * (model/diffusion_smpl.py:217-221: bodyEmbedding(body[:past]) + objEmbedding(obj[:past]) + pc_embedding, PositionalEmbedding, self.encoder =
+ * [std, QaN x6, std] post-norm layers without cross-attention and without a final norm, :20-70, sublayers.py:37-204, layers.py:198-217), chained
+ * behind the decoder's through d_cond -- what LitInteraction._common_step (train_diffusion_smpl.py:381-388) gets from calling
+ * self.model._get_embeddings(batch) with autograd on.  Additive; same arithmetic contract as above.
+ *
+ * FULL PARAMETER TABLE.  The flat vectors hold 228 tensors: the 144 above at their offsets, then the 84 encoder tensors, per encoder layer 0..7:
+ *     layers 0, 7: self_attn.in_proj_weight, self_attn.in_proj_bias, self_attn.out_proj.weight, self_attn.out_proj.bias;   layers 1..6: queries, wk;
+ *     then linear1.{weight,bias}, linear2.{weight,bias}, norm1.{weight,bias}, norm2.{weight,bias}
+ * (2 x 789 760 + 6 x 529 162 = 4 754 492 floats; n_param = 11 824 392).  bodyEmbedding / objEmbedding receive the sum of both paths, the decoder
+ * path's contribution first and the encoder path's added to it.
+ *
+ *  interdiff_mdm_train_full_param_table   as interdiff_mdm_train_param_table for the 228 tensors (HOST int64 [228], nullable).
+ *  interdiff_mdm_train_full_workspace_bytes   workspace of interdiff_mdm_train_full_grads; 0 for an unsupported shape.
+ *  interdiff_mdm_train_full_grads    the arguments of interdiff_mdm_train_grads with pc [B][256] (pc_embedding, the output of
+ *      interdiff_pointnet2_encode: the input seam of this pass) in the place of cond, and mem_len = past_len: the encoder's tokens are the past
+ *      frames target[..., :past_len].  Encoder forward -> decoder forward -> terms -> decoder backward -> encoder backward.  -> pred, terms,
+ *      grads [n_param of the full table], cond [past_len][B][256] (the encoder's output, as MDM._get_embeddings returns it), d_cond (as above),
+ *      d_pc [B][256] = d embedding summed over a clip's past_len tokens in token order (the seam a backward of pcEmbedding would take).
+ *      pred, terms, d_cond and the gradients of the tensors only the decoder reads have the bits interdiff_mdm_train_grads gives on that cond.
+ *      T <= 128, 2 <= past_len <= 16, T >= past_len + 2; IDF_E_INVAL otherwise.
+ *  interdiff_mdm_train_step serves the longer vectors as it is (n = the full n_param).
+ * ---------------------------------------------------------------------------------- */
+int interdiff_mdm_train_full_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param);
+size_t interdiff_mdm_train_full_workspace_bytes(int32_t B, int32_t T, int32_t past_len);
+int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *pc,
+                                   const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, const float *d_pred_in,
+                                   float *grads, float *cond, float *d_cond, float *d_pc, float *pred, float *terms, void *ws, size_t ws_bytes,
+                                   void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Scoring of a skeleton diffusion checkpoint (csrc/skeleton_losses.hip): the forward, scoring side of interdiff/train_diffusion_skeleton.py.
  * Forward only, additive.  Tokens [B,1,C,T] with C = n_body + 3 * n_points + 7 (63 + 36 + 7 = 106): body | object keypoints | object
  * translation 3 | object quaternion xyzw 4.  The keypoint channels are the prediction's own (the denoiser's keypoint head wrote them): nothing is

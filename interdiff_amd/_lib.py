@@ -196,6 +196,9 @@ _SIGS = {
     'interdiff_mdm_train_workspace_bytes': (sz, [i32, i32, i32]),
     'interdiff_mdm_train_grads': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_mdm_train_step': (C.c_int, [vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+    'interdiff_mdm_train_full_param_table': (C.c_int, [C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
+    'interdiff_mdm_train_full_workspace_bytes': (sz, [i32, i32, i32]),
+    'interdiff_mdm_train_full_grads': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_sample_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),

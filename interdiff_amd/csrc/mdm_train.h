@@ -1,6 +1,7 @@
 // Training of the SMPL denoiser's decoder: device code of the forward with saves, the backward of MDM.forward (model/diffusion_smpl.py:226-246: embedding,
 // timestep MLP, [std, QaN x6, std] decoder layers, the two output heads) under the loss of LitInteraction.forward_backward (train_diffusion_smpl.py:60-166),
-// and AdamW (:177-183).  Launchers: csrc/mdm_train.hip.
+// and AdamW (:177-183); and of the encoder side, MDM._get_embeddings from pc_embedding on (:217-221), which runs the same sublayers on past_len tokens per clip.
+// Launchers: csrc/mdm_train.hip.
 // Arithmetic: exact fp32 only -- every matrix product is v_mfma_f32_16x16x4_f32 (a k-ordered fp32 fma chain, four independent accumulators per wave), everything
 // else VALU.  No f16 MFMA, so the exclusive-CU rule (common.h) puts no obligation on these kernels.  No float atomics: a sum across workgroups is a partial-slab store
 // plus a fixed-order reducer (mt_colsum_*), every other sum is owned by one thread or one wave -- two calls give the same bits.
@@ -154,12 +155,12 @@ __global__ __launch_bounds__(256) void mt_gather_pe_kernel(const float *__restri
     t = t < 0 ? 0 : (t >= pe_rows ? pe_rows - 1 : t);
     out[(int64_t)blockIdx.x * D + threadIdx.x] = pe[t * D + threadIdx.x];
 }
-// h[r] += temb[b] + pe[t]
+// h[r] += temb[b] + pe[t].  Second use: the encoder's input embedding, with pc_embedding [B][256] as temb and T = past_len (diffusion_smpl.py:219-220)
 __global__ __launch_bounds__(256) void mt_add_temb_pe_kernel(float *__restrict__ h, const float *__restrict__ temb, const float *__restrict__ pe, int T) {
     const int r = blockIdx.x, b = r / T, t = r % T, c = threadIdx.x;
     h[(int64_t)r * D + c] = (h[(int64_t)r * D + c] + temb[(int64_t)b * D + c]) + pe[(int64_t)t * D + c];
 }
-// d temb[b] = sum_t d h[b*T + t], frames in ascending order
+// d temb[b] = sum_t d h[b*T + t], frames in ascending order.  Second use: d pc_embedding[b] = the encoder's d embedding summed over a clip's past_len tokens
 __global__ __launch_bounds__(256) void mt_sum_frames_kernel(const float *__restrict__ dh, float *__restrict__ out, int T) {
     const int b = blockIdx.x, c = threadIdx.x;
     float s = 0.f;
@@ -601,6 +602,27 @@ __global__ __launch_bounds__(256) void mt_loss_grad_kernel(const float *__restri
     if (cm != 0.f) acc -= cm * e(t - 1);
     if (cp != 0.f) acc -= cp * e(t + 1);
     dpred[i] = 2.f * acc / (float)B;
+}
+
+// ---------------------------------------------------------------------------------------------- encoder (_get_embeddings)
+// The encoder's token input is the past frames of x_start: rows[b*S + s][c] = target[b][c][s] of a [B][144][T] tensor (clip-major rows, like the decoder's).
+__global__ __launch_bounds__(256) void mt_gather_past_kernel(const float *__restrict__ target, float *__restrict__ rows, int B, int T, int S) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * S * CTOK) return;
+    const int c = (int)(i % CTOK);
+    const int64_t r = i / CTOK;
+    const int s = (int)(r % S), b = (int)(r / S);
+    rows[i] = target[((int64_t)b * CTOK + c) * T + s];
+}
+// [P][Q] rows of 256 -> [Q][P]: the encoder's clip-major output to cond's [S][B] order, and d_cond back
+__global__ __launch_bounds__(256) void mt_swap_rows_kernel(const float *__restrict__ in, float *__restrict__ out, int P, int Q) {
+    const int r = blockIdx.x, p = r / Q, q = r % Q, c = threadIdx.x;
+    out[((int64_t)q * P + p) * D + c] = in[(int64_t)r * D + c];
+}
+// dst[i] = dst[i] + src[i]: the encoder path's gradient of the shared bodyEmbedding / objEmbedding added to the decoder path's, in that order
+__global__ __launch_bounds__(256) void mt_add_into_kernel(float *__restrict__ dst, const float *__restrict__ src, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = dst[i] + src[i];
 }
 
 // ------------------------------------------------------------------------------------------------------------------ AdamW

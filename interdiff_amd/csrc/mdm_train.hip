@@ -1,10 +1,12 @@
 // Training of the SMPL denoiser's decoder (launchers; device code and the arithmetic contract: csrc/mdm_train.h).  Replaces, for the 144 tensors MDM.forward reads,
 // loss.backward() on LitInteraction.forward_backward (train_diffusion_smpl.py:60-166) and torch.optim.AdamW's step (:177-183).  `cond` is an input: its gradient
-// d_cond is returned for a later backward of MDM._get_embeddings.  The sampler's kernels and arena are not touched.
+// d_cond is returned, and interdiff_mdm_train_full_grads carries it on through MDM._get_embeddings (diffusion_smpl.py:217-221: the shared input embeddings,
+// pc_embedding, the positional rows, the eight encoder layers), whose 84 tensors follow the 144 in the flat vectors; pc_embedding is that pass's input seam.
+// The sampler's kernels and arena are not touched.
 //
 // Stored by the forward, per layer: the layer input, q|k|v and the attention output with its per-row log-sum-exp (layers 0, 7), the three normalised rows + 1/sigma
 // and LayerNorm outputs, the cross-attention query, memory k|v and output, the feed-forward pre-activation.  Recomputed by the backward: every softmax probability
-// (self-attention, cross-attention, QaN block) and the GELU output.
+// (self-attention, cross-attention, QaN block) and the GELU output.  The encoder stores the same per layer without the cross-attention items, on past_len * B rows.
 #include "mdm_train.h"
 
 using namespace mdmtrain;
@@ -20,6 +22,15 @@ struct Layout {
     int64_t body_w, body_b, obj_w, obj_b, t0_w, t0_b, t2_w, t2_b, bodyf_w, bodyf_b, objf_w, objf_b, total;
     LayerOff layer[N_LAYERS];
     int64_t off[N_TENSORS], size[N_TENSORS];
+};
+struct EncLayerOff {
+    int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, l1_w, l1_b, l2_w, l2_b, ln_w[2], ln_b[2];
+};
+constexpr int N_ENC_TENSORS = 84, N_FULL_TENSORS = N_TENSORS + N_ENC_TENSORS;
+struct EncLayout {
+    int64_t total;                                                // of the 144 + 84 tensors
+    EncLayerOff layer[N_LAYERS];
+    int64_t off[N_ENC_TENSORS], size[N_ENC_TENSORS];
 };
 inline bool is_qan(int l) { return l >= 1 && l <= 6; }
 
@@ -46,6 +57,31 @@ const Layout &layout() {
             for (int i = 0; i < 3; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
         }
         take(o.bodyf_w, (int64_t)NBODY * D); take(o.bodyf_b, NBODY); take(o.objf_w, (int64_t)(CTOK - NBODY) * D); take(o.objf_b, CTOK - NBODY);
+        o.total = at;
+        return o;
+    }();
+    return L;
+}
+
+// the encoder's 84 tensors behind the 144: interdiff_amd/mdm_train.py ENCODER_PARAM_NAMES
+const EncLayout &enc_layout() {
+    static const EncLayout L = [] {
+        EncLayout o{};
+        int64_t at = layout().total;
+        int n = 0;
+        auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
+        for (int l = 0; l < N_LAYERS; ++l) {
+            EncLayerOff &y = o.layer[l];
+            if (is_qan(l)) {
+                take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
+                y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
+            } else {
+                take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
+                y.queries = y.wk = -1;
+            }
+            take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
+            for (int i = 0; i < 2; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
+        }
         o.total = at;
         return o;
     }();
@@ -86,6 +122,35 @@ Ws plan(float *base, int B, int T, int S) {
     w.dG = take((size_t)SLOTS * NQ * D); w.dsim = take(M * NQ * SLOTS); w.cj = take(M * SLOTS); w.dwk_tok = take(M * NQ);
     w.partial = take(((M + 63) / 64 + 1) * FF);
     w.dtemb = take((size_t)B * D); w.dsz = take((size_t)B * D);
+    w.floats = at;
+    return w;
+}
+
+// The encoder's saves, behind the decoder's plan.  Its scratch (GELU output, d z, the four row buffers, d qkv, P / dS, the QaN items, the column-sum slabs) is the
+// decoder's: the encoder's forward ends before the decoder's begins and its backward begins after the decoder's has ended, and S * B < T * B rows.
+struct EncLayerWs {
+    float *qkv, *ao, *lse, *xh[2], *rs[2], *x1, *z, *G;
+};
+struct EncWs {
+    float *Xp, *h[N_LAYERS + 1], *genc;
+    EncLayerWs layer[N_LAYERS];
+    size_t floats;                                                // decoder plan included
+};
+inline int64_t n_shared() { return layout().t0_w; }               // bodyEmbedding.* and objEmbedding.*: the first four tensors of the table, back to back
+EncWs enc_plan(float *base, size_t at, int B, int S) {
+    EncWs w{};
+    const size_t M = (size_t)B * S;
+    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    w.Xp = take(M * CTOK);
+    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
+    w.genc = take((size_t)n_shared());
+    for (int l = 0; l < N_LAYERS; ++l) {
+        EncLayerWs &y = w.layer[l];
+        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
+        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * S); }
+        for (int i = 0; i < 2; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
+        y.x1 = take(M * D); y.z = take(M * FF);
+    }
     w.floats = at;
     return w;
 }
@@ -152,6 +217,75 @@ int loss_grad(hipStream_t st, const float *pred, const float *target, int B, int
     return IDF_OK;
 }
 
+// a linear layer's parameter gradients: dW = dY^T X, db = column sums of dY
+int lin_param_grads(hipStream_t st, const Ws &w, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, float *db, int M, int N, int K) {
+    MT_TRY(lin_dw(st, dY, ldy, X, ldx, dW, M, N, K));
+    return colsum(st, dY, ldy, nullptr, 0, M, N, w.partial, db);
+}
+
+// ---- the sublayers both stacks are made of; Off = LayerOff | EncLayerOff, T = tokens per clip ---------------------------------------------------------------
+// s = x + self_attn(x) (layers 0, 7) | x + QaN block(x) (layers 1..6)
+template <class Off>
+int mix_fwd(hipStream_t st, const float *th, const Off &o, bool qan, const float *xin, float *qkv, float *ao, float *lse, float *G, float *s, int B, int T) {
+    const int M = B * T;
+    if (qan) {
+        hipLaunchKernelGGL(mt_qan_prep_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, G);
+        IDF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(mt_qan_fwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, G, th + o.wk, s, M, T);
+        IDF_CHECK_LAUNCH();
+        return IDF_OK;
+    }
+    MT_TRY(lin_fwd(st, xin, D, th + o.sa_in_w, th + o.sa_in_b, qkv, 3 * D, nullptr, 0, M, 3 * D, D));
+    hipLaunchKernelGGL(mt_self_attn_fwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, qkv, ao, lse, T);
+    IDF_CHECK_LAUNCH();
+    return lin_fwd(st, ao, D, th + o.sa_out_w, th + o.sa_out_b, s, D, xin, D, M, D, D);
+}
+// s = x + linear2(gelu(linear1(x))); leaves the pre-activation z
+template <class Off>
+int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const Off &o, const float *x, float *z, float *s, int M) {
+    MT_TRY(lin_fwd(st, x, D, th + o.l1_w, th + o.l1_b, z, FF, nullptr, 0, M, FF, D));
+    hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
+    IDF_CHECK_LAUNCH();
+    return lin_fwd(st, w.g, FF, th + o.l2_w, th + o.l2_b, s, D, x, D, M, D, FF);
+}
+// E = d s (the feed-forward output and, through the residual, d x)  ->  F = d x, and the four parameter gradients
+template <class Off>
+int ffn_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &o, const float *E, const float *x, const float *z, float *F, int M) {
+    hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, E, D, w.g, FF, gr + o.l2_w, gr + o.l2_b, M, D, FF));
+    MT_TRY(lin_dx(st, E, D, th + o.l2_w, w.dz, FF, nullptr, 0, M, D, FF));
+    hipLaunchKernelGGL(mt_gelu_bwd_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.dz, (int64_t)M * FF);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, w.dz, FF, x, D, gr + o.l1_w, gr + o.l1_b, M, FF, D));
+    return lin_dx(st, w.dz, FF, th + o.l1_w, F, D, E, D, M, FF, D);
+}
+// E = d s of mix_fwd  ->  Dh = d x (the residual included), and the parameter gradients; F is scratch
+template <class Off>
+int mix_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &o, bool qan, const float *E, const float *xin, const float *qkv, const float *ao,
+            const float *lse, const float *G, float *F, float *Dh, int B, int T) {
+    const int M = B * T;
+    if (qan) {
+        hipLaunchKernelGGL(mt_qan_bwd_token_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, G, th + o.wk, E, w.dsim, w.cj, w.dwk_tok, M, T);
+        IDF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(mt_qan_bwd_gather_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, E, G, w.dsim, w.cj, Dh, M, T);
+        IDF_CHECK_LAUNCH();
+        // dG[j][n] = sum_t dsim[t][n][j] x[t-1+j]: slot 0 pairs token t with frame t-1 (rows 1.., a clip's first token is masked: dsim = 0), slot 2 with t+1
+        MT_TRY(gemm(st, w.dsim + NQ * SLOTS, SLOTS, NQ * SLOTS, xin, D, 1, w.dG, D, nullptr, nullptr, 0, NQ, D, M - 1));
+        MT_TRY(gemm(st, w.dsim + 1, SLOTS, NQ * SLOTS, xin, D, 1, w.dG + (int64_t)NQ * D, D, nullptr, nullptr, 0, NQ, D, M));
+        MT_TRY(gemm(st, w.dsim + 2, SLOTS, NQ * SLOTS, xin + D, D, 1, w.dG + (int64_t)2 * NQ * D, D, nullptr, nullptr, 0, NQ, D, M - 1));
+        hipLaunchKernelGGL(mt_qan_dqueries_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, w.dG, gr + o.queries);
+        IDF_CHECK_LAUNCH();
+        return colsum(st, w.dwk_tok, NQ, nullptr, 0, M, NQ, w.partial, gr + o.wk);
+    }
+    MT_TRY(lin_param_grads(st, w, E, D, ao, D, gr + o.sa_out_w, gr + o.sa_out_b, M, D, D));
+    MT_TRY(lin_dx(st, E, D, th + o.sa_out_w, F, D, nullptr, 0, M, D, D));                                                        // F = d (attention output)
+    hipLaunchKernelGGL(mt_self_attn_bwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, qkv, ao, lse, F, w.dqkv, w.P, w.dS, T);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, w.dqkv, 3 * D, xin, D, gr + o.sa_in_w, gr + o.sa_in_b, M, 3 * D, D));
+    return lin_dx(st, w.dqkv, 3 * D, th + o.sa_in_w, Dh, D, E, D, M, 3 * D, D);
+}
+
 // ---- forward with saves ---------------------------------------------------------------------------------------------------------------------------------
 int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *pe, int pe_rows, const float *x_t, const int64_t *ts, const float *cond, int B, int T,
             int S, float *pred) {
@@ -175,17 +309,7 @@ int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const
         const LayerWs &y = w.layer[l];
         const float *xin = w.h[l];
         float *s = w.t[0];                                        // the pre-LayerNorm sums live only until their LayerNorm has run
-        if (is_qan(l)) {
-            hipLaunchKernelGGL(mt_qan_prep_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, y.G);
-            IDF_CHECK_LAUNCH();
-            hipLaunchKernelGGL(mt_qan_fwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, y.G, th + o.wk, s, M, T);
-            IDF_CHECK_LAUNCH();
-        } else {
-            MT_TRY(lin_fwd(st, xin, D, th + o.sa_in_w, th + o.sa_in_b, y.qkv, 3 * D, nullptr, 0, M, 3 * D, D));
-            hipLaunchKernelGGL(mt_self_attn_fwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, y.qkv, y.ao, y.lse, T);
-            IDF_CHECK_LAUNCH();
-            MT_TRY(lin_fwd(st, y.ao, D, th + o.sa_out_w, th + o.sa_out_b, s, D, xin, D, M, D, D));
-        }
+        MT_TRY(mix_fwd(st, th, o, is_qan(l), xin, y.qkv, y.ao, y.lse, y.G, s, B, T));
         MT_TRY(ln_fwd(st, s, th + o.ln_w[0], th + o.ln_b[0], y.xh[0], y.rs[0], y.x1, M));
         // cross-attention on the memory
         MT_TRY(lin_fwd(st, y.x1, D, th + o.ca_in_w, th + o.ca_in_b, y.q2, D, nullptr, 0, M, D, D));
@@ -195,10 +319,7 @@ int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const
         MT_TRY(lin_fwd(st, y.o2, D, th + o.ca_out_w, th + o.ca_out_b, s, D, y.x1, D, M, D, D));
         MT_TRY(ln_fwd(st, s, th + o.ln_w[1], th + o.ln_b[1], y.xh[1], y.rs[1], y.x2, M));
         // feed-forward
-        MT_TRY(lin_fwd(st, y.x2, D, th + o.l1_w, th + o.l1_b, y.z, FF, nullptr, 0, M, FF, D));
-        hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.g, (int64_t)M * FF);
-        IDF_CHECK_LAUNCH();
-        MT_TRY(lin_fwd(st, w.g, FF, th + o.l2_w, th + o.l2_b, s, D, y.x2, D, M, D, FF));
+        MT_TRY(ffn_fwd(st, w, th, o, y.x2, y.z, s, M));
         if (is_qan(l)) {
             MT_TRY(ln_fwd(st, s, th + o.ln_w[2], th + o.ln_b[2], y.xh[2], y.rs[2], w.t[1], M));
             hipLaunchKernelGGL(mt_round_trip_kernel, dim3(blocks256((int64_t)M * D)), dim3(256), 0, st, xin, w.t[1], w.h[l + 1], (int64_t)M * D);
@@ -212,12 +333,6 @@ int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const
     hipLaunchKernelGGL(mt_rows_to_tokens_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, w.Y, pred, B, T);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
-}
-
-// a linear layer's parameter gradients: dW = dY^T X, db = column sums of dY
-int lin_param_grads(hipStream_t st, const Ws &w, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, float *db, int M, int N, int K) {
-    MT_TRY(lin_dw(st, dY, ldy, X, ldx, dW, M, N, K));
-    return colsum(st, dY, ldy, nullptr, 0, M, N, w.partial, db);
 }
 
 // ---- backward: d_pred [B,1,144,T] -> grads [n_param], d_cond [S][B][256] ------------------------------------------------------------------------------------
@@ -238,15 +353,7 @@ int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, cons
         const float *xin = w.h[l];
         // Dh = d (LayerNorm3 output): for a QaN layer the backward of tgt + (x - tgt) is the identity on x and nothing on tgt
         MT_TRY(ln_bwd(st, Dh, y.xh[2], y.rs[2], th + o.ln_w[2], gr + o.ln_w[2], gr + o.ln_b[2], E, w.partial, M));            // E = d s3 = d ffn-out = d x2 (residual)
-        // feed-forward
-        hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.g, (int64_t)M * FF);
-        IDF_CHECK_LAUNCH();
-        MT_TRY(lin_param_grads(st, w, E, D, w.g, FF, gr + o.l2_w, gr + o.l2_b, M, D, FF));
-        MT_TRY(lin_dx(st, E, D, th + o.l2_w, w.dz, FF, nullptr, 0, M, D, FF));
-        hipLaunchKernelGGL(mt_gelu_bwd_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, y.z, w.dz, (int64_t)M * FF);
-        IDF_CHECK_LAUNCH();
-        MT_TRY(lin_param_grads(st, w, w.dz, FF, y.x2, D, gr + o.l1_w, gr + o.l1_b, M, FF, D));
-        MT_TRY(lin_dx(st, w.dz, FF, th + o.l1_w, F, D, E, D, M, FF, D));                                                        // F = d x2
+        MT_TRY(ffn_bwd(st, w, th, gr, o, E, y.x2, y.z, F, M));                                                                  // F = d x2
         MT_TRY(ln_bwd(st, F, y.xh[1], y.rs[1], th + o.ln_w[1], gr + o.ln_w[1], gr + o.ln_b[1], E, w.partial, M));              // E = d s2 = d x1 (residual)
         // cross-attention
         MT_TRY(lin_param_grads(st, w, E, D, y.o2, D, gr + o.ca_out_w, gr + o.ca_out_b, M, D, D));
@@ -261,27 +368,7 @@ int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, cons
         first_cond = false;
         MT_TRY(lin_dx(st, Gq, D, th + o.ca_in_w, F, D, E, D, M, D, D));                                                          // F = d x1
         MT_TRY(ln_bwd(st, F, y.xh[0], y.rs[0], th + o.ln_w[0], gr + o.ln_w[0], gr + o.ln_b[0], E, w.partial, M));              // E = d s1
-        if (is_qan(l)) {
-            hipLaunchKernelGGL(mt_qan_bwd_token_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, xin, y.G, th + o.wk, E, w.dsim, w.cj, w.dwk_tok, M, T);
-            IDF_CHECK_LAUNCH();
-            hipLaunchKernelGGL(mt_qan_bwd_gather_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, E, y.G, w.dsim, w.cj, Dh, M, T);
-            IDF_CHECK_LAUNCH();
-            // dG[j][n] = sum_t dsim[t][n][j] x[t-1+j]: slot 0 pairs token t with frame t-1 (rows 1.., a clip's first token is masked: dsim = 0), slot 2 with t+1
-            MT_TRY(gemm(st, w.dsim + NQ * SLOTS, SLOTS, NQ * SLOTS, xin, D, 1, w.dG, D, nullptr, nullptr, 0, NQ, D, M - 1));
-            MT_TRY(gemm(st, w.dsim + 1, SLOTS, NQ * SLOTS, xin, D, 1, w.dG + (int64_t)NQ * D, D, nullptr, nullptr, 0, NQ, D, M));
-            MT_TRY(gemm(st, w.dsim + 2, SLOTS, NQ * SLOTS, xin + D, D, 1, w.dG + (int64_t)2 * NQ * D, D, nullptr, nullptr, 0, NQ, D, M - 1));
-            hipLaunchKernelGGL(mt_qan_dqueries_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, w.dG, gr + o.queries);
-            IDF_CHECK_LAUNCH();
-            MT_TRY(colsum(st, w.dwk_tok, NQ, nullptr, 0, M, NQ, w.partial, gr + o.wk));
-        } else {
-            MT_TRY(lin_param_grads(st, w, E, D, y.ao, D, gr + o.sa_out_w, gr + o.sa_out_b, M, D, D));
-            MT_TRY(lin_dx(st, E, D, th + o.sa_out_w, F, D, nullptr, 0, M, D, D));                                                // F = d (attention output)
-            hipLaunchKernelGGL(mt_self_attn_bwd_kernel, dim3((unsigned)(B * HEADS)), dim3(128), (size_t)2 * T * HD * sizeof(float), st, y.qkv, y.ao, y.lse, F, w.dqkv, w.P,
-                               w.dS, T);
-            IDF_CHECK_LAUNCH();
-            MT_TRY(lin_param_grads(st, w, w.dqkv, 3 * D, xin, D, gr + o.sa_in_w, gr + o.sa_in_b, M, 3 * D, D));
-            MT_TRY(lin_dx(st, w.dqkv, 3 * D, th + o.sa_in_w, Dh, D, E, D, M, 3 * D, D));
-        }
+        MT_TRY(mix_bwd(st, w, th, gr, o, is_qan(l), E, xin, y.qkv, y.ao, y.lse, y.G, F, Dh, B, T));
     }
     // embedding and the timestep MLP: Dh = d h0
     MT_TRY(lin_param_grads(st, w, Dh, D, w.X, CTOK, gr + L.body_w, gr + L.body_b, M, D, NBODY));
@@ -293,6 +380,65 @@ int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, cons
     hipLaunchKernelGGL(mt_silu_bwd_kernel, dim3(blocks256((int64_t)B * D)), dim3(256), 0, st, w.z0, w.dsz, (int64_t)B * D);
     IDF_CHECK_LAUNCH();
     MT_TRY(lin_param_grads(st, w, w.dsz, D, w.tin, D, gr + L.t0_w, gr + L.t0_b, B, D, D));
+    return IDF_OK;
+}
+
+// ---- the encoder: MDM._get_embeddings from pc_embedding on (diffusion_smpl.py:217-221), S = past_len tokens per clip ----------------------------------------
+// th holds the 228 tensors; target [B][144][T] gives the past frames; pc [B][256]; cond [S][B][256] is written in the memory's own order.
+int enc_forward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &w, const EncWs &e, const float *th, const float *pe, const float *target, const float *pc,
+                int B, int T, int S, float *cond) {
+    const int M = B * S;
+    hipLaunchKernelGGL(mt_gather_past_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, target, e.Xp, B, T, S);
+    IDF_CHECK_LAUNCH();
+    // embedding: (bodyEmbedding(body) + objEmbedding(obj) + pc_embedding) + pe[s] -- the decoder's kernel with pc in the place of the timestep embedding
+    MT_TRY(lin_fwd(st, e.Xp, CTOK, th + L.body_w, th + L.body_b, e.h[0], D, nullptr, 0, M, D, NBODY));
+    MT_TRY(lin_fwd(st, e.Xp + NBODY, CTOK, th + L.obj_w, th + L.obj_b, e.h[0], D, e.h[0], D, M, D, CTOK - NBODY));
+    hipLaunchKernelGGL(mt_add_temb_pe_kernel, dim3((unsigned)M), dim3(256), 0, st, e.h[0], pc, pe, S);
+    IDF_CHECK_LAUNCH();
+    for (int l = 0; l < N_LAYERS; ++l) {
+        const EncLayerOff &o = EL.layer[l];
+        const EncLayerWs &y = e.layer[l];
+        const float *xin = e.h[l];
+        float *s = w.t[0];
+        MT_TRY(mix_fwd(st, th, o, is_qan(l), xin, y.qkv, y.ao, y.lse, y.G, s, B, S));
+        MT_TRY(ln_fwd(st, s, th + o.ln_w[0], th + o.ln_b[0], y.xh[0], y.rs[0], y.x1, M));
+        MT_TRY(ffn_fwd(st, w, th, o, y.x1, y.z, s, M));
+        if (is_qan(l)) {
+            MT_TRY(ln_fwd(st, s, th + o.ln_w[1], th + o.ln_b[1], y.xh[1], y.rs[1], w.t[1], M));
+            hipLaunchKernelGGL(mt_round_trip_kernel, dim3(blocks256((int64_t)M * D)), dim3(256), 0, st, xin, w.t[1], e.h[l + 1], (int64_t)M * D);
+            IDF_CHECK_LAUNCH();
+        } else {
+            MT_TRY(ln_fwd(st, s, th + o.ln_w[1], th + o.ln_b[1], y.xh[1], y.rs[1], e.h[l + 1], M));
+        }
+    }
+    hipLaunchKernelGGL(mt_swap_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, e.h[N_LAYERS], cond, B, S);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+
+// d_cond [S][B][256] -> the 84 encoder gradients, the encoder path's share of the four shared embedding tensors (added to the decoder path's, which gr already
+// holds), d_pc [B][256]
+int enc_backward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &w, const EncWs &e, const float *th, const float *d_cond, int B, int S, float *gr,
+                 float *d_pc) {
+    const int M = B * S;
+    float *Dh = w.t[0], *E = w.t[1], *F = w.t[2];
+    hipLaunchKernelGGL(mt_swap_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, d_cond, Dh, S, B);
+    IDF_CHECK_LAUNCH();
+    for (int l = N_LAYERS - 1; l >= 0; --l) {
+        const EncLayerOff &o = EL.layer[l];
+        const EncLayerWs &y = e.layer[l];
+        MT_TRY(ln_bwd(st, Dh, y.xh[1], y.rs[1], th + o.ln_w[1], gr + o.ln_w[1], gr + o.ln_b[1], E, w.partial, M));              // E = d s2 = d x1 (residual)
+        MT_TRY(ffn_bwd(st, w, th, gr, o, E, y.x1, y.z, F, M));                                                                  // F = d x1
+        MT_TRY(ln_bwd(st, F, y.xh[0], y.rs[0], th + o.ln_w[0], gr + o.ln_w[0], gr + o.ln_b[0], E, w.partial, M));              // E = d s1
+        MT_TRY(mix_bwd(st, w, th, gr, o, is_qan(l), E, e.h[l], y.qkv, y.ao, y.lse, y.G, F, Dh, B, S));
+    }
+    // Dh = d embedding: pe takes nothing, pc_embedding the sum over a clip's tokens in token order, the two shared linears their encoder-path share
+    hipLaunchKernelGGL(mt_sum_frames_kernel, dim3((unsigned)B), dim3(256), 0, st, Dh, d_pc, S);
+    IDF_CHECK_LAUNCH();
+    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp, CTOK, e.genc + L.body_w, e.genc + L.body_b, M, D, NBODY));
+    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp + NBODY, CTOK, e.genc + L.obj_w, e.genc + L.obj_b, M, D, CTOK - NBODY));
+    hipLaunchKernelGGL(mt_add_into_kernel, dim3(blocks256(n_shared())), dim3(256), 0, st, gr, e.genc, n_shared());
+    IDF_CHECK_LAUNCH();
     return IDF_OK;
 }
 
@@ -343,6 +489,48 @@ extern "C" int interdiff_mdm_train_grads(const float *params, const float *pe, i
         dp = mine;
     }
     return backward(st, L, w, params, cond, dp, B, T, mem_len, grads, d_cond);
+}
+
+extern "C" int interdiff_mdm_train_full_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
+    const Layout &L = layout();
+    const EncLayout &EL = enc_layout();
+    for (int i = 0; i < N_FULL_TENSORS; ++i) {
+        if (offsets) offsets[i] = i < N_TENSORS ? L.off[i] : EL.off[i - N_TENSORS];
+        if (sizes) sizes[i] = i < N_TENSORS ? L.size[i] : EL.size[i - N_TENSORS];
+    }
+    if (n_tensors) *n_tensors = N_FULL_TENSORS;
+    if (n_param) *n_param = EL.total;
+    return IDF_OK;
+}
+
+extern "C" size_t interdiff_mdm_train_full_workspace_bytes(int32_t B, int32_t T, int32_t past_len) {
+    if (!shape_ok(B, T, past_len, past_len)) return 0;
+    return enc_plan(nullptr, plan(nullptr, B, T, past_len).floats, B, past_len).floats * sizeof(float);
+}
+
+extern "C" int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *pc,
+                                              const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, const float *d_pred_in, float *grads,
+                                              float *cond, float *d_cond, float *d_pc, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
+    if (!params || !pe || !x_t || !ts || !pc || !target || !weights16 || !grads || !cond || !d_cond || !d_pc || !pred || !terms || !ws) return IDF_E_INVAL;
+    if (!shape_ok(B, T, past_len, past_len) || pe_rows < T) return IDF_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
+    if (ws_bytes < interdiff_mdm_train_full_workspace_bytes(B, T, past_len)) return IDF_E_NOMEM;
+    hipStream_t st = idf_stream(stream);
+    const Layout &L = layout();
+    const EncLayout &EL = enc_layout();
+    const Ws w = plan(static_cast<float *>(ws), B, T, past_len);
+    const EncWs e = enc_plan(static_cast<float *>(ws), w.floats, B, past_len);
+    MT_TRY(enc_forward(st, L, EL, w, e, params, pe, target, pc, B, T, past_len, cond));
+    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, past_len, pred));
+    MT_TRY(interdiff_denoising_losses(pred, target, B, T, past_len, terms, stream));
+    const float *dp = d_pred_in;
+    if (!dp) {
+        float *mine = w.g;
+        MT_TRY(loss_grad(st, pred, target, B, T, past_len, weights16, mine));
+        dp = mine;
+    }
+    MT_TRY(backward(st, L, w, params, cond, dp, B, T, past_len, grads, d_cond));
+    return enc_backward(st, L, EL, w, e, params, d_cond, B, past_len, grads, d_pc);
 }
 
 extern "C" int interdiff_mdm_train_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, double lr, double beta1,
