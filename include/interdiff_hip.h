@@ -923,6 +923,42 @@ int interdiff_skeleton_denoising_losses(const float *pred, const float *target, 
                                         int32_t n_points, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * TRAINING of the skeleton denoiser (csrc/skeleton_mdm_train.hip on the stacks of csrc/mdm_train.h / .hip at feed-forward width 256, token width
+ * 106): one optimiser step of interdiff/train_diffusion_skeleton.py -- LitInteraction._common_step(mode='train') (:255-262) = MDM._get_embeddings
+ * (model/diffusion_skeleton.py:194-215), GaussianDiffusion.q_sample (interdiff_q_sample), MDM.forward(x, timesteps, zero_pose_obj, y) (:231-257:
+ * _decode, calc_obj_pred :218-229 with pytorch3d's quaternion_to_matrix, which does not normalise), the loss of forward_backward (:89-168),
+ * loss.backward() through all of it, and torch.optim.AdamW (configure_optimizers :181-184).  No seam is left: every one of the model's 230 parameter
+ * tensors (5 499 582 floats) gets its gradient.  Additive entries, same arithmetic contract as the SMPL trainer's (exact fp32, no float atomics, two
+ * calls give the same bits, linear in d_pred bit for bit); dropout 0, cond_mask_prob 0.  n_body = 63, n_points = 12.
+ *
+ * SKELETON PARAMETER TABLE.  230 tensors packed without padding: the 144 names of the PARAMETER TABLE above (shapes of the skeleton model:
+ * bodyEmbedding [256,63], objEmbedding [256,36], linear1 [256,256], bodyFinalLinear [63,256], objFinalLinear [7,256]), then the 84 encoder tensors in
+ * the order of the FULL PARAMETER TABLE, then shapeEmbedding.weight [256,36], shapeEmbedding.bias [256].  bodyEmbedding / objEmbedding receive the
+ * decoder path's gradient first and the encoder path's added to it.
+ *
+ *  interdiff_skeleton_denoising_loss_grad   replaces autograd through the 13 terms (:108-168): d_pred [B,1,106,T] = d/d pred of
+ *      mean_b sum_i weights13[i] * term_i[b], the terms and their order of interdiff_skeleton_denoising_losses (the schedule sampler's weights are
+ *      all one).  weights13: HOST pointer.  One launch, one thread per element.  past_len >= 1, T >= past_len + 1.
+ *  interdiff_skeleton_mdm_train_param_table   offsets / sizes (HOST int64 [230], nullable), their count and n_param.
+ *  interdiff_skeleton_mdm_train_workspace_bytes   workspace of the gradient call; 0 for an unsupported shape.
+ *  interdiff_skeleton_mdm_train_grads   encoder forward -> decoder forward -> keypoint head -> terms -> head, decoder and encoder backward -> the
+ *      shape embedding's gradient.  x_t, target [B,1,106,T] (target = x_start: its past frames are the encoder's tokens), ts int64 [B],
+ *      zero_pose_obj [B][12][3] (data: no gradient), pe [pe_rows][256] (pe_rows > every timestep and >= T).  -> grads [n_param],
+ *      cond [past_len][B][256] (what _get_embeddings returns), pred [B,1,106,T] = body | R(q) zero_pose_obj + translation | pose, terms [13][B].
+ *      d_pred_in NULL: the gradient of the weighted loss; else [B,1,106,T], any other objective's gradient with respect to pred, taken through the
+ *      same head backward.  ws 256-byte aligned.  T <= 128, 2 <= past_len <= 16, T >= past_len + 2; IDF_E_INVAL otherwise.
+ *  The optimiser step is interdiff_mdm_train_step (elementwise on n floats) as it stands.
+ * ---------------------------------------------------------------------------------- */
+int interdiff_skeleton_denoising_loss_grad(const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights13,
+                                           float *d_pred, void *stream);
+int interdiff_skeleton_mdm_train_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param);
+size_t interdiff_skeleton_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t past_len);
+int interdiff_skeleton_mdm_train_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *target,
+                                       const float *zero_pose_obj, int32_t B, int32_t T, int32_t past_len, const float *weights13,
+                                       const float *d_pred_in, float *grads, float *cond, float *pred, float *terms, void *ws, size_t ws_bytes,
+                                       void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Scoring of a correction-predictor checkpoint (csrc/corr_losses.hip).  Forward only, additive.
  *  interdiff_correction_losses  replaces LitInteraction.calc_loss_contact (interdiff/train_correction_smpl.py:103-185), calc_loss (:60-101) and the
  *      skeleton trainer's calc_loss (train_correction_skeleton.py:85-126).

@@ -202,6 +202,10 @@ _SIGS = {
     'interdiff_skeleton_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_sample_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    'interdiff_skeleton_denoising_loss_grad': (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp]),
+    'interdiff_skeleton_mdm_train_param_table': (C.c_int, [C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
+    'interdiff_skeleton_mdm_train_workspace_bytes': (sz, [i32, i32, i32]),
+    'interdiff_skeleton_mdm_train_grads': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, vp, vp, sz, vp]),
     'interdiff_correction_losses_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'interdiff_correction_losses': (C.c_int, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_contact_labels_workspace_bytes': (sz, [i64, i32, i32, i32]),

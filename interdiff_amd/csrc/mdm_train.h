@@ -1,18 +1,15 @@
 // Training of the SMPL denoiser's decoder: device code of the forward with saves, the backward of MDM.forward (model/diffusion_smpl.py:226-246: embedding,
 // timestep MLP, [std, QaN x6, std] decoder layers, the two output heads) under the loss of LitInteraction.forward_backward (train_diffusion_smpl.py:60-166),
 // and AdamW (:177-183); and of the encoder side, MDM._get_embeddings from pc_embedding on (:217-221), which runs the same sublayers on past_len tokens per clip.
-// Launchers: csrc/mdm_train.hip.
+// Launchers: csrc/mdm_train.hip; they take a geometry (csrc/mdm_train_stack.h) and also run the skeleton denoiser's stacks (csrc/skeleton_mdm_train.hip).
 // Arithmetic: exact fp32 only -- every matrix product is v_mfma_f32_16x16x4_f32 (a k-ordered fp32 fma chain, four independent accumulators per wave), everything
 // else VALU.  No f16 MFMA, so the exclusive-CU rule (common.h) puts no obligation on these kernels.  No float atomics: a sum across workgroups is a partial-slab store
 // plus a fixed-order reducer (mt_colsum_*), every other sum is owned by one thread or one wave -- two calls give the same bits.
 // Token rows are clip-major: row r = b * T + t of an [M = B*T, 256] matrix; memory rows are cond's own [S][B] order, row s * B + b.
 #pragma once
-#include "common.h"
+#include "mdm_train_stack.h"                                      // the constants, the geometry (feed-forward and token widths) the launchers take
 
 namespace mdmtrain {
-
-constexpr int D = 256, HEADS = 4, HD = 64, FF = 1024, CTOK = 144, NBODY = 135, NQ = 10, SLOTS = 3, MAX_MEM = 16, MAX_T = 128;
-constexpr float LN_EPS = 1e-5f;
 
 // ------------------------------------------------------------------------------------------------------------------ GEMM
 // C[M,N] = sum_k A(i,k) B(k,j) (+ bias[j]) (+ R[i,j]) with free strides on both operands, so one kernel is the NT product of a forward linear (Y = X W^T), the NN
@@ -132,22 +129,22 @@ __global__ __launch_bounds__(256) void mt_silu_bwd_kernel(const float *__restric
         ds[i] = ds[i] * (sg * (1.0f + z[i] * (1.0f - sg)));
     }
 }
-// [B][C][T] tokens <-> [B*T][C] rows
-__global__ __launch_bounds__(256) void mt_tokens_to_rows_kernel(const float *__restrict__ x, float *__restrict__ rows, int B, int T) {
+// [B][C][T] tokens <-> [B*T][C] rows, C channels per token
+__global__ __launch_bounds__(256) void mt_tokens_to_rows_kernel(const float *__restrict__ x, float *__restrict__ rows, int B, int T, int C) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * T * CTOK) return;
-    const int c = (int)(i % CTOK);
-    const int64_t r = i / CTOK;
+    if (i >= (int64_t)B * T * C) return;
+    const int c = (int)(i % C);
+    const int64_t r = i / C;
     const int t = (int)(r % T), b = (int)(r / T);
-    rows[i] = x[((int64_t)b * CTOK + c) * T + t];
+    rows[i] = x[((int64_t)b * C + c) * T + t];
 }
-__global__ __launch_bounds__(256) void mt_rows_to_tokens_kernel(const float *__restrict__ rows, float *__restrict__ x, int B, int T) {
+__global__ __launch_bounds__(256) void mt_rows_to_tokens_kernel(const float *__restrict__ rows, float *__restrict__ x, int B, int T, int C) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * T * CTOK) return;
+    if (i >= (int64_t)B * T * C) return;
     const int t = (int)(i % T);
     const int64_t bc = i / T;
-    const int c = (int)(bc % CTOK), b = (int)(bc / CTOK);
-    x[i] = rows[((int64_t)b * T + t) * CTOK + c];
+    const int c = (int)(bc % C), b = (int)(bc / C);
+    x[i] = rows[((int64_t)b * T + t) * C + c];
 }
 // input of the timestep MLP: pe[ts[b]] (layers.py:42-43); a timestep outside the table must not read outside it
 __global__ __launch_bounds__(256) void mt_gather_pe_kernel(const float *__restrict__ pe, int pe_rows, const int64_t *__restrict__ ts, float *__restrict__ out) {
@@ -574,6 +571,7 @@ struct Weights16 {
 };
 __global__ __launch_bounds__(256) void mt_loss_grad_kernel(const float *__restrict__ pred, const float *__restrict__ target, int B, int T, int P, const Weights16 W,
                                                            float *__restrict__ dpred) {
+    constexpr int CTOK = SMPL_GEOM.ctok;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)B * CTOK * T) return;
     const int t = (int)(i % T), c = (int)((i / T) % CTOK);
@@ -605,14 +603,14 @@ __global__ __launch_bounds__(256) void mt_loss_grad_kernel(const float *__restri
 }
 
 // ---------------------------------------------------------------------------------------------- encoder (_get_embeddings)
-// The encoder's token input is the past frames of x_start: rows[b*S + s][c] = target[b][c][s] of a [B][144][T] tensor (clip-major rows, like the decoder's).
-__global__ __launch_bounds__(256) void mt_gather_past_kernel(const float *__restrict__ target, float *__restrict__ rows, int B, int T, int S) {
+// The encoder's token input is the past frames of x_start: rows[b*S + s][c] = target[b][c][s] of a [B][C][T] tensor (clip-major rows, like the decoder's).
+__global__ __launch_bounds__(256) void mt_gather_past_kernel(const float *__restrict__ target, float *__restrict__ rows, int B, int T, int S, int C) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * S * CTOK) return;
-    const int c = (int)(i % CTOK);
-    const int64_t r = i / CTOK;
+    if (i >= (int64_t)B * S * C) return;
+    const int c = (int)(i % C);
+    const int64_t r = i / C;
     const int s = (int)(r % S), b = (int)(r / S);
-    rows[i] = target[((int64_t)b * CTOK + c) * T + s];
+    rows[i] = target[((int64_t)b * C + c) * T + s];
 }
 // [P][Q] rows of 256 -> [Q][P]: the encoder's clip-major output to cond's [S][B] order, and d_cond back
 __global__ __launch_bounds__(256) void mt_swap_rows_kernel(const float *__restrict__ in, float *__restrict__ out, int P, int Q) {

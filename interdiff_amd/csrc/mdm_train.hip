@@ -4,6 +4,9 @@
 // pc_embedding, the positional rows, the eight encoder layers), whose 84 tensors follow the 144 in the flat vectors; pc_embedding is that pass's input seam.
 // The sampler's kernels and arena are not touched.
 //
+// The two stacks, their layouts and workspace plans take a geometry (csrc/mdm_train_stack.h: feed-forward width, token and head widths) and are what the skeleton
+// denoiser's trainer (csrc/skeleton_mdm_train.hip) runs too; the SMPL entries at the end of this file run them at SMPL_GEOM.
+//
 // Stored by the forward, per layer: the layer input, q|k|v and the attention output with its per-row log-sum-exp (layers 0, 7), the three normalised rows + 1/sigma
 // and LayerNorm outputs, the cross-attention query, memory k|v and output, the feed-forward pre-activation.  Recomputed by the backward: every softmax probability
 // (self-attention, cross-attention, QaN block) and the GELU output.  The encoder stores the same per layer without the cross-attention items, on past_len * B rows.
@@ -13,154 +16,8 @@ using namespace mdmtrain;
 
 namespace {
 
-constexpr int N_LAYERS = 8, N_TENSORS = 144;
-
-struct LayerOff {
-    int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, ca_in_w, ca_in_b, ca_out_w, ca_out_b, l1_w, l1_b, l2_w, l2_b, ln_w[3], ln_b[3];
-};
-struct Layout {
-    int64_t body_w, body_b, obj_w, obj_b, t0_w, t0_b, t2_w, t2_b, bodyf_w, bodyf_b, objf_w, objf_b, total;
-    LayerOff layer[N_LAYERS];
-    int64_t off[N_TENSORS], size[N_TENSORS];
-};
-struct EncLayerOff {
-    int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, l1_w, l1_b, l2_w, l2_b, ln_w[2], ln_b[2];
-};
-constexpr int N_ENC_TENSORS = 84, N_FULL_TENSORS = N_TENSORS + N_ENC_TENSORS;
-struct EncLayout {
-    int64_t total;                                                // of the 144 + 84 tensors
-    EncLayerOff layer[N_LAYERS];
-    int64_t off[N_ENC_TENSORS], size[N_ENC_TENSORS];
-};
 inline bool is_qan(int l) { return l >= 1 && l <= 6; }
-
-// the flat master vector: the tensors in the order of interdiff_amd/mdm_train.py PARAM_NAMES, packed without padding
-const Layout &layout() {
-    static const Layout L = [] {
-        Layout o{};
-        int64_t at = 0;
-        int n = 0;
-        auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
-        take(o.body_w, (int64_t)D * NBODY); take(o.body_b, D); take(o.obj_w, (int64_t)D * (CTOK - NBODY)); take(o.obj_b, D);
-        take(o.t0_w, (int64_t)D * D); take(o.t0_b, D); take(o.t2_w, (int64_t)D * D); take(o.t2_b, D);
-        for (int l = 0; l < N_LAYERS; ++l) {
-            LayerOff &y = o.layer[l];
-            if (is_qan(l)) {
-                take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
-                y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
-            } else {
-                take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
-                y.queries = y.wk = -1;
-            }
-            take(y.ca_in_w, (int64_t)3 * D * D); take(y.ca_in_b, 3 * D); take(y.ca_out_w, (int64_t)D * D); take(y.ca_out_b, D);
-            take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
-            for (int i = 0; i < 3; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
-        }
-        take(o.bodyf_w, (int64_t)NBODY * D); take(o.bodyf_b, NBODY); take(o.objf_w, (int64_t)(CTOK - NBODY) * D); take(o.objf_b, CTOK - NBODY);
-        o.total = at;
-        return o;
-    }();
-    return L;
-}
-
-// the encoder's 84 tensors behind the 144: interdiff_amd/mdm_train.py ENCODER_PARAM_NAMES
-const EncLayout &enc_layout() {
-    static const EncLayout L = [] {
-        EncLayout o{};
-        int64_t at = layout().total;
-        int n = 0;
-        auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
-        for (int l = 0; l < N_LAYERS; ++l) {
-            EncLayerOff &y = o.layer[l];
-            if (is_qan(l)) {
-                take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
-                y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
-            } else {
-                take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
-                y.queries = y.wk = -1;
-            }
-            take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
-            for (int i = 0; i < 2; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
-        }
-        o.total = at;
-        return o;
-    }();
-    return L;
-}
-
-// ---- workspace plan (floats) ---------------------------------------------------------------------------------------------------------------------------
-struct LayerWs {
-    float *qkv, *ao, *lse, *xh[3], *rs[3], *x1, *x2, *q2, *kv, *o2, *z, *G;
-};
-struct Ws {
-    float *X, *Y, *dY, *tin, *z0, *sz, *temb, *h[N_LAYERS + 1];
-    LayerWs layer[N_LAYERS];
-    float *g, *dz, *t[4], *dqkv, *P, *dS, *Pc, *dSc, *dkv, *dG, *dsim, *cj, *dwk_tok, *partial, *dtemb, *dsz;
-    size_t floats;
-};
-Ws plan(float *base, int B, int T, int S) {
-    Ws w{};
-    size_t at = 0;
-    const size_t M = (size_t)B * T;
-    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
-    w.X = take(M * CTOK); w.Y = take(M * CTOK); w.dY = take(M * CTOK);
-    w.tin = take((size_t)B * D); w.z0 = take((size_t)B * D); w.sz = take((size_t)B * D); w.temb = take((size_t)B * D);
-    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
-    for (int l = 0; l < N_LAYERS; ++l) {
-        LayerWs &y = w.layer[l];
-        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
-        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * T); }
-        for (int i = 0; i < 3; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
-        y.x1 = take(M * D); y.x2 = take(M * D); y.q2 = take(M * D); y.kv = take((size_t)S * B * 2 * D); y.o2 = take(M * D); y.z = take(M * FF);
-    }
-    w.g = take(M * FF); w.dz = take(M * FF);
-    for (int i = 0; i < 4; ++i) w.t[i] = take(M * D);
-    w.dqkv = take(M * 3 * D);
-    w.P = take((size_t)B * HEADS * T * T); w.dS = take((size_t)B * HEADS * T * T);
-    w.Pc = take(M * HEADS * MAX_MEM); w.dSc = take(M * HEADS * MAX_MEM);
-    w.dkv = take((size_t)S * B * 2 * D);
-    w.dG = take((size_t)SLOTS * NQ * D); w.dsim = take(M * NQ * SLOTS); w.cj = take(M * SLOTS); w.dwk_tok = take(M * NQ);
-    w.partial = take(((M + 63) / 64 + 1) * FF);
-    w.dtemb = take((size_t)B * D); w.dsz = take((size_t)B * D);
-    w.floats = at;
-    return w;
-}
-
-// The encoder's saves, behind the decoder's plan.  Its scratch (GELU output, d z, the four row buffers, d qkv, P / dS, the QaN items, the column-sum slabs) is the
-// decoder's: the encoder's forward ends before the decoder's begins and its backward begins after the decoder's has ended, and S * B < T * B rows.
-struct EncLayerWs {
-    float *qkv, *ao, *lse, *xh[2], *rs[2], *x1, *z, *G;
-};
-struct EncWs {
-    float *Xp, *h[N_LAYERS + 1], *genc;
-    EncLayerWs layer[N_LAYERS];
-    size_t floats;                                                // decoder plan included
-};
-inline int64_t n_shared() { return layout().t0_w; }               // bodyEmbedding.* and objEmbedding.*: the first four tensors of the table, back to back
-EncWs enc_plan(float *base, size_t at, int B, int S) {
-    EncWs w{};
-    const size_t M = (size_t)B * S;
-    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
-    w.Xp = take(M * CTOK);
-    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
-    w.genc = take((size_t)n_shared());
-    for (int l = 0; l < N_LAYERS; ++l) {
-        EncLayerWs &y = w.layer[l];
-        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
-        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * S); }
-        for (int i = 0; i < 2; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
-        y.x1 = take(M * D); y.z = take(M * FF);
-    }
-    w.floats = at;
-    return w;
-}
-
-// ---- launch helpers: every one returns IDF_OK or IDF_E_LAUNCH ----------------------------------------------------------------------------------------------
-#define MT_TRY(x)                  \
-    do {                           \
-        const int mt_rc_ = (x);    \
-        if (mt_rc_ != IDF_OK) return mt_rc_; \
-    } while (0)
+inline int64_t n_shared(const Layout &L) { return L.t0_w; }      // bodyEmbedding.* and objEmbedding.*: the first four tensors of the table, back to back
 
 int gemm(hipStream_t st, const float *A, int64_t sam, int64_t sak, const float *Bm, int64_t sbk, int64_t sbn, float *C, int64_t ldc, const float *bias, const float *R,
          int64_t ldr, int M, int N, int K) {
@@ -168,10 +25,6 @@ int gemm(hipStream_t st, const float *A, int64_t sam, int64_t sak, const float *
     hipLaunchKernelGGL(mt_gemm_kernel, dim3((unsigned)idf_cdiv(N, 32), (unsigned)idf_cdiv(M, 32)), dim3(64), 0, st, g);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
-}
-// Y[M,N] = X[M,K] W[N,K]^T + b (+ R)
-int lin_fwd(hipStream_t st, const float *X, int64_t ldx, const float *W, const float *b, float *Y, int64_t ldy, const float *R, int64_t ldr, int M, int N, int K) {
-    return gemm(st, X, ldx, 1, W, 1, K, Y, ldy, b, R, ldr, M, N, K);
 }
 // dX[M,K] = dY[M,N] W[N,K] (+ R)
 int lin_dx(hipStream_t st, const float *dY, int64_t ldy, const float *W, float *dX, int64_t ldx, const float *R, int64_t ldr, int M, int N, int K) {
@@ -191,6 +44,18 @@ int colsum(hipStream_t st, const float *A, int64_t lda, const float *Bm, int64_t
     return IDF_OK;
 }
 inline unsigned blocks256(int64_t n) { return (unsigned)idf_cdiv(n, 256); }
+
+// [B][C][T] tokens <-> [B*T][C] rows
+int tokens_to_rows(hipStream_t st, const float *x, float *rows, int B, int T, int C) {
+    hipLaunchKernelGGL(mt_tokens_to_rows_kernel, dim3(blocks256((int64_t)B * T * C)), dim3(256), 0, st, x, rows, B, T, C);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
+int rows_to_tokens(hipStream_t st, const float *rows, float *x, int B, int T, int C) {
+    hipLaunchKernelGGL(mt_rows_to_tokens_kernel, dim3(blocks256((int64_t)B * T * C)), dim3(256), 0, st, rows, x, B, T, C);
+    IDF_CHECK_LAUNCH();
+    return IDF_OK;
+}
 
 int ln_fwd(hipStream_t st, const float *s, const float *gw, const float *gb, float *xh, float *rs, float *y, int M) {
     hipLaunchKernelGGL(mt_ln_fwd_kernel, dim3((unsigned)idf_cdiv(M, 4)), dim3(256), 0, st, s, gw, gb, xh, rs, y, M);
@@ -212,15 +77,9 @@ Weights16 weights_of(const float *w16) {
     return W;
 }
 int loss_grad(hipStream_t st, const float *pred, const float *target, int B, int T, int P, const float *w16, float *dpred) {
-    hipLaunchKernelGGL(mt_loss_grad_kernel, dim3(blocks256((int64_t)B * CTOK * T)), dim3(256), 0, st, pred, target, B, T, P, weights_of(w16), dpred);
+    hipLaunchKernelGGL(mt_loss_grad_kernel, dim3(blocks256((int64_t)B * SMPL_GEOM.ctok * T)), dim3(256), 0, st, pred, target, B, T, P, weights_of(w16), dpred);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
-}
-
-// a linear layer's parameter gradients: dW = dY^T X, db = column sums of dY
-int lin_param_grads(hipStream_t st, const Ws &w, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, float *db, int M, int N, int K) {
-    MT_TRY(lin_dw(st, dY, ldy, X, ldx, dW, M, N, K));
-    return colsum(st, dY, ldy, nullptr, 0, M, N, w.partial, db);
 }
 
 // ---- the sublayers both stacks are made of; Off = LayerOff | EncLayerOff, T = tokens per clip ---------------------------------------------------------------
@@ -243,6 +102,7 @@ int mix_fwd(hipStream_t st, const float *th, const Off &o, bool qan, const float
 // s = x + linear2(gelu(linear1(x))); leaves the pre-activation z
 template <class Off>
 int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const Off &o, const float *x, float *z, float *s, int M) {
+    const int FF = w.geo.ff;
     MT_TRY(lin_fwd(st, x, D, th + o.l1_w, th + o.l1_b, z, FF, nullptr, 0, M, FF, D));
     hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
     IDF_CHECK_LAUNCH();
@@ -251,6 +111,7 @@ int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const Off &o, const fl
 // E = d s (the feed-forward output and, through the residual, d x)  ->  F = d x, and the four parameter gradients
 template <class Off>
 int ffn_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &o, const float *E, const float *x, const float *z, float *F, int M) {
+    const int FF = w.geo.ff;
     hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
     IDF_CHECK_LAUNCH();
     MT_TRY(lin_param_grads(st, w, E, D, w.g, FF, gr + o.l2_w, gr + o.l2_b, M, D, FF));
@@ -286,12 +147,129 @@ int mix_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &
     return lin_dx(st, w.dqkv, 3 * D, th + o.sa_in_w, Dh, D, E, D, M, 3 * D, D);
 }
 
+}  // namespace
+
+namespace mdmtrain {
+
+// the flat master vector: the tensors in the order of interdiff_amd/mdm_train.py PARAM_NAMES, packed without padding
+Layout make_layout(const Geom &g) {
+    Layout o{};
+    int64_t at = 0;
+    int n = 0;
+    auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
+    const int FF = g.ff;
+    take(o.body_w, (int64_t)D * g.nbody); take(o.body_b, D); take(o.obj_w, (int64_t)D * g.nobj); take(o.obj_b, D);
+    take(o.t0_w, (int64_t)D * D); take(o.t0_b, D); take(o.t2_w, (int64_t)D * D); take(o.t2_b, D);
+    for (int l = 0; l < N_LAYERS; ++l) {
+        LayerOff &y = o.layer[l];
+        if (is_qan(l)) {
+            take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
+            y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
+        } else {
+            take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
+            y.queries = y.wk = -1;
+        }
+        take(y.ca_in_w, (int64_t)3 * D * D); take(y.ca_in_b, 3 * D); take(y.ca_out_w, (int64_t)D * D); take(y.ca_out_b, D);
+        take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
+        for (int i = 0; i < 3; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
+    }
+    take(o.bodyf_w, (int64_t)g.hbody * D); take(o.bodyf_b, g.hbody); take(o.objf_w, (int64_t)g.hobj * D); take(o.objf_b, g.hobj);
+    o.total = at;
+    return o;
+}
+
+// the encoder's 84 tensors behind the 144: interdiff_amd/mdm_train.py ENCODER_PARAM_NAMES
+EncLayout make_enc_layout(const Geom &g, const Layout &L) {
+    EncLayout o{};
+    int64_t at = L.total;
+    int n = 0;
+    auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
+    const int FF = g.ff;
+    for (int l = 0; l < N_LAYERS; ++l) {
+        EncLayerOff &y = o.layer[l];
+        if (is_qan(l)) {
+            take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
+            y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
+        } else {
+            take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
+            y.queries = y.wk = -1;
+        }
+        take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
+        for (int i = 0; i < 2; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
+    }
+    o.total = at;
+    return o;
+}
+
+// ---- workspace plan (floats) ---------------------------------------------------------------------------------------------------------------------------
+Ws plan(float *base, const Geom &g, int B, int T, int S) {
+    Ws w{};
+    w.geo = g;
+    size_t at = 0;
+    const size_t M = (size_t)B * T, FF = (size_t)g.ff, CTOK = (size_t)g.ctok;
+    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    w.X = take(M * CTOK); w.Y = take(M * CTOK); w.dY = take(M * CTOK);
+    w.tin = take((size_t)B * D); w.z0 = take((size_t)B * D); w.sz = take((size_t)B * D); w.temb = take((size_t)B * D);
+    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
+    for (int l = 0; l < N_LAYERS; ++l) {
+        LayerWs &y = w.layer[l];
+        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
+        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * T); }
+        for (int i = 0; i < 3; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
+        y.x1 = take(M * D); y.x2 = take(M * D); y.q2 = take(M * D); y.kv = take((size_t)S * B * 2 * D); y.o2 = take(M * D); y.z = take(M * FF);
+    }
+    w.g = take(M * FF); w.dz = take(M * FF);
+    for (int i = 0; i < 4; ++i) w.t[i] = take(M * D);
+    w.dqkv = take(M * 3 * D);
+    w.P = take((size_t)B * HEADS * T * T); w.dS = take((size_t)B * HEADS * T * T);
+    w.Pc = take(M * HEADS * MAX_MEM); w.dSc = take(M * HEADS * MAX_MEM);
+    w.dkv = take((size_t)S * B * 2 * D);
+    w.dG = take((size_t)SLOTS * NQ * D); w.dsim = take(M * NQ * SLOTS); w.cj = take(M * SLOTS); w.dwk_tok = take(M * NQ);
+    w.partial = take(((M + 63) / 64 + 1) * (FF > (size_t)3 * D ? FF : (size_t)3 * D));      // the widest column sum: a feed-forward bias or the q|k|v bias
+    w.dtemb = take((size_t)B * D); w.dsz = take((size_t)B * D);
+    w.floats = at;
+    return w;
+}
+
+// The encoder's saves, behind the decoder's plan.  Its scratch (GELU output, d z, the four row buffers, d qkv, P / dS, the QaN items, the column-sum slabs) is the
+// decoder's: the encoder's forward ends before the decoder's begins and its backward begins after the decoder's has ended, and S * B < T * B rows.
+EncWs enc_plan(float *base, size_t at, const Geom &g, const Layout &L, int B, int S) {
+    EncWs w{};
+    const size_t M = (size_t)B * S, FF = (size_t)g.ff;
+    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    w.Xp = take(M * g.ctok);
+    for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
+    w.genc = take((size_t)n_shared(L));
+    for (int l = 0; l < N_LAYERS; ++l) {
+        EncLayerWs &y = w.layer[l];
+        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
+        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * S); }
+        for (int i = 0; i < 2; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
+        y.x1 = take(M * D); y.z = take(M * FF);
+    }
+    w.floats = at;
+    return w;
+}
+
+bool shape_ok(const Geom &g, int B, int T, int S, int past_len) {
+    return B > 0 && T > 0 && T <= MAX_T && S > 0 && S <= MAX_MEM && past_len >= 2 && T >= past_len + 2 && (int64_t)B * T * (g.ff > 3 * D ? g.ff : 3 * D) < 0x7FFFFFFF;
+}
+
+// ---- launchers the model-specific files use too ----------------------------------------------------------------------------------------------------------
+int lin_fwd(hipStream_t st, const float *X, int64_t ldx, const float *W, const float *b, float *Y, int64_t ldy, const float *R, int64_t ldr, int M, int N, int K) {
+    return gemm(st, X, ldx, 1, W, 1, K, Y, ldy, b, R, ldr, M, N, K);
+}
+int lin_param_grads(hipStream_t st, const Ws &w, const float *dY, int64_t ldy, const float *X, int64_t ldx, float *dW, float *db, int M, int N, int K) {
+    MT_TRY(lin_dw(st, dY, ldy, X, ldx, dW, M, N, K));
+    return colsum(st, dY, ldy, nullptr, 0, M, N, w.partial, db);
+}
+
 // ---- forward with saves ---------------------------------------------------------------------------------------------------------------------------------
 int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *pe, int pe_rows, const float *x_t, const int64_t *ts, const float *cond, int B, int T,
-            int S, float *pred) {
-    const int M = B * T, SB = S * B;
-    hipLaunchKernelGGL(mt_tokens_to_rows_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, x_t, w.X, B, T);
-    IDF_CHECK_LAUNCH();
+            int S) {
+    const Geom &g = w.geo;
+    const int M = B * T, SB = S * B, CTOK = g.ctok, HEAD = g.head();
+    MT_TRY(tokens_to_rows(st, x_t, w.X, B, T, CTOK));
     // timestep MLP (layers.py:42-43)
     hipLaunchKernelGGL(mt_gather_pe_kernel, dim3((unsigned)B), dim3(256), 0, st, pe, pe_rows, ts, w.tin);
     IDF_CHECK_LAUNCH();
@@ -299,9 +277,9 @@ int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const
     hipLaunchKernelGGL(mt_silu_kernel, dim3(blocks256((int64_t)B * D)), dim3(256), 0, st, w.z0, w.sz, (int64_t)B * D);
     IDF_CHECK_LAUNCH();
     MT_TRY(lin_fwd(st, w.sz, D, th + L.t2_w, th + L.t2_b, w.temb, D, nullptr, 0, B, D, D));
-    // embedding: bodyEmbedding(x[:135]) + objEmbedding(x[135:]) + temb + pe[t]
-    MT_TRY(lin_fwd(st, w.X, CTOK, th + L.body_w, th + L.body_b, w.h[0], D, nullptr, 0, M, D, NBODY));
-    MT_TRY(lin_fwd(st, w.X + NBODY, CTOK, th + L.obj_w, th + L.obj_b, w.h[0], D, w.h[0], D, M, D, CTOK - NBODY));
+    // embedding: bodyEmbedding(x[:nbody]) + objEmbedding(x[nbody : nbody + nobj]) + temb + pe[t]
+    MT_TRY(lin_fwd(st, w.X, CTOK, th + L.body_w, th + L.body_b, w.h[0], D, nullptr, 0, M, D, g.nbody));
+    MT_TRY(lin_fwd(st, w.X + g.nbody, CTOK, th + L.obj_w, th + L.obj_b, w.h[0], D, w.h[0], D, M, D, g.nobj));
     hipLaunchKernelGGL(mt_add_temb_pe_kernel, dim3((unsigned)M), dim3(256), 0, st, w.h[0], w.temb, pe, T);
     IDF_CHECK_LAUNCH();
     for (int l = 0; l < N_LAYERS; ++l) {
@@ -328,24 +306,20 @@ int forward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const
             MT_TRY(ln_fwd(st, s, th + o.ln_w[2], th + o.ln_b[2], y.xh[2], y.rs[2], w.h[l + 1], M));
         }
     }
-    MT_TRY(lin_fwd(st, w.h[N_LAYERS], D, th + L.bodyf_w, th + L.bodyf_b, w.Y, CTOK, nullptr, 0, M, NBODY, D));
-    MT_TRY(lin_fwd(st, w.h[N_LAYERS], D, th + L.objf_w, th + L.objf_b, w.Y + NBODY, CTOK, nullptr, 0, M, CTOK - NBODY, D));
-    hipLaunchKernelGGL(mt_rows_to_tokens_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, w.Y, pred, B, T);
-    IDF_CHECK_LAUNCH();
-    return IDF_OK;
+    MT_TRY(lin_fwd(st, w.h[N_LAYERS], D, th + L.bodyf_w, th + L.bodyf_b, w.Y, HEAD, nullptr, 0, M, g.hbody, D));
+    return lin_fwd(st, w.h[N_LAYERS], D, th + L.objf_w, th + L.objf_b, w.Y + g.hbody, HEAD, nullptr, 0, M, g.hobj, D);
 }
 
-// ---- backward: d_pred [B,1,144,T] -> grads [n_param], d_cond [S][B][256] ------------------------------------------------------------------------------------
-int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *cond, const float *d_pred, int B, int T, int S, float *gr, float *d_cond) {
-    const int M = B * T, SB = S * B;
-    hipLaunchKernelGGL(mt_tokens_to_rows_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, d_pred, w.dY, B, T);
-    IDF_CHECK_LAUNCH();
+// ---- backward: w.dY [B*T][head()] -> grads [n_param], d_cond [S][B][256] ------------------------------------------------------------------------------------
+int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, const float *cond, int B, int T, int S, float *gr, float *d_cond) {
+    const Geom &g = w.geo;
+    const int M = B * T, SB = S * B, CTOK = g.ctok, HEAD = g.head();
     float *Dh = w.t[0], *E = w.t[1], *F = w.t[2], *Gq = w.t[3];
     // the two output heads
-    MT_TRY(lin_param_grads(st, w, w.dY, CTOK, w.h[N_LAYERS], D, gr + L.bodyf_w, gr + L.bodyf_b, M, NBODY, D));
-    MT_TRY(lin_param_grads(st, w, w.dY + NBODY, CTOK, w.h[N_LAYERS], D, gr + L.objf_w, gr + L.objf_b, M, CTOK - NBODY, D));
-    MT_TRY(lin_dx(st, w.dY, CTOK, th + L.bodyf_w, Dh, D, nullptr, 0, M, NBODY, D));
-    MT_TRY(lin_dx(st, w.dY + NBODY, CTOK, th + L.objf_w, Dh, D, Dh, D, M, CTOK - NBODY, D));
+    MT_TRY(lin_param_grads(st, w, w.dY, HEAD, w.h[N_LAYERS], D, gr + L.bodyf_w, gr + L.bodyf_b, M, g.hbody, D));
+    MT_TRY(lin_param_grads(st, w, w.dY + g.hbody, HEAD, w.h[N_LAYERS], D, gr + L.objf_w, gr + L.objf_b, M, g.hobj, D));
+    MT_TRY(lin_dx(st, w.dY, HEAD, th + L.bodyf_w, Dh, D, nullptr, 0, M, g.hbody, D));
+    MT_TRY(lin_dx(st, w.dY + g.hbody, HEAD, th + L.objf_w, Dh, D, Dh, D, M, g.hobj, D));
     bool first_cond = true;
     for (int l = N_LAYERS - 1; l >= 0; --l) {
         const LayerOff &o = L.layer[l];
@@ -371,8 +345,8 @@ int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, cons
         MT_TRY(mix_bwd(st, w, th, gr, o, is_qan(l), E, xin, y.qkv, y.ao, y.lse, y.G, F, Dh, B, T));
     }
     // embedding and the timestep MLP: Dh = d h0
-    MT_TRY(lin_param_grads(st, w, Dh, D, w.X, CTOK, gr + L.body_w, gr + L.body_b, M, D, NBODY));
-    MT_TRY(lin_param_grads(st, w, Dh, D, w.X + NBODY, CTOK, gr + L.obj_w, gr + L.obj_b, M, D, CTOK - NBODY));
+    MT_TRY(lin_param_grads(st, w, Dh, D, w.X, CTOK, gr + L.body_w, gr + L.body_b, M, D, g.nbody));
+    MT_TRY(lin_param_grads(st, w, Dh, D, w.X + g.nbody, CTOK, gr + L.obj_w, gr + L.obj_b, M, D, g.nobj));
     hipLaunchKernelGGL(mt_sum_frames_kernel, dim3((unsigned)B), dim3(256), 0, st, Dh, w.dtemb, T);
     IDF_CHECK_LAUNCH();
     MT_TRY(lin_param_grads(st, w, w.dtemb, D, w.sz, D, gr + L.t2_w, gr + L.t2_b, B, D, D));
@@ -383,16 +357,17 @@ int backward(hipStream_t st, const Layout &L, const Ws &w, const float *th, cons
     return IDF_OK;
 }
 
-// ---- the encoder: MDM._get_embeddings from pc_embedding on (diffusion_smpl.py:217-221), S = past_len tokens per clip ----------------------------------------
-// th holds the 228 tensors; target [B][144][T] gives the past frames; pc [B][256]; cond [S][B][256] is written in the memory's own order.
+// ---- the encoder: MDM._get_embeddings from the per-clip row on (diffusion_smpl.py:217-221, diffusion_skeleton.py:208-213), S = past_len tokens per clip -------
+// th holds the 228 tensors; target [B][ctok][T] gives the past frames; pc [B][256]; cond [S][B][256] is written in the memory's own order.
 int enc_forward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &w, const EncWs &e, const float *th, const float *pe, const float *target, const float *pc,
                 int B, int T, int S, float *cond) {
-    const int M = B * S;
-    hipLaunchKernelGGL(mt_gather_past_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, target, e.Xp, B, T, S);
+    const Geom &g = w.geo;
+    const int M = B * S, CTOK = g.ctok;
+    hipLaunchKernelGGL(mt_gather_past_kernel, dim3(blocks256((int64_t)M * CTOK)), dim3(256), 0, st, target, e.Xp, B, T, S, CTOK);
     IDF_CHECK_LAUNCH();
     // embedding: (bodyEmbedding(body) + objEmbedding(obj) + pc_embedding) + pe[s] -- the decoder's kernel with pc in the place of the timestep embedding
-    MT_TRY(lin_fwd(st, e.Xp, CTOK, th + L.body_w, th + L.body_b, e.h[0], D, nullptr, 0, M, D, NBODY));
-    MT_TRY(lin_fwd(st, e.Xp + NBODY, CTOK, th + L.obj_w, th + L.obj_b, e.h[0], D, e.h[0], D, M, D, CTOK - NBODY));
+    MT_TRY(lin_fwd(st, e.Xp, CTOK, th + L.body_w, th + L.body_b, e.h[0], D, nullptr, 0, M, D, g.nbody));
+    MT_TRY(lin_fwd(st, e.Xp + g.nbody, CTOK, th + L.obj_w, th + L.obj_b, e.h[0], D, e.h[0], D, M, D, g.nobj));
     hipLaunchKernelGGL(mt_add_temb_pe_kernel, dim3((unsigned)M), dim3(256), 0, st, e.h[0], pc, pe, S);
     IDF_CHECK_LAUNCH();
     for (int l = 0; l < N_LAYERS; ++l) {
@@ -420,7 +395,8 @@ int enc_forward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &
 // holds), d_pc [B][256]
 int enc_backward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &w, const EncWs &e, const float *th, const float *d_cond, int B, int S, float *gr,
                  float *d_pc) {
-    const int M = B * S;
+    const Geom &g = w.geo;
+    const int M = B * S, CTOK = g.ctok;
     float *Dh = w.t[0], *E = w.t[1], *F = w.t[2];
     hipLaunchKernelGGL(mt_swap_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, d_cond, Dh, S, B);
     IDF_CHECK_LAUNCH();
@@ -435,15 +411,40 @@ int enc_backward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws 
     // Dh = d embedding: pe takes nothing, pc_embedding the sum over a clip's tokens in token order, the two shared linears their encoder-path share
     hipLaunchKernelGGL(mt_sum_frames_kernel, dim3((unsigned)B), dim3(256), 0, st, Dh, d_pc, S);
     IDF_CHECK_LAUNCH();
-    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp, CTOK, e.genc + L.body_w, e.genc + L.body_b, M, D, NBODY));
-    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp + NBODY, CTOK, e.genc + L.obj_w, e.genc + L.obj_b, M, D, CTOK - NBODY));
-    hipLaunchKernelGGL(mt_add_into_kernel, dim3(blocks256(n_shared())), dim3(256), 0, st, gr, e.genc, n_shared());
+    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp, CTOK, e.genc + L.body_w, e.genc + L.body_b, M, D, g.nbody));
+    MT_TRY(lin_param_grads(st, w, Dh, D, e.Xp + g.nbody, CTOK, e.genc + L.obj_w, e.genc + L.obj_b, M, D, g.nobj));
+    hipLaunchKernelGGL(mt_add_into_kernel, dim3(blocks256(n_shared(L))), dim3(256), 0, st, gr, e.genc, n_shared(L));
     IDF_CHECK_LAUNCH();
     return IDF_OK;
 }
 
-bool shape_ok(int B, int T, int S, int past_len) {
-    return B > 0 && T > 0 && T <= MAX_T && S > 0 && S <= MAX_MEM && past_len >= 2 && T >= past_len + 2 && (int64_t)B * T * FF < 0x7FFFFFFF;
+}  // namespace mdmtrain
+
+// ---- the SMPL trainer's entries -------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr Geom GEO = SMPL_GEOM;
+const Layout &layout() {
+    static const Layout L = make_layout(GEO);
+    return L;
+}
+const EncLayout &enc_layout() {
+    static const EncLayout L = make_enc_layout(GEO, layout());
+    return L;
+}
+// w.Y [B*T][144] -> pred [B,1,144,T]
+int emit_pred(hipStream_t st, const Ws &w, int B, int T, float *pred) { return rows_to_tokens(st, w.Y, pred, B, T, GEO.ctok); }
+// the terms, the loss gradient (or d_pred_in in its place) as rows in w.dY
+int terms_and_d_rows(hipStream_t st, const Ws &w, const float *pred, const float *target, int B, int T, int past_len, const float *weights16, const float *d_pred_in,
+                     float *terms, void *stream) {
+    MT_TRY(interdiff_denoising_losses(pred, target, B, T, past_len, terms, stream));
+    const float *dp = d_pred_in;
+    if (!dp) {
+        float *mine = w.g;                                        // (free between the forward and the backward; M * 1024 >= B * 144 * T floats)
+        MT_TRY(loss_grad(st, pred, target, B, T, past_len, weights16, mine));
+        dp = mine;
+    }
+    return tokens_to_rows(st, dp, w.dY, B, T, GEO.ctok);
 }
 
 }  // namespace
@@ -466,29 +467,24 @@ extern "C" int interdiff_mdm_train_param_table(int64_t *offsets, int64_t *sizes,
 }
 
 extern "C" size_t interdiff_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t mem_len) {
-    if (B <= 0 || T <= 0 || T > MAX_T || mem_len <= 0 || mem_len > MAX_MEM || (int64_t)B * T * FF >= 0x7FFFFFFF) return 0;
-    return plan(nullptr, B, T, mem_len).floats * sizeof(float);
+    if (B <= 0 || T <= 0 || T > MAX_T || mem_len <= 0 || mem_len > MAX_MEM || (int64_t)B * T * GEO.ff >= 0x7FFFFFFF) return 0;
+    return plan(nullptr, GEO, B, T, mem_len).floats * sizeof(float);
 }
 
 extern "C" int interdiff_mdm_train_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *cond, const float *target,
                                          int32_t B, int32_t T, int32_t mem_len, int32_t past_len, const float *weights16, const float *d_pred_in, float *grads,
                                          float *d_cond, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
     if (!params || !pe || !x_t || !ts || !cond || !target || !weights16 || !grads || !d_cond || !pred || !terms || !ws) return IDF_E_INVAL;
-    if (!shape_ok(B, T, mem_len, past_len) || pe_rows < T) return IDF_E_INVAL;
+    if (!shape_ok(GEO, B, T, mem_len, past_len) || pe_rows < T) return IDF_E_INVAL;
     if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
     if (ws_bytes < interdiff_mdm_train_workspace_bytes(B, T, mem_len)) return IDF_E_NOMEM;
     hipStream_t st = idf_stream(stream);
     const Layout &L = layout();
-    const Ws w = plan(static_cast<float *>(ws), B, T, mem_len);
-    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, mem_len, pred));
-    MT_TRY(interdiff_denoising_losses(pred, target, B, T, past_len, terms, stream));
-    const float *dp = d_pred_in;
-    if (!dp) {
-        float *mine = w.g;                                        // (free between the forward and the backward; M * 1024 >= B * 144 * T floats)
-        MT_TRY(loss_grad(st, pred, target, B, T, past_len, weights16, mine));
-        dp = mine;
-    }
-    return backward(st, L, w, params, cond, dp, B, T, mem_len, grads, d_cond);
+    const Ws w = plan(static_cast<float *>(ws), GEO, B, T, mem_len);
+    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, mem_len));
+    MT_TRY(emit_pred(st, w, B, T, pred));
+    MT_TRY(terms_and_d_rows(st, w, pred, target, B, T, past_len, weights16, d_pred_in, terms, stream));
+    return backward(st, L, w, params, cond, B, T, mem_len, grads, d_cond);
 }
 
 extern "C" int interdiff_mdm_train_full_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
@@ -504,32 +500,27 @@ extern "C" int interdiff_mdm_train_full_param_table(int64_t *offsets, int64_t *s
 }
 
 extern "C" size_t interdiff_mdm_train_full_workspace_bytes(int32_t B, int32_t T, int32_t past_len) {
-    if (!shape_ok(B, T, past_len, past_len)) return 0;
-    return enc_plan(nullptr, plan(nullptr, B, T, past_len).floats, B, past_len).floats * sizeof(float);
+    if (!shape_ok(GEO, B, T, past_len, past_len)) return 0;
+    return enc_plan(nullptr, plan(nullptr, GEO, B, T, past_len).floats, GEO, layout(), B, past_len).floats * sizeof(float);
 }
 
 extern "C" int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *pc,
                                               const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, const float *d_pred_in, float *grads,
                                               float *cond, float *d_cond, float *d_pc, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
     if (!params || !pe || !x_t || !ts || !pc || !target || !weights16 || !grads || !cond || !d_cond || !d_pc || !pred || !terms || !ws) return IDF_E_INVAL;
-    if (!shape_ok(B, T, past_len, past_len) || pe_rows < T) return IDF_E_INVAL;
+    if (!shape_ok(GEO, B, T, past_len, past_len) || pe_rows < T) return IDF_E_INVAL;
     if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
     if (ws_bytes < interdiff_mdm_train_full_workspace_bytes(B, T, past_len)) return IDF_E_NOMEM;
     hipStream_t st = idf_stream(stream);
     const Layout &L = layout();
     const EncLayout &EL = enc_layout();
-    const Ws w = plan(static_cast<float *>(ws), B, T, past_len);
-    const EncWs e = enc_plan(static_cast<float *>(ws), w.floats, B, past_len);
+    const Ws w = plan(static_cast<float *>(ws), GEO, B, T, past_len);
+    const EncWs e = enc_plan(static_cast<float *>(ws), w.floats, GEO, L, B, past_len);
     MT_TRY(enc_forward(st, L, EL, w, e, params, pe, target, pc, B, T, past_len, cond));
-    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, past_len, pred));
-    MT_TRY(interdiff_denoising_losses(pred, target, B, T, past_len, terms, stream));
-    const float *dp = d_pred_in;
-    if (!dp) {
-        float *mine = w.g;
-        MT_TRY(loss_grad(st, pred, target, B, T, past_len, weights16, mine));
-        dp = mine;
-    }
-    MT_TRY(backward(st, L, w, params, cond, dp, B, T, past_len, grads, d_cond));
+    MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, past_len));
+    MT_TRY(emit_pred(st, w, B, T, pred));
+    MT_TRY(terms_and_d_rows(st, w, pred, target, B, T, past_len, weights16, d_pred_in, terms, stream));
+    MT_TRY(backward(st, L, w, params, cond, B, T, past_len, grads, d_cond));
     return enc_backward(st, L, EL, w, e, params, d_cond, B, past_len, grads, d_pc);
 }
 
