@@ -894,6 +894,35 @@ int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t
                                    void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Fine-tuning of the SMPL denoiser's PointNet++ (csrc/pointnet2.hip, csrc/pointnet2_train.h / .hip): consumes the d_pc of the entry above.  Additive entries:
+ * interdiff_abi_version() stays what it was.  Regime: pcEmbedding in eval() with autograd on (frozen running statistics); batch statistics are not built.
+ *
+ *  interdiff_pointnet2_encode_saved   replaces PointNet2Encoder.forward (model/layers.py:141-175) as MDM._get_embeddings calls it with autograd on
+ *      (model/diffusion_smpl.py:210-211): out [B,256] has the bits of interdiff_pointnet2_encode, and `saves` (interdiff_pointnet2_saves_bytes(B) bytes, 4-byte
+ *      aligned) receives per clip what autograd would keep: the 48 SA2 slots as FPS position, point id and duplicate-slot map, the 16 + 32 neighbour point ids
+ *      of every centre, the hit counts of all ball queries, the SA1 output of each slot (layout: csrc/pointnet2_train.h).
+ *  interdiff_pointnet2_finetune_grads replaces loss.backward() through pcEmbedding (train_diffusion_smpl.py:60-166 with the module of model/layers.py:111-175):
+ *      grads [113,917] = d sum(d_pc * pc) / d theta for the 38 raw tensors of the PARAMETER TABLE below.  It runs no sampling and no ball query; activations,
+ *      ReLU masks and pool winners are recomputed from `saves` and the folded arena of `pn`, which must be the fold of `theta` / `stats` (interdiff_pointnet2_refold).
+ *      d_pc[:, 0:3] (the key point's xyz) reaches no parameter; no gradient with respect to obj_points.  fp32, fixed summation order, clips folded in index
+ *      order in double, no atomics.  ws: interdiff_pointnet2_finetune_workspace_bytes(B) bytes, 256-byte aligned.
+ *  interdiff_pointnet2_refold         replaces the host fold of eval BatchNorm (mdm.py pack_pointnet2; the reference's BatchNorm2d.forward in eval(), applied by
+ *      torch at every call): rewrites pn->arena from theta and stats on the stream, no host round trip; stats are read and never written.
+ *  interdiff_pointnet2_finetune_param_table   PARAMETER TABLE: the 38 tensors in the reference's state_dict order -- for SA_modules.{0,1}.mlps.{0,1} and layer
+ *      l = 0..2: `.{3l}.weight` [cout,cin,1,1], `.{3l+1}.weight` [cout], `.{3l+1}.bias` [cout]; then Linear.weight [253,256], Linear.bias [253].
+ *      stats [1472]: per layer, in the same order, running_mean [cout] then running_var [cout].
+ * The optimiser step is interdiff_mdm_train_step on the flat vectors (torch.optim.AdamW.step, train_diffusion_smpl.py:177-183).
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_pointnet2_saves_bytes(int32_t B);
+int interdiff_pointnet2_encode_saved(const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out, void *saves, size_t saves_bytes,
+                                     void *stream);
+int interdiff_pointnet2_finetune_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param);
+size_t interdiff_pointnet2_finetune_workspace_bytes(int32_t B);
+int interdiff_pointnet2_finetune_grads(const idf_pointnet2 *pn, const float *theta, const float *stats, const float *obj_points, int32_t B, int32_t P,
+                                       const void *saves, const float *d_pc, float *grads, void *ws, size_t ws_bytes, void *stream);
+int interdiff_pointnet2_refold(const idf_pointnet2 *pn, const float *theta, const float *stats, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Scoring of a skeleton diffusion checkpoint (csrc/skeleton_losses.hip): the forward, scoring side of interdiff/train_diffusion_skeleton.py.
  * Forward only, additive.  Tokens [B,1,C,T] with C = n_body + 3 * n_points + 7 (63 + 36 + 7 = 106): body | object keypoints | object
  * translation 3 | object quaternion xyzw 4.  The keypoint channels are the prediction's own (the denoiser's keypoint head wrote them): nothing is

@@ -199,6 +199,12 @@ _SIGS = {
     'interdiff_mdm_train_full_param_table': (C.c_int, [C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
     'interdiff_mdm_train_full_workspace_bytes': (sz, [i32, i32, i32]),
     'interdiff_mdm_train_full_grads': (C.c_int, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'interdiff_pointnet2_saves_bytes': (sz, [i32]),
+    'interdiff_pointnet2_encode_saved': (C.c_int, [C.POINTER(PointNet2), vp, i32, i32, vp, vp, sz, vp]),
+    'interdiff_pointnet2_finetune_param_table': (C.c_int, [C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]),
+    'interdiff_pointnet2_finetune_workspace_bytes': (sz, [i32]),
+    'interdiff_pointnet2_finetune_grads': (C.c_int, [C.POINTER(PointNet2), vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    'interdiff_pointnet2_refold': (C.c_int, [C.POINTER(PointNet2), vp, vp, vp]),
     'interdiff_skeleton_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_sample_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),

@@ -11,17 +11,13 @@
 //   3. evaluates the SA1 multi-scale grouping + shared MLPs for those centres only,
 //   4. evaluates SA2 and the final Linear.
 // Eval-mode BatchNorm is folded into the 1x1 convolutions on the host (interdiff_amd/mdm.py: pack_pointnet2).
-#include "common.h"
+// interdiff_pointnet2_encode_saved is the same kernel (SAVE = true) that also writes the per-clip record the backward reads (csrc/pointnet2_train.h).
+#include "pointnet2_train.h"
 #include <float.h>
 
 namespace {
 
-constexpr int PT = 1024, NWV = PT / 64;
-constexpr int MAXP = 2048;                 // points per cloud (two per thread)
-constexpr int NP1 = 1024;                  // SA1 npoint
-constexpr int NS0 = 16, NS1 = 32, NSLOT = NS0 + NS1;
-constexpr int F1 = 96;                     // SA1 output channels (32 + 64)
-constexpr int CIN2 = F1 + 3;               // SA2 input channels
+using namespace pn2;
 
 __device__ __forceinline__ float d2_exact(float ax, float ay, float az, float bx, float by, float bz) {
 #pragma clang fp contract(off)
@@ -48,18 +44,6 @@ __device__ __forceinline__ int block_rank(bool hit, unsigned *wcount, int &total
     return base + below;
 }
 
-// out[n][o] = relu(b[o] + sum_c W[o][c] in[n][c]) for n < ns, o < cout
-__device__ __forceinline__ void mlp_layer(const float *in, int in_stride, const float *__restrict__ W, const float *__restrict__ bias,
-                                          int cin, int cout, int ns, float *out, int out_stride) {
-    for (int i = threadIdx.x; i < ns * cout; i += PT) {
-        const int n = i / cout, o = i - n * cout;
-        const float *w = W + (size_t)o * cin, *x = in + n * in_stride;
-        float s = bias[o];
-        for (int c = 0; c < cin; ++c) s += w[c] * x[c];
-        out[n * out_stride + o] = fmaxf(s, 0.f);
-    }
-}
-
 __device__ __forceinline__ void maxpool(const float *a, int stride, int ns, int cout, float *dst) {
     for (int o = threadIdx.x; o < cout; o += PT) {
         float m = a[o];
@@ -68,8 +52,9 @@ __device__ __forceinline__ void maxpool(const float *a, int stride, int ns, int 
     }
 }
 
+template <bool SAVE>
 __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, const float *__restrict__ obj_points, int P,
-                                                       float *__restrict__ out) {
+                                                       float *__restrict__ out, int *__restrict__ saves) {
     __shared__ float4 pts[MAXP];                       // x, y, z, ||p||
     __shared__ unsigned short fps[NP1];
     __shared__ float redv[2][NWV];
@@ -82,6 +67,7 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
     __shared__ float f2[256];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *ar = pn.arena;
+    int *sv = SAVE ? saves + (size_t)b * SV_WORDS : nullptr;
 
     // ---- 0. the cloud
     for (int i = tid; i < MAXP; i += PT) {
@@ -147,11 +133,13 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
         if (d2 < r0 * r0 && rk < NS0) list[rk] = tid;
         __syncthreads();
         if (tid < NS0 && tid >= tot) list[tid] = tot > 0 ? list[0] : 0;
+        if (SAVE && tid == 0) sv[SV_CNT] = tot;
         __syncthreads();
         rk = block_rank(d2 < r1 * r1, wcount, tot);
         if (d2 < r1 * r1 && rk < NS1) list[NS0 + rk] = tid;
         __syncthreads();
         if (tid < NS1 && tid >= tot) list[NS0 + tid] = tot > 0 ? list[NS0] : 0;
+        if (SAVE && tid == 0) sv[SV_CNT + 1] = tot;
         __syncthreads();
     }
 
@@ -193,6 +181,11 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
         const int t1 = tlo + thi;
         if (tid < NS1 && tid >= t1) nb1[tid] = t1 > 0 ? nb1[0] : 0;
         __syncthreads();
+        if (SAVE) {
+            if (tid < NS0) sv[SV_NB0 + s * NS0 + tid] = nb0[tid];
+            else if (tid < NS0 + NS1) sv[SV_NB1 + s * NS1 + tid - NS0] = nb1[tid - NS0];
+            else if (tid == NS0 + NS1) { sv[SV_CNT + 2 + s] = t0; sv[SV_CNT + 2 + NSLOT + s] = t1; }
+        }
         // grouped inputs [xyz_j - centre | ||p_j||]: scale 0 in xin[0 .. 16*4), scale 1 in xin[64 .. 64 + 32*4)
         if (tid < NS0 + NS1) {
             const bool sc1 = tid >= NS0;
@@ -215,6 +208,20 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
         maxpool(a3, 32, NS0, 32, &feat1[s][0]);
         maxpool(a3 + 512, 64, NS1, 64, &feat1[s][32]);
         __syncthreads();
+    }
+
+    if (SAVE) {
+        if (tid < NSLOT) {
+            const int pid = fps[list[tid]];
+            int dup = tid;
+            for (int e = 0; e < tid; ++e)
+                if (fps[list[e]] == pid) { dup = e; break; }
+            sv[SV_POS + tid] = list[tid];
+            sv[SV_PID + tid] = pid;
+            sv[SV_DUP + tid] = dup;
+            if (dup != tid) { sv[SV_CNT + 2 + tid] = sv[SV_CNT + 2 + dup]; sv[SV_CNT + 2 + NSLOT + tid] = sv[SV_CNT + 2 + NSLOT + dup]; }
+        }
+        for (int i = tid; i < NSLOT * F1; i += PT) reinterpret_cast<float *>(sv)[SV_FEAT + i] = feat1[i / F1][i % F1];
     }
 
     // ---- 4. SA2 around the key point (MLPs 99-64-64-128 and 99-64-96-128), max pool, Linear 256 -> 253
@@ -254,8 +261,7 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
 
 }  // namespace
 
-extern "C" int interdiff_pointnet2_encode(const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out,
-                                          void *stream) {
+static int encode(const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out, void *saves, void *stream) {
     if (!pn || !pn->arena || !obj_points || !out || B <= 0 || P < 1 || P > MAXP) return IDF_E_INVAL;
     if (pn->sa1[0].c[0] != 4 || pn->sa1[0].c[1] != 16 || pn->sa1[0].c[2] != 16 || pn->sa1[0].c[3] != 32 || pn->sa1[1].c[0] != 4 ||
         pn->sa1[1].c[1] != 32 || pn->sa1[1].c[2] != 32 || pn->sa1[1].c[3] != 64)
@@ -264,8 +270,25 @@ extern "C" int interdiff_pointnet2_encode(const idf_pointnet2 *pn, const float *
         if (pn->sa2[sc].c[0] != CIN2 || pn->sa2[sc].c[1] > 64 || pn->sa2[sc].c[2] > 96 || pn->sa2[sc].c[3] != 128) return IDF_E_INVAL;
     hipStream_t s = idf_stream(stream);
     idf_prof_mark(IDF_K_OTHER, s);
-    hipLaunchKernelGGL(pointnet2_kernel, dim3(B), dim3(PT), 0, s, *pn, obj_points, P, out);
+    if (saves)
+        hipLaunchKernelGGL(pointnet2_kernel<true>, dim3(B), dim3(PT), 0, s, *pn, obj_points, P, out, static_cast<int *>(saves));
+    else
+        hipLaunchKernelGGL(pointnet2_kernel<false>, dim3(B), dim3(PT), 0, s, *pn, obj_points, P, out, static_cast<int *>(nullptr));
     idf_prof_mark(-1, s);
     IDF_CHECK_LAUNCH();
     return IDF_OK;
+}
+
+extern "C" int interdiff_pointnet2_encode(const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out,
+                                          void *stream) {
+    return encode(pn, obj_points, B, P, out, nullptr, stream);
+}
+
+extern "C" size_t interdiff_pointnet2_saves_bytes(int32_t B) { return B > 0 ? (size_t)B * pn2::SV_WORDS * sizeof(int32_t) : 0; }
+
+extern "C" int interdiff_pointnet2_encode_saved(const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out, void *saves,
+                                                size_t saves_bytes, void *stream) {
+    if (!saves || (reinterpret_cast<uintptr_t>(saves) & 3)) return IDF_E_INVAL;
+    if (B > 0 && saves_bytes < interdiff_pointnet2_saves_bytes(B)) return IDF_E_NOMEM;
+    return encode(pn, obj_points, B, P, out, saves, stream);
 }

@@ -19,6 +19,12 @@ exact fp32, no float atomics -- two calls give the same bits.  torch holds the d
 ``LitInteraction._common_step`` (train_diffusion_smpl.py:381-388) has it with autograd on.  The 84 encoder tensors (``ENCODER_PARAM_NAMES``; 4,754,492
 parameters) follow the 144 in the flat vectors, bodyEmbedding / objEmbedding receive the sum of both paths, and a batch carries ``pc`` [B,256] or raw
 ``obj_points`` [B,P,3] instead of ``cond``.  ``pc_embedding`` is the new input seam: ``d_pc`` [B,256] is returned, ``pcEmbedding.*`` is carried through.
+
+``DenoiserTrainer(state_dict, train_encoder=True, train_pointnet=True)`` closes the ``d_pc`` seam too: ``pcEmbedding`` (the PointNet++ object encoder,
+model/diffusion_smpl.py:210-211) is trained with frozen normalisation statistics -- the module in ``eval()`` with autograd on (interdiff_amd/pointnet2_train.py says
+what that regime is and what is not built).  Its 38 tensors (``POINTNET_PARAM_NAMES``; 113,917 parameters) follow the 228 in the flat vectors, a batch carries raw
+``obj_points`` [B,P,3] (never ``pc`` or ``cond``: their gradient could not reach the points), and one ``training_step`` is: encode with saves, the full pass, the
+PointNet++ backward on its ``d_pc``, AdamW over all 266 tensors, the device re-fold of eval BatchNorm -- so the encoder's pack is never stale.
 """
 import ctypes as C
 import torch
@@ -27,6 +33,7 @@ from .diffusion import create_gaussian_diffusion
 from .eval import as_clip_batch
 from .losses import LOSS_KEYS, LossWeights
 from .mdm import MDM, positional_table
+from .pointnet2_train import POINTNET_PARAM_NAMES, PointNetFineTuner, param_table as pointnet_param_table
 
 MAX_T, MAX_MEM = 128, 16
 QAN_LAYERS = (1, 2, 3, 4, 5, 6)
@@ -86,24 +93,32 @@ class DenoiserTrainer:
     ``state_dict``: the reference ``MDM``'s (tensors or arrays).  ``dropout`` / ``cond_mask_prob``: the configuration the checkpoint was made
     for; anything but 0 raises (not built).  ``weights`` / ``past_len``: the loss of ``forward_backward``; ``n_steps``: the cosine schedule's length.
     ``train_encoder``: the 84 encoder tensors are trained too (module docstring); a batch then carries ``pc`` or ``obj_points``, never ``cond``.
+    ``train_pointnet`` (needs ``train_encoder``): the 38 ``pcEmbedding.*`` tensors are trained too, running statistics frozen; a batch carries ``obj_points``.
     """
 
     def __init__(self, state_dict, device='cuda', lr=3e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, weights=LossWeights(), past_len=10, n_steps=1000,
-                 dropout=0.0, cond_mask_prob=0.0, train_encoder=False):
+                 dropout=0.0, cond_mask_prob=0.0, train_encoder=False, train_pointnet=False):
         if dropout > 0 or cond_mask_prob > 0:
             raise ValueError('DenoiserTrainer implements the reference defaults --dropout 0 --cond_mask_prob 0 only')
+        if train_pointnet and not train_encoder:
+            raise ValueError('train_pointnet=True needs train_encoder=True: the gradient reaches pcEmbedding through the encoder')
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
         self.weights, self.past_len, self.n_steps = weights, int(past_len), int(n_steps)
         self.diffusion = create_gaussian_diffusion('cosine', self.n_steps)
         sd = {k: torch.as_tensor(v).detach().clone() for k, v in state_dict.items()}
-        self.train_encoder = bool(train_encoder)
+        self.train_encoder, self.train_pointnet = bool(train_encoder), bool(train_pointnet)
         self.names = FULL_PARAM_NAMES if self.train_encoder else PARAM_NAMES
+        if self.train_pointnet:
+            self.names = self.names + POINTNET_PARAM_NAMES
         missing = [k for k in self.names if k not in sd]
         if missing:
             raise KeyError('state_dict lacks %s' % missing[:3])
         self.offsets, self.sizes, self.n_param = param_table(self.train_encoder)
+        if self.train_pointnet:                                      # the 38 follow the 228
+            off, size, n = pointnet_param_table()
+            self.offsets, self.sizes, self.n_param, self._n_mdm = self.offsets + [self.n_param + o for o in off], self.sizes + size, self.n_param + n, self.n_param
         self.shapes = [tuple(sd[k].shape) for k in self.names]
         for k, s, shp in zip(self.names, self.sizes, self.shapes):
             if sd[k].numel() != s:
@@ -119,6 +134,7 @@ class DenoiserTrainer:
         self._wdev = torch.tensor(weights.vector(), dtype=torch.float32, device=self.device)
         self._ws, self._mdm, self._pn = {}, None, None
         self.cond = None                                             # encoder mode: the conditioning the last gradient call computed
+        self.pointnet = PointNetFineTuner(sd, self.device, params=self.params[self._n_mdm:], grad=self.grads[self._n_mdm:]) if self.train_pointnet else None
 
     # ------------------------------------------------------------------------------------------------------------ state
     def named_views(self, flat):
@@ -165,10 +181,20 @@ class DenoiserTrainer:
                                                           self._w16, _lib.dptr(d), _lib.stream()), 'denoising_loss_grad')
         return d
 
-    def grads_at(self, x_t, t, cond=None, target=None, d_pred=None, pc=None):
+    def grads_at(self, x_t, t, cond=None, target=None, d_pred=None, pc=None, obj_points=None):
         """One forward with saves and the backward on given x_t: (pred, terms [16,B], d_cond); the flat gradient lands in ``self.grads``.
         With ``train_encoder`` it is ``grads_at(x_t, t, pc, target, d_pred=None)``: the third argument (or ``pc=``) is ``pc`` [B,256] and the result is
-        (pred, terms, d_cond, d_pc [B,256]); ``self.cond`` [past_len,B,256] keeps the encoder's output."""
+        (pred, terms, d_cond, d_pc [B,256]); ``self.cond`` [past_len,B,256] keeps the encoder's output.  With ``train_pointnet`` it is
+        ``grads_at(x_t, t, target=target, obj_points=obj_points)``: ``pc`` is encoded from the raw points with saves, and the PointNet++ backward fills the
+        last 113,917 entries of ``self.grads`` from ``d_pc``; the result is the same 4-tuple."""
+        if self.train_pointnet:
+            if target is None or obj_points is None or cond is not None or pc is not None:
+                raise ValueError('train_pointnet=True: grads_at(x_t, t, target=target, obj_points=obj_points [B,P,3])')
+            out = self._full_grads_at(x_t, t, self.pointnet.encode_saved(obj_points), target, d_pred)
+            self.pointnet.grads(out[3], flat=True)
+            return out
+        if obj_points is not None:
+            raise ValueError('obj_points= is the train_pointnet form of grads_at')
         if target is None or (cond is None) == (pc is None) or (pc is not None and not self.train_encoder):
             raise ValueError('grads_at(x_t, t, cond, target) or, with train_encoder, grads_at(x_t, t, pc, target)')
         if self.train_encoder:
@@ -217,19 +243,30 @@ class DenoiserTrainer:
 
     def encode_points(self, obj_points):
         """``pc_embedding`` [B,256] of raw ``obj_points`` [B,P,3]: ``interdiff_pointnet2_encode`` on a pack made once from the constructor's
-        ``pcEmbedding.*`` (frozen, so the pack is never stale)."""
+        ``pcEmbedding.*`` (frozen, so the pack is never stale).  With ``train_pointnet``: on the trained tensors' pack, which every optimiser step re-folds."""
         from .mdm import pack_pointnet2
+        if self.train_pointnet:
+            return self._encode(self.pointnet.pn, obj_points)
         if self._pn is None:
             if 'pcEmbedding.Linear.weight' not in self._passthrough:
                 raise KeyError('state_dict lacks pcEmbedding.*: pass pc [B,256] instead of obj_points')
             self._pn = pack_pointnet2(self._passthrough, self.device)
+        return self._encode(self._pn[0], obj_points)
+
+    def _encode(self, pn, obj_points):
         pts = obj_points.to(self.device).contiguous().float()
         pc = torch.empty(pts.shape[0], 256, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.interdiff_pointnet2_encode(C.byref(self._pn[0]), _lib.dptr(pts), pts.shape[0], pts.shape[1], _lib.dptr(pc), _lib.stream()), 'pointnet2_encode')
+        _lib.check(self.lib.interdiff_pointnet2_encode(C.byref(pn), _lib.dptr(pts), pts.shape[0], pts.shape[1], _lib.dptr(pc), _lib.stream()), 'pointnet2_encode')
         return pc
 
     def _full_batch(self, batch):
-        """Encoder mode: (gt [B,1,144,T], pc [B,256]) of a clip batch that carries ``pc`` or raw ``obj_points``."""
+        """Encoder mode: (gt [B,1,144,T], pc [B,256]) of a clip batch that carries ``pc`` or raw ``obj_points``; with ``train_pointnet`` (gt, obj_points)."""
+        if self.train_pointnet:
+            if isinstance(batch, dict) and ('cond' in batch or 'pc' in batch):
+                raise ValueError('train_pointnet=True: a batch that carries cond or pc cannot reach the points; pass raw obj_points [B,P,3]')
+            if not isinstance(batch, dict) or 'gt' not in batch or 'obj_points' not in batch:
+                raise ValueError('train_pointnet=True takes a clip batch with gt [B,1,144,T] and obj_points [B,P,3]')
+            return batch['gt'], batch['obj_points']
         if isinstance(batch, dict) and 'cond' in batch:
             raise ValueError('train_encoder=True: a batch that carries cond cannot reach the encoder; pass pc [B,256] or obj_points [B,P,3]')
         if not isinstance(batch, dict) or 'gt' not in batch or not ('pc' in batch or 'obj_points' in batch):
@@ -262,15 +299,20 @@ class DenoiserTrainer:
             t, _ = self.diffusion.sample_timesteps(B, gt.device, generator)
         t = t.to(gt.device)
         x_t = self.diffusion.q_sample(gt, t, noise=noise, seed=seed)
-        self.pred, terms, *seams = self.grads_at(x_t, t, third, gt, d_pred)
+        if self.train_pointnet:
+            self.pred, terms, *seams = self.grads_at(x_t, t, target=gt, d_pred=d_pred, obj_points=third)
+        else:
+            self.pred, terms, *seams = self.grads_at(x_t, t, third, gt, d_pred)
         wt = terms * self._wdev[:, None]
         return (wt.sum(0), {k: terms[i] for i, k in enumerate(LOSS_KEYS)}, {k: wt[i] for i, k in enumerate(LOSS_KEYS)}, self.named_views(self.grads), *seams)
 
     def apply_gradients(self):
-        """``optimizer.step()``: AdamW on the flat vectors with the gradient of the last ``loss_and_grads``."""
+        """``optimizer.step()``: AdamW on the flat vectors with the gradient of the last ``loss_and_grads``; with ``train_pointnet`` the re-fold follows."""
         self.step += 1
         _lib.check(self.lib.interdiff_mdm_train_step(_lib.dptr(self.params), _lib.dptr(self.grads), _lib.dptr(self.exp_avg), _lib.dptr(self.exp_avg_sq), self.n_param,
                                                      self.step, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, _lib.stream()), 'mdm_train_step')
+        if self.train_pointnet:
+            self.pointnet.refold()
 
     def training_step(self, batch, t=None, noise=None, seed=None, d_pred=None, generator=None):
         """``loss_and_grads`` followed by the AdamW entry; returns what ``loss_and_grads`` returns."""

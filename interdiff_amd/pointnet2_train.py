@@ -1,0 +1,134 @@
+"""Fine-tuning of the SMPL denoiser's PointNet++ object encoder on the HIP path: the backward of ``PointNet2Encoder.forward`` (model/layers.py:141-175) as
+``MDM._get_embeddings`` calls it (model/diffusion_smpl.py:210-211), with ``pcEmbedding`` in ``eval()`` and autograd on -- frozen running statistics, the
+regime of ``SkeletonFineTuner`` and ``CorrectionFineTuner``.
+
+    ft = PointNetFineTuner(state_dict)
+    pc = ft.encode_saved(obj_points)          # [B,256], the bits of interdiff_pointnet2_encode; keeps the sampling / grouping decisions
+    g = ft.grads(d_pc)                        # {reference name: gradient of sum(d_pc * pc)} for the 38 raw tensors (views of ft.grad)
+    ...update ft.params...; ft.refold()       # the folded arena the encoder reads, rewritten on the device
+
+The 38 tensors (``POINTNET_PARAM_NAMES``, 113,917 parameters): twelve bias-free 1x1 convolutions, their BatchNorm ``weight`` / ``bias``, and the Linear.
+``running_mean`` / ``running_var`` are read and never written; ``num_batches_tracked`` is carried through.  NOT built: the ``train()`` regime (batch statistics
+over all 1024 SA1 centres, running-statistic updates), a gradient with respect to ``obj_points``, caching FPS results across steps, parity with the real
+``pointnet2_ops`` (oracle/pointnet2.py).  All arithmetic is in libinterdiff_hip.so (csrc/pointnet2.hip, csrc/pointnet2_train.hip); torch holds the memory.
+"""
+import ctypes as C
+import torch
+from . import _lib
+from .mdm import pack_pointnet2
+
+PREFIX = 'pcEmbedding'
+
+
+def _layers(prefix=PREFIX):
+    return ['%s.SA_modules.%d.mlps.%d' % (prefix, si, sc) for si in range(2) for sc in range(2)]
+
+
+def pointnet_param_names(prefix=PREFIX):
+    """The 38 trained names in the order of the flat vectors (include/interdiff_hip.h, interdiff_pointnet2_finetune_param_table)."""
+    names = []
+    for q in _layers(prefix):
+        for l in range(3):
+            names += ['%s.%d.weight' % (q, 3 * l), '%s.%d.weight' % (q, 3 * l + 1), '%s.%d.bias' % (q, 3 * l + 1)]
+    return names + [prefix + '.Linear.weight', prefix + '.Linear.bias']
+
+
+def pointnet_stat_names(prefix=PREFIX):
+    """running_mean / running_var of the twelve BatchNorm sites in the order of the ``stats`` vector."""
+    return [n for q in _layers(prefix) for l in range(3) for n in ('%s.%d.running_mean' % (q, 3 * l + 1), '%s.%d.running_var' % (q, 3 * l + 1))]
+
+
+POINTNET_PARAM_NAMES = tuple(pointnet_param_names())
+POINTNET_STAT_NAMES = tuple(pointnet_stat_names())
+
+
+def param_table():
+    """(offsets, sizes, n_param) of the 38 tensors as the library lays them out."""
+    n = len(POINTNET_PARAM_NAMES)
+    off, size, cnt, total = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_int32(0), C.c_int64(0)
+    _lib.check(_lib.load().interdiff_pointnet2_finetune_param_table(off, size, C.byref(cnt), C.byref(total)), 'pointnet2_finetune_param_table')
+    if cnt.value != n:
+        raise RuntimeError('parameter table: %d tensors, expected %d' % (cnt.value, n))
+    return list(off), list(size), int(total.value)
+
+
+class PointNetFineTuner:
+    """``state_dict``: any dict that holds the reference's ``pcEmbedding.*``.  ``params`` / ``grad``: views of a larger flat master / gradient vector to work on
+    (``DenoiserTrainer`` passes the tail of its own); by default the tuner owns both."""
+
+    def __init__(self, state_dict, device='cuda', params=None, grad=None):
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.names = POINTNET_PARAM_NAMES
+        missing = [k for k in self.names + POINTNET_STAT_NAMES if k not in state_dict]
+        if missing:
+            raise KeyError('state_dict lacks %s' % missing[:3])
+        sd = {k: torch.as_tensor(v).detach() for k, v in state_dict.items() if k.startswith(PREFIX + '.')}
+        self.offsets, self.sizes, self.n_param = param_table()
+        self.shapes = [tuple(sd[k].shape) for k in self.names]
+        for k, s in zip(self.names, self.sizes):
+            if sd[k].numel() != s:
+                raise ValueError('%s: %s does not match the parameter table (%d floats)' % (k, tuple(sd[k].shape), s))
+        flat = torch.cat([sd[k].reshape(-1).float() for k in self.names]).to(self.device)
+        if params is None:
+            self.params = flat.contiguous()
+        else:
+            self.params = params
+            self.params.copy_(flat)
+        self.grad = torch.zeros_like(self.params) if grad is None else grad
+        if self.params.numel() != self.n_param or self.grad.numel() != self.n_param or not (self.params.is_contiguous() and self.grad.is_contiguous()):
+            raise ValueError('params / grad must be contiguous vectors of %d floats' % self.n_param)
+        self.stats = torch.cat([sd[k].reshape(-1).float() for k in POINTNET_STAT_NAMES]).to(self.device).contiguous()
+        self._passthrough = {k: v.clone() for k, v in sd.items() if k not in self.names}       # running statistics, num_batches_tracked: their own bits
+        self.pn, self.arena = pack_pointnet2(sd, self.device)
+        self._saves = self._points = None
+        self._ws = {}
+
+    def named_views(self, flat):
+        return {k: flat[o:o + s].view(shp) for k, o, s, shp in zip(self.names, self.offsets, self.sizes, self.shapes)}
+
+    def state_dict(self):
+        """``pcEmbedding.*`` under the reference's names: the 38 trained tensors (copies) and every other entry as it came in."""
+        out = dict(self._passthrough)
+        out.update({k: v.clone() for k, v in self.named_views(self.params).items()})
+        return out
+
+    def encode_saved(self, obj_points):
+        """``pc_embedding`` [B,256] of ``obj_points`` [B,P,3] (P <= 2048) with the record the backward reads (``interdiff_pointnet2_encode_saved``)."""
+        pts = obj_points.to(self.device).contiguous().float()
+        if pts.dim() != 3 or pts.shape[2] != 3:
+            raise ValueError('obj_points must be [B,P,3]')
+        B = pts.shape[0]
+        need = self.lib.interdiff_pointnet2_saves_bytes(B)
+        if self._saves is None or self._saves.numel() != need:
+            self._saves = torch.empty(need, dtype=torch.uint8, device=self.device)
+        pc = torch.empty(B, 256, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.interdiff_pointnet2_encode_saved(C.byref(self.pn), _lib.dptr(pts), B, pts.shape[1], _lib.dptr(pc), _lib.dptr(self._saves), need, _lib.stream()),
+                   'pointnet2_encode_saved')
+        self._points = pts
+        return pc
+
+    def saves(self):
+        """The last record as int32 [B,7156] (layout: csrc/pointnet2_train.h); its last 48 x 96 words are floats."""
+        return self._saves.view(torch.int32).view(self._points.shape[0], -1)
+
+    def grads(self, d_pc, flat=False):
+        """Gradient of ``sum(d_pc * pc)`` of the last ``encode_saved`` with respect to the 38 raw tensors: a dict by reference name (views of ``self.grad``, valid
+        until the next call), or the flat vector itself."""
+        if self._points is None:
+            raise RuntimeError('grads() follows encode_saved()')
+        B = self._points.shape[0]
+        d_pc = d_pc.to(self.device).contiguous().float()
+        if tuple(d_pc.shape) != (B, 256):
+            raise ValueError('d_pc must be [B,256] of the last encode_saved')
+        ws = self._ws.get(B)
+        if ws is None:
+            ws = self._ws[B] = torch.empty(self.lib.interdiff_pointnet2_finetune_workspace_bytes(B), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.interdiff_pointnet2_finetune_grads(C.byref(self.pn), _lib.dptr(self.params), _lib.dptr(self.stats), _lib.dptr(self._points), B, self._points.shape[1],
+                                                               _lib.dptr(self._saves), _lib.dptr(d_pc), _lib.dptr(self.grad), _lib.dptr(ws), ws.numel(), _lib.stream()),
+                   'pointnet2_finetune_grads')
+        return self.grad if flat else self.named_views(self.grad)
+
+    def refold(self):
+        """Rewrite the folded arena ``encode_saved`` reads from the current ``params`` (``interdiff_pointnet2_refold``: on the stream, no host round trip)."""
+        _lib.check(self.lib.interdiff_pointnet2_refold(C.byref(self.pn), _lib.dptr(self.params), _lib.dptr(self.stats), _lib.stream()), 'pointnet2_refold')
