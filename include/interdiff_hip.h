@@ -836,6 +836,9 @@ int interdiff_sample_losses(const float *samples, const float *gt, const float *
  *                              linear2.{weight,bias}, norm1.{weight,bias}, norm2.{weight,bias}, norm3.{weight,bias},
  *     bodyFinalLinear.{weight,bias}, objFinalLinear.{weight,bias}.
  * bodyEmbedding / objEmbedding are shared with the encoder; their gradient here is the decoder path's alone (cond is an input of this pass).
+ * This table, the FULL, SKELETON and PointNet++ tables below are each built once on the host (csrc/mdm_train.hip make_layout / make_enc_layout,
+ * csrc/pointnet2_train.hip) and read once in Python, by interdiff_amd/flat_trainer.py param_table(entry, n), against the names in
+ * interdiff_amd/mdm_train.py (PARAM_NAMES, ENCODER_PARAM_NAMES), skeleton_mdm_train.py (PARAM_NAMES) and pointnet2_train.py (POINTNET_PARAM_NAMES).
  *
  *  interdiff_denoising_loss_grad     replaces autograd through the 16 terms of forward_backward (:72-134): d_pred [B,1,144,T] = d/d pred of
  *      mean_b sum_i weights16[i] * term_i[b], the terms of interdiff_denoising_losses (velocity terms as the reference writes them: the

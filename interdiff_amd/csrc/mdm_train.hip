@@ -82,10 +82,9 @@ int loss_grad(hipStream_t st, const float *pred, const float *target, int B, int
     return IDF_OK;
 }
 
-// ---- the sublayers both stacks are made of; Off = LayerOff | EncLayerOff, T = tokens per clip ---------------------------------------------------------------
+// ---- the sublayers both stacks are made of; T = tokens per clip ---------------------------------------------------------------------------------------------
 // s = x + self_attn(x) (layers 0, 7) | x + QaN block(x) (layers 1..6)
-template <class Off>
-int mix_fwd(hipStream_t st, const float *th, const Off &o, bool qan, const float *xin, float *qkv, float *ao, float *lse, float *G, float *s, int B, int T) {
+int mix_fwd(hipStream_t st, const float *th, const LayerOff &o, bool qan, const float *xin, float *qkv, float *ao, float *lse, float *G, float *s, int B, int T) {
     const int M = B * T;
     if (qan) {
         hipLaunchKernelGGL(mt_qan_prep_kernel, dim3(NQ), dim3(256), 0, st, th + o.queries, G);
@@ -100,8 +99,7 @@ int mix_fwd(hipStream_t st, const float *th, const Off &o, bool qan, const float
     return lin_fwd(st, ao, D, th + o.sa_out_w, th + o.sa_out_b, s, D, xin, D, M, D, D);
 }
 // s = x + linear2(gelu(linear1(x))); leaves the pre-activation z
-template <class Off>
-int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const Off &o, const float *x, float *z, float *s, int M) {
+int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const LayerOff &o, const float *x, float *z, float *s, int M) {
     const int FF = w.geo.ff;
     MT_TRY(lin_fwd(st, x, D, th + o.l1_w, th + o.l1_b, z, FF, nullptr, 0, M, FF, D));
     hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
@@ -109,8 +107,7 @@ int ffn_fwd(hipStream_t st, const Ws &w, const float *th, const Off &o, const fl
     return lin_fwd(st, w.g, FF, th + o.l2_w, th + o.l2_b, s, D, x, D, M, D, FF);
 }
 // E = d s (the feed-forward output and, through the residual, d x)  ->  F = d x, and the four parameter gradients
-template <class Off>
-int ffn_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &o, const float *E, const float *x, const float *z, float *F, int M) {
+int ffn_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const LayerOff &o, const float *E, const float *x, const float *z, float *F, int M) {
     const int FF = w.geo.ff;
     hipLaunchKernelGGL(mt_gelu_kernel, dim3(blocks256((int64_t)M * FF)), dim3(256), 0, st, z, w.g, (int64_t)M * FF);
     IDF_CHECK_LAUNCH();
@@ -122,8 +119,7 @@ int ffn_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &
     return lin_dx(st, w.dz, FF, th + o.l1_w, F, D, E, D, M, FF, D);
 }
 // E = d s of mix_fwd  ->  Dh = d x (the residual included), and the parameter gradients; F is scratch
-template <class Off>
-int mix_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &o, bool qan, const float *E, const float *xin, const float *qkv, const float *ao,
+int mix_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const LayerOff &o, bool qan, const float *E, const float *xin, const float *qkv, const float *ao,
             const float *lse, const float *G, float *F, float *Dh, int B, int T) {
     const int M = B * T;
     if (qan) {
@@ -151,73 +147,77 @@ int mix_bwd(hipStream_t st, const Ws &w, const float *th, float *gr, const Off &
 
 namespace mdmtrain {
 
-// the flat master vector: the tensors in the order of interdiff_amd/mdm_train.py PARAM_NAMES, packed without padding
+// ---- the flat vectors: tensors packed without padding, in the order of interdiff_amd/mdm_train.py PARAM_NAMES and, behind them, ENCODER_PARAM_NAMES -----------------
+struct Packer {
+    int64_t at, *off, *size;
+    int n;
+    void operator()(int64_t &slot, int64_t sz) { slot = at; off[n] = at; size[n] = sz; ++n; at += sz; }
+};
+// one layer's tensors; cross: a decoder layer (cross-attention, three LayerNorms) -- else an encoder layer (two LayerNorms)
+static void layer_layout(Packer &take, LayerOff &y, int l, int64_t FF, bool cross) {
+    y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = y.queries = y.wk = y.ca_in_w = y.ca_in_b = y.ca_out_w = y.ca_out_b = y.ln_w[2] = y.ln_b[2] = -1;
+    if (is_qan(l)) {
+        take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
+    } else {
+        take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
+    }
+    if (cross) { take(y.ca_in_w, (int64_t)3 * D * D); take(y.ca_in_b, 3 * D); take(y.ca_out_w, (int64_t)D * D); take(y.ca_out_b, D); }
+    take(y.l1_w, FF * D); take(y.l1_b, FF); take(y.l2_w, D * FF); take(y.l2_b, D);
+    for (int i = 0; i < (cross ? 3 : 2); ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
+}
+
 Layout make_layout(const Geom &g) {
     Layout o{};
-    int64_t at = 0;
-    int n = 0;
-    auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
-    const int FF = g.ff;
+    Packer take{0, o.off, o.size, 0};
     take(o.body_w, (int64_t)D * g.nbody); take(o.body_b, D); take(o.obj_w, (int64_t)D * g.nobj); take(o.obj_b, D);
     take(o.t0_w, (int64_t)D * D); take(o.t0_b, D); take(o.t2_w, (int64_t)D * D); take(o.t2_b, D);
-    for (int l = 0; l < N_LAYERS; ++l) {
-        LayerOff &y = o.layer[l];
-        if (is_qan(l)) {
-            take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
-            y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
-        } else {
-            take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
-            y.queries = y.wk = -1;
-        }
-        take(y.ca_in_w, (int64_t)3 * D * D); take(y.ca_in_b, 3 * D); take(y.ca_out_w, (int64_t)D * D); take(y.ca_out_b, D);
-        take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
-        for (int i = 0; i < 3; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
-    }
+    for (int l = 0; l < N_LAYERS; ++l) layer_layout(take, o.layer[l], l, g.ff, true);
     take(o.bodyf_w, (int64_t)g.hbody * D); take(o.bodyf_b, g.hbody); take(o.objf_w, (int64_t)g.hobj * D); take(o.objf_b, g.hobj);
-    o.total = at;
+    o.total = take.at;
     return o;
 }
 
-// the encoder's 84 tensors behind the 144: interdiff_amd/mdm_train.py ENCODER_PARAM_NAMES
 EncLayout make_enc_layout(const Geom &g, const Layout &L) {
     EncLayout o{};
-    int64_t at = L.total;
-    int n = 0;
-    auto take = [&](int64_t &slot, int64_t sz) { slot = at; o.off[n] = at; o.size[n] = sz; ++n; at += sz; };
-    const int FF = g.ff;
-    for (int l = 0; l < N_LAYERS; ++l) {
-        EncLayerOff &y = o.layer[l];
-        if (is_qan(l)) {
-            take(y.queries, (int64_t)NQ * D); take(y.wk, NQ);
-            y.sa_in_w = y.sa_in_b = y.sa_out_w = y.sa_out_b = -1;
-        } else {
-            take(y.sa_in_w, (int64_t)3 * D * D); take(y.sa_in_b, 3 * D); take(y.sa_out_w, (int64_t)D * D); take(y.sa_out_b, D);
-            y.queries = y.wk = -1;
-        }
-        take(y.l1_w, (int64_t)FF * D); take(y.l1_b, FF); take(y.l2_w, (int64_t)D * FF); take(y.l2_b, D);
-        for (int i = 0; i < 2; ++i) { take(y.ln_w[i], D); take(y.ln_b[i], D); }
-    }
-    o.total = at;
+    Packer take{L.total, o.off, o.size, 0};
+    for (int l = 0; l < N_LAYERS; ++l) layer_layout(take, o.layer[l], l, g.ff, false);
+    o.total = take.at;
     return o;
+}
+
+int table_out(std::initializer_list<TableRun> parts, int64_t total, int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
+    int n = 0;
+    for (const TableRun &p : parts)
+        for (int i = 0; i < p.n; ++i, ++n) {
+            if (offsets) offsets[n] = p.off[i];
+            if (sizes) sizes[n] = p.size[i];
+        }
+    if (n_tensors) *n_tensors = n;
+    if (n_param) *n_param = total;
+    return IDF_OK;
 }
 
 // ---- workspace plan (floats) ---------------------------------------------------------------------------------------------------------------------------
+// one layer's saves on M rows of T-token clips; S: the memory's length for a decoder layer, 0 for an encoder layer (no cross-attention, two LayerNorms)
+static void layer_plan(Carver &take, LayerWs &y, int l, size_t B, size_t T, size_t FF, size_t S) {
+    const size_t M = B * T;
+    if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
+    else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take(B * HEADS * T); }
+    for (int i = 0; i < (S ? 3 : 2); ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
+    y.x1 = take(M * D);
+    if (S) { y.x2 = take(M * D); y.q2 = take(M * D); y.kv = take(S * B * 2 * D); y.o2 = take(M * D); }
+    y.z = take(M * FF);
+}
+
 Ws plan(float *base, const Geom &g, int B, int T, int S) {
     Ws w{};
     w.geo = g;
-    size_t at = 0;
     const size_t M = (size_t)B * T, FF = (size_t)g.ff, CTOK = (size_t)g.ctok;
-    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    Carver take{base, 0};
     w.X = take(M * CTOK); w.Y = take(M * CTOK); w.dY = take(M * CTOK);
     w.tin = take((size_t)B * D); w.z0 = take((size_t)B * D); w.sz = take((size_t)B * D); w.temb = take((size_t)B * D);
     for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
-    for (int l = 0; l < N_LAYERS; ++l) {
-        LayerWs &y = w.layer[l];
-        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
-        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * T); }
-        for (int i = 0; i < 3; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
-        y.x1 = take(M * D); y.x2 = take(M * D); y.q2 = take(M * D); y.kv = take((size_t)S * B * 2 * D); y.o2 = take(M * D); y.z = take(M * FF);
-    }
+    for (int l = 0; l < N_LAYERS; ++l) layer_plan(take, w.layer[l], l, B, T, FF, S);
     w.g = take(M * FF); w.dz = take(M * FF);
     for (int i = 0; i < 4; ++i) w.t[i] = take(M * D);
     w.dqkv = take(M * 3 * D);
@@ -227,7 +227,7 @@ Ws plan(float *base, const Geom &g, int B, int T, int S) {
     w.dG = take((size_t)SLOTS * NQ * D); w.dsim = take(M * NQ * SLOTS); w.cj = take(M * SLOTS); w.dwk_tok = take(M * NQ);
     w.partial = take(((M + 63) / 64 + 1) * (FF > (size_t)3 * D ? FF : (size_t)3 * D));      // the widest column sum: a feed-forward bias or the q|k|v bias
     w.dtemb = take((size_t)B * D); w.dsz = take((size_t)B * D);
-    w.floats = at;
+    w.floats = take.at;
     return w;
 }
 
@@ -235,20 +235,24 @@ Ws plan(float *base, const Geom &g, int B, int T, int S) {
 // decoder's: the encoder's forward ends before the decoder's begins and its backward begins after the decoder's has ended, and S * B < T * B rows.
 EncWs enc_plan(float *base, size_t at, const Geom &g, const Layout &L, int B, int S) {
     EncWs w{};
-    const size_t M = (size_t)B * S, FF = (size_t)g.ff;
-    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    const size_t M = (size_t)B * S;
+    Carver take{base, at};
     w.Xp = take(M * g.ctok);
     for (int l = 0; l <= N_LAYERS; ++l) w.h[l] = take(M * D);
     w.genc = take((size_t)n_shared(L));
-    for (int l = 0; l < N_LAYERS; ++l) {
-        EncLayerWs &y = w.layer[l];
-        if (is_qan(l)) y.G = take((size_t)NQ * SLOTS * D);
-        else { y.qkv = take(M * 3 * D); y.ao = take(M * D); y.lse = take((size_t)B * HEADS * S); }
-        for (int i = 0; i < 2; ++i) { y.xh[i] = take(M * D); y.rs[i] = take(M); }
-        y.x1 = take(M * D); y.z = take(M * FF);
-    }
-    w.floats = at;
+    for (int l = 0; l < N_LAYERS; ++l) layer_plan(take, w.layer[l], l, B, S, (size_t)g.ff, 0);
+    w.floats = take.at;
     return w;
+}
+
+FullWs full_plan(float *base, const Geom &g, const Layout &L, int B, int T, int past_len) {
+    const Ws w = plan(base, g, B, T, past_len);
+    return {w, enc_plan(base, w.floats, g, L, B, past_len)};
+}
+
+int ws_check(const void *ws, size_t ws_bytes, size_t need) {
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
+    return ws_bytes < need ? IDF_E_NOMEM : IDF_OK;
 }
 
 bool shape_ok(const Geom &g, int B, int T, int S, int past_len) {
@@ -371,8 +375,8 @@ int enc_forward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws &
     hipLaunchKernelGGL(mt_add_temb_pe_kernel, dim3((unsigned)M), dim3(256), 0, st, e.h[0], pc, pe, S);
     IDF_CHECK_LAUNCH();
     for (int l = 0; l < N_LAYERS; ++l) {
-        const EncLayerOff &o = EL.layer[l];
-        const EncLayerWs &y = e.layer[l];
+        const LayerOff &o = EL.layer[l];
+        const LayerWs &y = e.layer[l];
         const float *xin = e.h[l];
         float *s = w.t[0];
         MT_TRY(mix_fwd(st, th, o, is_qan(l), xin, y.qkv, y.ao, y.lse, y.G, s, B, S));
@@ -401,8 +405,8 @@ int enc_backward(hipStream_t st, const Layout &L, const EncLayout &EL, const Ws 
     hipLaunchKernelGGL(mt_swap_rows_kernel, dim3((unsigned)M), dim3(256), 0, st, d_cond, Dh, S, B);
     IDF_CHECK_LAUNCH();
     for (int l = N_LAYERS - 1; l >= 0; --l) {
-        const EncLayerOff &o = EL.layer[l];
-        const EncLayerWs &y = e.layer[l];
+        const LayerOff &o = EL.layer[l];
+        const LayerWs &y = e.layer[l];
         MT_TRY(ln_bwd(st, Dh, y.xh[1], y.rs[1], th + o.ln_w[1], gr + o.ln_w[1], gr + o.ln_b[1], E, w.partial, M));              // E = d s2 = d x1 (residual)
         MT_TRY(ffn_bwd(st, w, th, gr, o, E, y.x1, y.z, F, M));                                                                  // F = d x1
         MT_TRY(ln_bwd(st, F, y.xh[0], y.rs[0], th + o.ln_w[0], gr + o.ln_w[0], gr + o.ln_b[0], E, w.partial, M));              // E = d s1
@@ -457,13 +461,7 @@ extern "C" int interdiff_denoising_loss_grad(const float *pred, const float *tar
 
 extern "C" int interdiff_mdm_train_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
     const Layout &L = layout();
-    for (int i = 0; i < N_TENSORS; ++i) {
-        if (offsets) offsets[i] = L.off[i];
-        if (sizes) sizes[i] = L.size[i];
-    }
-    if (n_tensors) *n_tensors = N_TENSORS;
-    if (n_param) *n_param = L.total;
-    return IDF_OK;
+    return table_out({{L.off, L.size, N_TENSORS}}, L.total, offsets, sizes, n_tensors, n_param);
 }
 
 extern "C" size_t interdiff_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t mem_len) {
@@ -476,8 +474,7 @@ extern "C" int interdiff_mdm_train_grads(const float *params, const float *pe, i
                                          float *d_cond, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
     if (!params || !pe || !x_t || !ts || !cond || !target || !weights16 || !grads || !d_cond || !pred || !terms || !ws) return IDF_E_INVAL;
     if (!shape_ok(GEO, B, T, mem_len, past_len) || pe_rows < T) return IDF_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
-    if (ws_bytes < interdiff_mdm_train_workspace_bytes(B, T, mem_len)) return IDF_E_NOMEM;
+    MT_TRY(ws_check(ws, ws_bytes, interdiff_mdm_train_workspace_bytes(B, T, mem_len)));
     hipStream_t st = idf_stream(stream);
     const Layout &L = layout();
     const Ws w = plan(static_cast<float *>(ws), GEO, B, T, mem_len);
@@ -490,18 +487,12 @@ extern "C" int interdiff_mdm_train_grads(const float *params, const float *pe, i
 extern "C" int interdiff_mdm_train_full_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param) {
     const Layout &L = layout();
     const EncLayout &EL = enc_layout();
-    for (int i = 0; i < N_FULL_TENSORS; ++i) {
-        if (offsets) offsets[i] = i < N_TENSORS ? L.off[i] : EL.off[i - N_TENSORS];
-        if (sizes) sizes[i] = i < N_TENSORS ? L.size[i] : EL.size[i - N_TENSORS];
-    }
-    if (n_tensors) *n_tensors = N_FULL_TENSORS;
-    if (n_param) *n_param = EL.total;
-    return IDF_OK;
+    return table_out({{L.off, L.size, N_TENSORS}, {EL.off, EL.size, N_ENC_TENSORS}}, EL.total, offsets, sizes, n_tensors, n_param);
 }
 
 extern "C" size_t interdiff_mdm_train_full_workspace_bytes(int32_t B, int32_t T, int32_t past_len) {
     if (!shape_ok(GEO, B, T, past_len, past_len)) return 0;
-    return enc_plan(nullptr, plan(nullptr, GEO, B, T, past_len).floats, GEO, layout(), B, past_len).floats * sizeof(float);
+    return full_plan(nullptr, GEO, layout(), B, T, past_len).e.floats * sizeof(float);
 }
 
 extern "C" int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *pc,
@@ -509,13 +500,11 @@ extern "C" int interdiff_mdm_train_full_grads(const float *params, const float *
                                               float *cond, float *d_cond, float *d_pc, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
     if (!params || !pe || !x_t || !ts || !pc || !target || !weights16 || !grads || !cond || !d_cond || !d_pc || !pred || !terms || !ws) return IDF_E_INVAL;
     if (!shape_ok(GEO, B, T, past_len, past_len) || pe_rows < T) return IDF_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
-    if (ws_bytes < interdiff_mdm_train_full_workspace_bytes(B, T, past_len)) return IDF_E_NOMEM;
+    MT_TRY(ws_check(ws, ws_bytes, interdiff_mdm_train_full_workspace_bytes(B, T, past_len)));
     hipStream_t st = idf_stream(stream);
     const Layout &L = layout();
     const EncLayout &EL = enc_layout();
-    const Ws w = plan(static_cast<float *>(ws), GEO, B, T, past_len);
-    const EncWs e = enc_plan(static_cast<float *>(ws), w.floats, GEO, L, B, past_len);
+    const auto [w, e] = full_plan(static_cast<float *>(ws), GEO, L, B, T, past_len);
     MT_TRY(enc_forward(st, L, EL, w, e, params, pe, target, pc, B, T, past_len, cond));
     MT_TRY(forward(st, L, w, params, pe, pe_rows, x_t, ts, cond, B, T, past_len));
     MT_TRY(emit_pred(st, w, B, T, pred));

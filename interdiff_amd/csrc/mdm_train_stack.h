@@ -4,6 +4,7 @@
 // Declarations only: the device code (csrc/mdm_train.h) is compiled once, in mdm_train.hip.
 #pragma once
 #include "common.h"
+#include <initializer_list>
 
 namespace mdmtrain {
 
@@ -21,6 +22,7 @@ constexpr Geom SKELETON_GEOM{256, 106, 63, 36, 63, 7};           // the 7 pose c
 
 constexpr int N_TENSORS = 144, N_ENC_TENSORS = 84, N_FULL_TENSORS = N_TENSORS + N_ENC_TENSORS;
 
+// One layer of either stack.  An encoder layer has no cross-attention (ca_* = -1) and two LayerNorms (ln_*[2] = -1); a QaN layer has queries / wk in the place of sa_*.
 struct LayerOff {
     int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, ca_in_w, ca_in_b, ca_out_w, ca_out_b, l1_w, l1_b, l2_w, l2_b, ln_w[3], ln_b[3];
 };
@@ -29,19 +31,33 @@ struct Layout {
     LayerOff layer[N_LAYERS];
     int64_t off[N_TENSORS], size[N_TENSORS];
 };
-struct EncLayerOff {
-    int64_t sa_in_w, sa_in_b, sa_out_w, sa_out_b, queries, wk, l1_w, l1_b, l2_w, l2_b, ln_w[2], ln_b[2];
-};
 struct EncLayout {
     int64_t total;                                                // of the 144 + 84 tensors
-    EncLayerOff layer[N_LAYERS];
+    LayerOff layer[N_LAYERS];
     int64_t off[N_ENC_TENSORS], size[N_ENC_TENSORS];
 };
 // the 144 tensors of a decoder-side flat vector, and the 84 encoder tensors behind them, packed without padding (orders: include/interdiff_hip.h)
 Layout make_layout(const Geom &g);
 EncLayout make_enc_layout(const Geom &g, const Layout &L);
+// A parameter table's entry: the (off, size, n) runs in `parts`, one after the other, copied out; any output may be null.
+struct TableRun {
+    const int64_t *off, *size;
+    int n;
+};
+int table_out(std::initializer_list<TableRun> parts, int64_t total, int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param);
 
 // ---- workspace plans (floats) ---------------------------------------------------------------------------------------------------------------------------
+// hands out 64-float-aligned slots behind base + at; with a null base it only counts
+struct Carver {
+    float *base;
+    size_t at;
+    float *operator()(size_t n) {
+        float *p = base ? base + at : nullptr;
+        at += (n + 63) / 64 * 64;
+        return p;
+    }
+};
+// One layer's saves in either stack.  An encoder layer leaves x2, q2, kv, o2 and xh[2] / rs[2] null.
 struct LayerWs {
     float *qkv, *ao, *lse, *xh[3], *rs[3], *x1, *x2, *q2, *kv, *o2, *z, *G;
 };
@@ -52,16 +68,21 @@ struct Ws {
     float *g, *dz, *t[4], *dqkv, *P, *dS, *Pc, *dSc, *dkv, *dG, *dsim, *cj, *dwk_tok, *partial, *dtemb, *dsz;
     size_t floats;
 };
-struct EncLayerWs {
-    float *qkv, *ao, *lse, *xh[2], *rs[2], *x1, *z, *G;
-};
 struct EncWs {
     float *Xp, *h[N_LAYERS + 1], *genc;
-    EncLayerWs layer[N_LAYERS];
+    LayerWs layer[N_LAYERS];
     size_t floats;                                                // decoder plan included
 };
 Ws plan(float *base, const Geom &g, int B, int T, int S);
 EncWs enc_plan(float *base, size_t at, const Geom &g, const Layout &L, int B, int S);
+// the decoder's plan with the encoder's behind it, S = past_len: what a whole-model gradient call works in
+struct FullWs {
+    Ws w;
+    EncWs e;
+};
+FullWs full_plan(float *base, const Geom &g, const Layout &L, int B, int T, int past_len);
+// a *_grads entry's workspace check: 256-byte alignment (IDF_E_INVAL), then room for `need` bytes (IDF_E_NOMEM)
+int ws_check(const void *ws, size_t ws_bytes, size_t need);
 bool shape_ok(const Geom &g, int B, int T, int S, int past_len);
 
 // ---- launchers: every one returns IDF_OK or IDF_E_LAUNCH ---------------------------------------------------------------------------------------------------

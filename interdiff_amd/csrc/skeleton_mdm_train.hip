@@ -13,7 +13,7 @@ using namespace mdmtrain;
 namespace {
 
 constexpr Geom GEO = SKELETON_GEOM;
-constexpr int CTOK = GEO.ctok, NBODY = GEO.hbody, NPTS = 12, NOBJ = 3 * NPTS, NPOSE = GEO.hobj, HEAD = GEO.head(), N_SKEL_TENSORS = N_FULL_TENSORS + 2, N_TERMS = 13;
+constexpr int CTOK = GEO.ctok, NBODY = GEO.hbody, NPTS = 12, NOBJ = 3 * NPTS, NPOSE = GEO.hobj, HEAD = GEO.head(), N_TERMS = 13;
 static_assert(CTOK == NBODY + NOBJ + NPOSE && GEO.nobj == NOBJ, "token = body | object keypoints | pose");
 
 // ------------------------------------------------------------------------------------------------------------------ head
@@ -168,9 +168,9 @@ struct SkelWs {
 };
 SkelWs skel_plan(float *base, size_t at, int B, int S) {
     SkelWs w{};
-    auto take = [&](size_t n) { float *p = base ? base + at : nullptr; at += (n + 63) / 64 * 64; return p; };
+    Carver take{base, at};
     w.shape = take((size_t)B * D); w.d_shape = take((size_t)B * D); w.d_cond = take((size_t)S * B * D);
-    w.floats = at;
+    w.floats = take.at;
     return w;
 }
 
@@ -185,21 +185,13 @@ extern "C" int interdiff_skeleton_denoising_loss_grad(const float *pred, const f
 extern "C" int interdiff_skeleton_mdm_train_param_table(int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param_out) {
     const Layout &L = layout();
     const EncLayout &EL = enc_layout();
-    for (int i = 0; i < N_FULL_TENSORS; ++i) {
-        if (offsets) offsets[i] = i < N_TENSORS ? L.off[i] : EL.off[i - N_TENSORS];
-        if (sizes) sizes[i] = i < N_TENSORS ? L.size[i] : EL.size[i - N_TENSORS];
-    }
-    if (offsets) { offsets[N_FULL_TENSORS] = shape_w_off(); offsets[N_FULL_TENSORS + 1] = shape_b_off(); }
-    if (sizes) { sizes[N_FULL_TENSORS] = (int64_t)D * NOBJ; sizes[N_FULL_TENSORS + 1] = D; }
-    if (n_tensors) *n_tensors = N_SKEL_TENSORS;
-    if (n_param_out) *n_param_out = n_param();
-    return IDF_OK;
+    const int64_t shape_off[2] = {shape_w_off(), shape_b_off()}, shape_size[2] = {(int64_t)D * NOBJ, D};
+    return table_out({{L.off, L.size, N_TENSORS}, {EL.off, EL.size, N_ENC_TENSORS}, {shape_off, shape_size, 2}}, n_param(), offsets, sizes, n_tensors, n_param_out);
 }
 
 extern "C" size_t interdiff_skeleton_mdm_train_workspace_bytes(int32_t B, int32_t T, int32_t past_len) {
     if (!shape_ok(GEO, B, T, past_len, past_len)) return 0;
-    const size_t enc = enc_plan(nullptr, plan(nullptr, GEO, B, T, past_len).floats, GEO, layout(), B, past_len).floats;
-    return skel_plan(nullptr, enc, B, past_len).floats * sizeof(float);
+    return skel_plan(nullptr, full_plan(nullptr, GEO, layout(), B, T, past_len).e.floats, B, past_len).floats * sizeof(float);
 }
 
 extern "C" int interdiff_skeleton_mdm_train_grads(const float *params, const float *pe, int32_t pe_rows, const float *x_t, const int64_t *ts, const float *target,
@@ -207,14 +199,12 @@ extern "C" int interdiff_skeleton_mdm_train_grads(const float *params, const flo
                                                   float *grads, float *cond, float *pred, float *terms, void *ws, size_t ws_bytes, void *stream) {
     if (!params || !pe || !x_t || !ts || !target || !zero_pose_obj || !weights13 || !grads || !cond || !pred || !terms || !ws) return IDF_E_INVAL;
     if (!shape_ok(GEO, B, T, past_len, past_len) || pe_rows < T) return IDF_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return IDF_E_INVAL;
-    if (ws_bytes < interdiff_skeleton_mdm_train_workspace_bytes(B, T, past_len)) return IDF_E_NOMEM;
+    MT_TRY(ws_check(ws, ws_bytes, interdiff_skeleton_mdm_train_workspace_bytes(B, T, past_len)));
     hipStream_t st = idf_stream(stream);
     const Layout &L = layout();
     const EncLayout &EL = enc_layout();
     float *base = static_cast<float *>(ws);
-    const Ws w = plan(base, GEO, B, T, past_len);
-    const EncWs e = enc_plan(base, w.floats, GEO, L, B, past_len);
+    const auto [w, e] = full_plan(base, GEO, L, B, T, past_len);
     const SkelWs k = skel_plan(base, e.floats, B, past_len);
     const int M = B * T;
     // _get_embeddings: the shape row takes the place pc_embedding has in the SMPL encoder

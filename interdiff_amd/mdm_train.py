@@ -12,7 +12,9 @@ objEmbedding are shared with the encoder; their gradient here is the decoder pat
 
 The reference trains with ``--dropout 0`` and ``--cond_mask_prob 0`` and runs ``stochastic_depth`` at rate 0, so ``train()`` and ``eval()`` compute
 the same function; a configuration with dropout or condition masking is refused.  All arithmetic is in libinterdiff_hip.so (csrc/mdm_train.h):
-exact fp32, no float atomics -- two calls give the same bits.  torch holds the device memory.
+exact fp32, no float atomics -- two calls give the same bits.  torch holds the device memory.  The flat vectors, the state-dict round trip, the workspace
+cache and the model-independent half of a step are ``flat_trainer.FlatAdamWTrainer``'s; this module supplies the names, the three modes' batch handling and
+gradient calls, and ``export_mdm``.
 
 ``DenoiserTrainer(state_dict, train_encoder=True)`` closes the ``d_cond`` seam: the pass then covers ``MDM._get_embeddings`` from ``pc_embedding`` on
 (model/diffusion_smpl.py:217-221: the shared input embeddings on the past frames, ``pc_embedding``, the positional rows, the eight ``encoder.layers.*``), as
@@ -28,14 +30,13 @@ PointNet++ backward on its ``d_pc``, AdamW over all 266 tensors, the device re-f
 """
 import ctypes as C
 import torch
-from . import _lib
-from .diffusion import create_gaussian_diffusion
+from . import _lib, flat_trainer
 from .eval import as_clip_batch
+from .flat_trainer import MAX_T, MAX_MEM
 from .losses import LOSS_KEYS, LossWeights
-from .mdm import MDM, positional_table
+from .mdm import MDM
 from .pointnet2_train import POINTNET_PARAM_NAMES, PointNetFineTuner, param_table as pointnet_param_table
 
-MAX_T, MAX_MEM = 128, 16
 QAN_LAYERS = (1, 2, 3, 4, 5, 6)
 
 
@@ -78,82 +79,47 @@ FULL_PARAM_NAMES = PARAM_NAMES + ENCODER_PARAM_NAMES
 def param_table(full=False):
     """(offsets, sizes, n_param) of the flat vectors as the library lays them out (``interdiff_mdm_train_param_table``; ``full``: the 228 tensors of
     ``interdiff_mdm_train_full_param_table``)."""
-    n = len(FULL_PARAM_NAMES if full else PARAM_NAMES)
-    off, size, cnt, total = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_int32(0), C.c_int64(0)
-    entry = _lib.load().interdiff_mdm_train_full_param_table if full else _lib.load().interdiff_mdm_train_param_table
-    _lib.check(entry(off, size, C.byref(cnt), C.byref(total)), 'mdm_train_param_table')
-    if cnt.value != n:
-        raise RuntimeError('parameter table: %d tensors, expected %d' % (cnt.value, n))
-    return list(off), list(size), int(total.value)
+    return flat_trainer.param_table('interdiff_mdm_train_full_param_table' if full else 'interdiff_mdm_train_param_table', len(FULL_PARAM_NAMES if full else PARAM_NAMES))
 
 
-class DenoiserTrainer:
-    """``loss.backward()`` + ``optimizer.step()`` of the reference's diffusion trainer for the decoder side of the SMPL denoiser.
+class DenoiserTrainer(flat_trainer.FlatAdamWTrainer):
+    """``loss.backward()`` + ``optimizer.step()`` of the reference's diffusion trainer for the SMPL denoiser (the scaffold: interdiff_amd/flat_trainer.py).
 
     ``state_dict``: the reference ``MDM``'s (tensors or arrays).  ``dropout`` / ``cond_mask_prob``: the configuration the checkpoint was made
     for; anything but 0 raises (not built).  ``weights`` / ``past_len``: the loss of ``forward_backward``; ``n_steps``: the cosine schedule's length.
     ``train_encoder``: the 84 encoder tensors are trained too (module docstring); a batch then carries ``pc`` or ``obj_points``, never ``cond``.
     ``train_pointnet`` (needs ``train_encoder``): the 38 ``pcEmbedding.*`` tensors are trained too, running statistics frozen; a batch carries ``obj_points``.
+    ``state_dict()`` returns the trained tensors (144, 228 or 266) and every other tensor of the constructor's state_dict exactly as it came in.
+
+    ``loss_and_grads`` returns, behind the four common elements, ``d_cond`` [mem_len,B,256] and, with ``train_encoder``, ``d_pc`` [B,256]; ``self.cond`` then
+    keeps the conditioning the step computed.
     """
+
+    LOSS_KEYS, C_TOK = LOSS_KEYS, 144
+    # per mode (train_encoder, train_pointnet): the one argument of cond / pc / obj_points that grads_at takes, its form for the refusal, and the names of the
+    # methods that turn a batch into (gt, that argument) and that compute the gradients from it
+    MODES = {
+        (False, False): (('cond',), 'grads_at(x_t, t, cond, target)', '_decoder_inputs', '_decoder_grads'),
+        (True, False): (('cond', 'pc'), 'train_encoder=True: grads_at(x_t, t, pc [B,256], target)', '_encoder_inputs', '_full_grads'),
+        (True, True): (('obj_points',), 'train_pointnet=True: grads_at(x_t, t, target=target, obj_points=obj_points [B,P,3])', '_pointnet_inputs', '_pointnet_grads'),
+    }
 
     def __init__(self, state_dict, device='cuda', lr=3e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, weights=LossWeights(), past_len=10, n_steps=1000,
                  dropout=0.0, cond_mask_prob=0.0, train_encoder=False, train_pointnet=False):
-        if dropout > 0 or cond_mask_prob > 0:
-            raise ValueError('DenoiserTrainer implements the reference defaults --dropout 0 --cond_mask_prob 0 only')
         if train_pointnet and not train_encoder:
             raise ValueError('train_pointnet=True needs train_encoder=True: the gradient reaches pcEmbedding through the encoder')
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
-        self.weights, self.past_len, self.n_steps = weights, int(past_len), int(n_steps)
-        self.diffusion = create_gaussian_diffusion('cosine', self.n_steps)
-        sd = {k: torch.as_tensor(v).detach().clone() for k, v in state_dict.items()}
         self.train_encoder, self.train_pointnet = bool(train_encoder), bool(train_pointnet)
-        self.names = FULL_PARAM_NAMES if self.train_encoder else PARAM_NAMES
-        if self.train_pointnet:
-            self.names = self.names + POINTNET_PARAM_NAMES
-        missing = [k for k in self.names if k not in sd]
-        if missing:
-            raise KeyError('state_dict lacks %s' % missing[:3])
-        self.offsets, self.sizes, self.n_param = param_table(self.train_encoder)
+        self._takes, self._form, inputs, grads = self.MODES[self.train_encoder, self.train_pointnet]
+        self._inputs, self._grads = getattr(self, inputs), getattr(self, grads)
+        names, table = (FULL_PARAM_NAMES if self.train_encoder else PARAM_NAMES), param_table(self.train_encoder)
+        n_mdm = table[2]
         if self.train_pointnet:                                      # the 38 follow the 228
-            off, size, n = pointnet_param_table()
-            self.offsets, self.sizes, self.n_param, self._n_mdm = self.offsets + [self.n_param + o for o in off], self.sizes + size, self.n_param + n, self.n_param
-        self.shapes = [tuple(sd[k].shape) for k in self.names]
-        for k, s, shp in zip(self.names, self.sizes, self.shapes):
-            if sd[k].numel() != s:
-                raise ValueError('%s: %s does not match the parameter table (%d floats)' % (k, shp, s))
-        self._passthrough = {k: v for k, v in sd.items() if k not in self.names}         # returned by state_dict() with identical bits
-        self.params = torch.cat([sd[k].reshape(-1).float() for k in self.names]).to(self.device).contiguous()
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.grads = torch.zeros_like(self.params)
-        self.step = 0
-        pe = sd['PositionalEmbedding.pe'][:, 0] if 'PositionalEmbedding.pe' in sd else positional_table()
-        self.pe = torch.as_tensor(pe).float().to(self.device).contiguous()
-        self._w16 = (C.c_float * 16)(*weights.vector())
-        self._wdev = torch.tensor(weights.vector(), dtype=torch.float32, device=self.device)
-        self._ws, self._mdm, self._pn = {}, None, None
-        self.cond = None                                             # encoder mode: the conditioning the last gradient call computed
-        self.pointnet = PointNetFineTuner(sd, self.device, params=self.params[self._n_mdm:], grad=self.grads[self._n_mdm:]) if self.train_pointnet else None
-
-    # ------------------------------------------------------------------------------------------------------------ state
-    def named_views(self, flat):
-        return {k: flat[o:o + s].view(shp) for k, o, s, shp in zip(self.names, self.offsets, self.sizes, self.shapes)}
-
-    def state_dict(self):
-        """The reference's names: the trained tensors (144, or 228 with ``train_encoder``; copies, on the trainer's device) and every other tensor of
-        the constructor's state_dict exactly as it came in."""
-        out = dict(self._passthrough)
-        out.update({k: v.clone() for k, v in self.named_views(self.params).items()})
-        return out
-
-    def optimizer_state(self):
-        return dict(step=self.step, exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone())
-
-    def load_optimizer_state(self, state):
-        self.step = int(state['step'])
-        self.exp_avg.copy_(state['exp_avg'])
-        self.exp_avg_sq.copy_(state['exp_avg_sq'])
+            names, table = names + POINTNET_PARAM_NAMES, flat_trainer.append_table(table, pointnet_param_table())
+        super().__init__(state_dict, names, table, device, lr, weight_decay, betas, eps, weights, past_len, n_steps, dropout, cond_mask_prob)
+        self._mdm, self._pn, self.pointnet = None, None, None
+        if self.train_pointnet:
+            self.pointnet = PointNetFineTuner(state_dict, self.device, params=self.params[n_mdm:], grad=self.grads[n_mdm:])
+            self.after_step = self.pointnet.refold                   # so the encoder's pack is never stale
 
     def export_mdm(self):
         """An ``interdiff_amd.mdm.MDM`` packed (on the host, ``pack_mdm_weights``) from the current weights: for sampling and ``validation_step``.
@@ -163,22 +129,12 @@ class DenoiserTrainer:
         self._mdm = MDM({k: v.cpu() for k, v in self.state_dict().items()}, device=self.device, n_steps=self.n_steps)
         return self._mdm
 
-    # ------------------------------------------------------------------------------------------------------------ steps
-    def _workspace(self, B, T, S):
-        need = (self.lib.interdiff_mdm_train_full_workspace_bytes if self.train_encoder else self.lib.interdiff_mdm_train_workspace_bytes)(B, T, S)
-        if need == 0:
-            raise ValueError('unsupported shape B=%d T=%d mem_len=%d' % (B, T, S))
-        ws = self._ws.get((B, T, S))
-        if ws is None:
-            ws = self._ws[(B, T, S)] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
-
     def loss_grad(self, pred, target):
         """``interdiff_denoising_loss_grad``: d/d pred of mean_b sum_i w_i term_i[b]."""
         B, T = pred.shape[0], pred.shape[-1]
         d = torch.empty_like(pred)
         _lib.check(self.lib.interdiff_denoising_loss_grad(_lib.dptr(pred.contiguous(), torch.float32), _lib.dptr(target.contiguous(), torch.float32), B, T, self.past_len,
-                                                          self._w16, _lib.dptr(d), _lib.stream()), 'denoising_loss_grad')
+                                                          self._wvec, _lib.dptr(d), _lib.stream()), 'denoising_loss_grad')
         return d
 
     def grads_at(self, x_t, t, cond=None, target=None, d_pred=None, pc=None, obj_points=None):
@@ -187,59 +143,70 @@ class DenoiserTrainer:
         (pred, terms, d_cond, d_pc [B,256]); ``self.cond`` [past_len,B,256] keeps the encoder's output.  With ``train_pointnet`` it is
         ``grads_at(x_t, t, target=target, obj_points=obj_points)``: ``pc`` is encoded from the raw points with saves, and the PointNet++ backward fills the
         last 113,917 entries of ``self.grads`` from ``d_pc``; the result is the same 4-tuple."""
-        if self.train_pointnet:
-            if target is None or obj_points is None or cond is not None or pc is not None:
-                raise ValueError('train_pointnet=True: grads_at(x_t, t, target=target, obj_points=obj_points [B,P,3])')
-            out = self._full_grads_at(x_t, t, self.pointnet.encode_saved(obj_points), target, d_pred)
-            self.pointnet.grads(out[3], flat=True)
-            return out
-        if obj_points is not None:
-            raise ValueError('obj_points= is the train_pointnet form of grads_at')
-        if target is None or (cond is None) == (pc is None) or (pc is not None and not self.train_encoder):
-            raise ValueError('grads_at(x_t, t, cond, target) or, with train_encoder, grads_at(x_t, t, pc, target)')
-        if self.train_encoder:
-            return self._full_grads_at(x_t, t, cond if pc is None else pc, target, d_pred)
-        x_t, target, cond = x_t.contiguous(), target.contiguous(), cond.contiguous()
-        B, T, S = x_t.shape[0], x_t.shape[-1], cond.shape[0]
-        if tuple(x_t.shape[1:3]) != (1, 144) or tuple(cond.shape[1:]) != (B, 256) or target.shape != x_t.shape:
-            raise ValueError('x_t / target [B,1,144,T], cond [mem_len,B,256]')
-        if T > MAX_T:
-            raise ValueError('DenoiserTrainer supports T <= %d (got %d)' % (MAX_T, T))
+        given = [(k, v) for k, v in (('cond', cond), ('pc', pc), ('obj_points', obj_points)) if v is not None]
+        if target is None or len(given) != 1 or given[0][0] not in self._takes:
+            raise ValueError(self._form)
+        return self._grads(x_t, t, given[0][1], target, d_pred)
+
+    # ---- decoder only: cond [mem_len,B,256] is an input
+    def _decoder_inputs(self, batch):
+        if not (isinstance(batch, dict) and 'cond' in batch):        # the conditioning of the lazily exported model (export_mdm)
+            if self._mdm is None:
+                self.export_mdm()
+            batch = as_clip_batch(self._mdm, batch, self.past_len)
+        return batch['gt'], batch['cond']
+
+    def _decoder_grads(self, x_t, t, cond, target, d_pred):
+        x_t, target, d_pred, B, T = self._checked(x_t, target, d_pred)
+        cond, S = cond.contiguous(), cond.shape[0]
+        if tuple(cond.shape[1:]) != (B, 256):
+            raise ValueError('cond must be [mem_len,B,256]')
         if S > MAX_MEM:
             raise ValueError('DenoiserTrainer supports mem_len <= %d (got %d)' % (MAX_MEM, S))
-        if d_pred is not None:
-            if d_pred.shape != x_t.shape:
-                raise ValueError('d_pred must be [B,1,144,T]')
-            d_pred = d_pred.contiguous()
-        ws = self._workspace(B, T, S)
+        ws = self._workspace(self.lib.interdiff_mdm_train_workspace_bytes, B, T, S)
         pred, terms, d_cond = torch.empty_like(x_t), torch.empty(16, B, dtype=torch.float32, device=self.device), torch.empty_like(cond)
         _lib.check(self.lib.interdiff_mdm_train_grads(
             _lib.dptr(self.params), _lib.dptr(self.pe), self.pe.shape[0], _lib.dptr(x_t, torch.float32), _lib.dptr(t.to(self.device).contiguous(), torch.int64),
-            _lib.dptr(cond, torch.float32), _lib.dptr(target, torch.float32), B, T, S, self.past_len, self._w16, _lib.dptr(d_pred, torch.float32, allow_none=True),
+            _lib.dptr(cond, torch.float32), _lib.dptr(target, torch.float32), B, T, S, self.past_len, self._wvec, _lib.dptr(d_pred, torch.float32, allow_none=True),
             _lib.dptr(self.grads), _lib.dptr(d_cond), _lib.dptr(pred), _lib.dptr(terms), _lib.dptr(ws), ws.numel(), _lib.stream()), 'mdm_train_grads')
         return pred, terms, d_cond
 
-    def _full_grads_at(self, x_t, t, pc, target, d_pred):
-        x_t, target, pc = x_t.contiguous(), target.contiguous(), pc.contiguous()
-        B, T, S = x_t.shape[0], x_t.shape[-1], self.past_len
-        if tuple(x_t.shape[1:3]) != (1, 144) or tuple(pc.shape) != (B, 256) or target.shape != x_t.shape:
-            raise ValueError('x_t / target [B,1,144,T], pc [B,256]')
-        if T > MAX_T:
-            raise ValueError('DenoiserTrainer supports T <= %d (got %d)' % (MAX_T, T))
-        if d_pred is not None:
-            if d_pred.shape != x_t.shape:
-                raise ValueError('d_pred must be [B,1,144,T]')
-            d_pred = d_pred.contiguous()
-        ws = self._workspace(B, T, S)
+    # ---- train_encoder: pc [B,256] is the input, cond is computed
+    def _encoder_inputs(self, batch):
+        if isinstance(batch, dict) and 'cond' in batch:
+            raise ValueError('train_encoder=True: a batch that carries cond cannot reach the encoder; pass pc [B,256] or obj_points [B,P,3]')
+        if not isinstance(batch, dict) or 'gt' not in batch or not ('pc' in batch or 'obj_points' in batch):
+            raise ValueError('train_encoder=True takes a clip batch with gt [B,1,144,T] and pc [B,256] or obj_points [B,P,3]')
+        return batch['gt'], (batch['pc'] if 'pc' in batch else self.encode_points(batch['obj_points']))
+
+    def _full_grads(self, x_t, t, pc, target, d_pred):
+        x_t, target, d_pred, B, T = self._checked(x_t, target, d_pred)
+        pc, S = pc.contiguous(), self.past_len
+        if tuple(pc.shape) != (B, 256):
+            raise ValueError('pc must be [B,256]')
+        ws = self._workspace(self.lib.interdiff_mdm_train_full_workspace_bytes, B, T, S)
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
         pred, terms, cond, d_cond, d_pc = torch.empty_like(x_t), new(16, B), new(S, B, 256), new(S, B, 256), new(B, 256)
         _lib.check(self.lib.interdiff_mdm_train_full_grads(
             _lib.dptr(self.params), _lib.dptr(self.pe), self.pe.shape[0], _lib.dptr(x_t, torch.float32), _lib.dptr(t.to(self.device).contiguous(), torch.int64),
-            _lib.dptr(pc, torch.float32), _lib.dptr(target, torch.float32), B, T, S, self._w16, _lib.dptr(d_pred, torch.float32, allow_none=True),
+            _lib.dptr(pc, torch.float32), _lib.dptr(target, torch.float32), B, T, S, self._wvec, _lib.dptr(d_pred, torch.float32, allow_none=True),
             _lib.dptr(self.grads), _lib.dptr(cond), _lib.dptr(d_cond), _lib.dptr(d_pc), _lib.dptr(pred), _lib.dptr(terms), _lib.dptr(ws), ws.numel(), _lib.stream()),
             'mdm_train_full_grads')
         self.cond = cond
         return pred, terms, d_cond, d_pc
+
+    # ---- train_pointnet: raw obj_points [B,P,3] are the input (pc or cond could not carry a gradient to the points)
+    def _pointnet_inputs(self, batch):
+        if isinstance(batch, dict) and ('cond' in batch or 'pc' in batch):
+            raise ValueError('train_pointnet=True: a batch that carries cond or pc cannot reach the points; pass raw obj_points [B,P,3]')
+        if not isinstance(batch, dict) or 'gt' not in batch or 'obj_points' not in batch:
+            raise ValueError('train_pointnet=True takes a clip batch with gt [B,1,144,T] and obj_points [B,P,3]')
+        return batch['gt'], batch['obj_points']
+
+    def _pointnet_grads(self, x_t, t, obj_points, target, d_pred):
+        out = self._full_grads(x_t, t, self.pointnet.encode_saved(obj_points), target, d_pred)
+        self.pointnet.grads(out[3], flat=True)
+        return out
 
     def encode_points(self, obj_points):
         """``pc_embedding`` [B,256] of raw ``obj_points`` [B,P,3]: ``interdiff_pointnet2_encode`` on a pack made once from the constructor's
@@ -258,64 +225,3 @@ class DenoiserTrainer:
         pc = torch.empty(pts.shape[0], 256, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.interdiff_pointnet2_encode(C.byref(pn), _lib.dptr(pts), pts.shape[0], pts.shape[1], _lib.dptr(pc), _lib.stream()), 'pointnet2_encode')
         return pc
-
-    def _full_batch(self, batch):
-        """Encoder mode: (gt [B,1,144,T], pc [B,256]) of a clip batch that carries ``pc`` or raw ``obj_points``; with ``train_pointnet`` (gt, obj_points)."""
-        if self.train_pointnet:
-            if isinstance(batch, dict) and ('cond' in batch or 'pc' in batch):
-                raise ValueError('train_pointnet=True: a batch that carries cond or pc cannot reach the points; pass raw obj_points [B,P,3]')
-            if not isinstance(batch, dict) or 'gt' not in batch or 'obj_points' not in batch:
-                raise ValueError('train_pointnet=True takes a clip batch with gt [B,1,144,T] and obj_points [B,P,3]')
-            return batch['gt'], batch['obj_points']
-        if isinstance(batch, dict) and 'cond' in batch:
-            raise ValueError('train_encoder=True: a batch that carries cond cannot reach the encoder; pass pc [B,256] or obj_points [B,P,3]')
-        if not isinstance(batch, dict) or 'gt' not in batch or not ('pc' in batch or 'obj_points' in batch):
-            raise ValueError('train_encoder=True takes a clip batch with gt [B,1,144,T] and pc [B,256] or obj_points [B,P,3]')
-        return batch['gt'], (batch['pc'] if 'pc' in batch else self.encode_points(batch['obj_points']))
-
-    def _batch(self, batch):
-        if not (isinstance(batch, dict) and 'cond' in batch):
-            if self._mdm is None:
-                self.export_mdm()
-            batch = as_clip_batch(self._mdm, batch, self.past_len)
-        return batch
-
-    def loss_and_grads(self, batch, t=None, noise=None, seed=None, d_pred=None, generator=None):
-        """``forward_backward`` with the backward: the batch handling, timestep draw and ``q_sample`` of ``losses.denoising_losses``, then one
-        forward with saves, the 16 terms, the loss gradient (or ``d_pred`` [B,1,144,T] in its place -- the seam for other objectives) and the
-        backward.  Returns (loss [B], loss_dict {name: [B]}, weighted {name: [B]}, grads {name: tensor} -- views of the flat gradient, valid until
-        the next call --, d_cond [mem_len,B,256]); ``self.pred`` keeps the model output.  With ``train_encoder``: ``d_pc`` [B,256] as a further
-        last element, and ``self.cond`` keeps the conditioning the step computed."""
-        if self.train_encoder:
-            gt, third = self._full_batch(batch)
-        else:
-            batch = self._batch(batch)
-            gt, third = batch['gt'], batch['cond']
-        gt = gt.contiguous()
-        B = gt.shape[0]
-        if gt.shape[-1] > MAX_T:
-            raise ValueError('DenoiserTrainer supports T <= %d (got %d)' % (MAX_T, gt.shape[-1]))
-        if t is None:
-            t, _ = self.diffusion.sample_timesteps(B, gt.device, generator)
-        t = t.to(gt.device)
-        x_t = self.diffusion.q_sample(gt, t, noise=noise, seed=seed)
-        if self.train_pointnet:
-            self.pred, terms, *seams = self.grads_at(x_t, t, target=gt, d_pred=d_pred, obj_points=third)
-        else:
-            self.pred, terms, *seams = self.grads_at(x_t, t, third, gt, d_pred)
-        wt = terms * self._wdev[:, None]
-        return (wt.sum(0), {k: terms[i] for i, k in enumerate(LOSS_KEYS)}, {k: wt[i] for i, k in enumerate(LOSS_KEYS)}, self.named_views(self.grads), *seams)
-
-    def apply_gradients(self):
-        """``optimizer.step()``: AdamW on the flat vectors with the gradient of the last ``loss_and_grads``; with ``train_pointnet`` the re-fold follows."""
-        self.step += 1
-        _lib.check(self.lib.interdiff_mdm_train_step(_lib.dptr(self.params), _lib.dptr(self.grads), _lib.dptr(self.exp_avg), _lib.dptr(self.exp_avg_sq), self.n_param,
-                                                     self.step, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, _lib.stream()), 'mdm_train_step')
-        if self.train_pointnet:
-            self.pointnet.refold()
-
-    def training_step(self, batch, t=None, noise=None, seed=None, d_pred=None, generator=None):
-        """``loss_and_grads`` followed by the AdamW entry; returns what ``loss_and_grads`` returns."""
-        out = self.loss_and_grads(batch, t=t, noise=noise, seed=seed, d_pred=d_pred, generator=generator)
-        self.apply_gradients()
-        return out

@@ -14,7 +14,7 @@ over all 1024 SA1 centres, running-statistic updates), a gradient with respect t
 """
 import ctypes as C
 import torch
-from . import _lib
+from . import _lib, flat_trainer
 from .mdm import pack_pointnet2
 
 PREFIX = 'pcEmbedding'
@@ -44,32 +44,19 @@ POINTNET_STAT_NAMES = tuple(pointnet_stat_names())
 
 def param_table():
     """(offsets, sizes, n_param) of the 38 tensors as the library lays them out."""
-    n = len(POINTNET_PARAM_NAMES)
-    off, size, cnt, total = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_int32(0), C.c_int64(0)
-    _lib.check(_lib.load().interdiff_pointnet2_finetune_param_table(off, size, C.byref(cnt), C.byref(total)), 'pointnet2_finetune_param_table')
-    if cnt.value != n:
-        raise RuntimeError('parameter table: %d tensors, expected %d' % (cnt.value, n))
-    return list(off), list(size), int(total.value)
+    return flat_trainer.param_table('interdiff_pointnet2_finetune_param_table', len(POINTNET_PARAM_NAMES))
 
 
-class PointNetFineTuner:
+class PointNetFineTuner(flat_trainer.FlatParams):
     """``state_dict``: any dict that holds the reference's ``pcEmbedding.*``.  ``params`` / ``grad``: views of a larger flat master / gradient vector to work on
-    (``DenoiserTrainer`` passes the tail of its own); by default the tuner owns both."""
+    (``DenoiserTrainer`` passes the tail of its own); by default the tuner owns both.  ``state_dict()`` gives ``pcEmbedding.*`` under the reference's names: the
+    38 trained tensors (copies) and every other entry (running statistics, ``num_batches_tracked``) with the bits it came in with."""
 
     def __init__(self, state_dict, device='cuda', params=None, grad=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
-        self.names = POINTNET_PARAM_NAMES
-        missing = [k for k in self.names + POINTNET_STAT_NAMES if k not in state_dict]
-        if missing:
-            raise KeyError('state_dict lacks %s' % missing[:3])
-        sd = {k: torch.as_tensor(v).detach() for k, v in state_dict.items() if k.startswith(PREFIX + '.')}
-        self.offsets, self.sizes, self.n_param = param_table()
-        self.shapes = [tuple(sd[k].shape) for k in self.names]
-        for k, s in zip(self.names, self.sizes):
-            if sd[k].numel() != s:
-                raise ValueError('%s: %s does not match the parameter table (%d floats)' % (k, tuple(sd[k].shape), s))
-        flat = torch.cat([sd[k].reshape(-1).float() for k in self.names]).to(self.device)
+        sd = {k: torch.as_tensor(v).detach().clone() for k, v in state_dict.items() if k.startswith(PREFIX + '.')}
+        flat = self._intake(sd, POINTNET_PARAM_NAMES, param_table(), also=POINTNET_STAT_NAMES)
         if params is None:
             self.params = flat.contiguous()
         else:
@@ -79,19 +66,9 @@ class PointNetFineTuner:
         if self.params.numel() != self.n_param or self.grad.numel() != self.n_param or not (self.params.is_contiguous() and self.grad.is_contiguous()):
             raise ValueError('params / grad must be contiguous vectors of %d floats' % self.n_param)
         self.stats = torch.cat([sd[k].reshape(-1).float() for k in POINTNET_STAT_NAMES]).to(self.device).contiguous()
-        self._passthrough = {k: v.clone() for k, v in sd.items() if k not in self.names}       # running statistics, num_batches_tracked: their own bits
         self.pn, self.arena = pack_pointnet2(sd, self.device)
         self._saves = self._points = None
         self._ws = {}
-
-    def named_views(self, flat):
-        return {k: flat[o:o + s].view(shp) for k, o, s, shp in zip(self.names, self.offsets, self.sizes, self.shapes)}
-
-    def state_dict(self):
-        """``pcEmbedding.*`` under the reference's names: the 38 trained tensors (copies) and every other entry as it came in."""
-        out = dict(self._passthrough)
-        out.update({k: v.clone() for k, v in self.named_views(self.params).items()})
-        return out
 
     def encode_saved(self, obj_points):
         """``pc_embedding`` [B,256] of ``obj_points`` [B,P,3] (P <= 2048) with the record the backward reads (``interdiff_pointnet2_encode_saved``)."""

@@ -17,19 +17,16 @@ Points: E1  B = 4, T = 35, past_len 10, t = [37, 412, 655, 999] (the scene of md
 odd batch, a memory length other than 10, the shortest decoder the limits allow, t = 0; 15 encoder rows, one 32-row GEMM tile not filled).  pc_embedding is a recorded leaf.
 Measured on MI355X: DESIGN.md 8.16.  Without the feature every test below fails: the keyword, the names and the entries do not exist.
 """
-import os
-import re
 import numpy as np
 import pytest
 import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
+from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 DEV = 'cuda'
 N_PARAM, N_PARAM_DEC = 11824392, 7069900
-FLOOR = 1e-5
 NEW_SYMBOLS = {
     'interdiff_mdm_train_full_param_table': 'int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param',
     'interdiff_mdm_train_full_workspace_bytes': 'int32_t B, int32_t T, int32_t past_len',
@@ -48,20 +45,6 @@ def names():
 def meo():
     from tests import mdm_encoder_train_oracle
     return mdm_encoder_train_oracle
-
-
-def tn(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def rel(a, b):
-    a, b = (x.detach().cpu().double() if isinstance(x, torch.Tensor) else tn(x).double() for x in (a, b))
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-def betas():
-    from interdiff_amd.diffusion import get_named_beta_schedule
-    return get_named_beta_schedule('cosine', 1000, 1.)
 
 
 _POINTS = {}
@@ -85,10 +68,6 @@ def point(name):
         assert [str(k) for k in z['wk_names']] == list(meo().WK_NAMES)
         _POINTS[name] = dict(z=z, x0=x0, pc=pc, t=t, eps=eps, x_t=x_t, past=past, ref=ref, e_ref=e_ref)
     return _POINTS[name]
-
-
-def gate(e_ref):
-    return max(4.0 * float(e_ref), FLOOR)
 
 
 @pytest.fixture(scope='module')
@@ -154,15 +133,7 @@ def test_oracle_trajectory_vs_reference_samples(traj):
 
 
 def test_new_symbols_declared_typed_and_exported():
-    from interdiff_amd import _lib
-    src = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'include', 'interdiff_hip.h')).read())
-    for name, args in NEW_SYMBOLS.items():
-        assert '%s(%s);' % (name, args) in src, name
-        assert name in _lib._SIGS and len(_lib._SIGS[name][1]) == args.count(',') + 1, name
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name)
-    assert lib.interdiff_abi_version() == _lib.ABI_VERSION == 17          # additive entries: the ABI version does not move
+    lib = check_new_symbols(NEW_SYMBOLS)
     # the limits, on the host: T <= 128, 2 <= past_len <= 16, T >= past_len + 2
     ok = lib.interdiff_mdm_train_full_workspace_bytes
     assert ok(3, 12, 5) > lib.interdiff_mdm_train_workspace_bytes(3, 12, 5) > 0 and ok(1, 4, 2) > 0 and ok(2, 128, 16) > 0
@@ -326,13 +297,8 @@ def test_trajectory_vs_fp64(lib, traj):
         assert e <= 1e-5
     got = tr.state_dict()
     y = float(z['y_traj'])
-    far, worst, moved = 0, 0.0, 0.0
-    for k in FULL:
-        dist = (got[k].cpu().double() - traj['theta'][k]).abs()
-        far += int((dist > 8 * y).sum())
-        worst = max(worst, float(dist.max()))
-        if k.startswith('encoder.'):
-            moved = max(moved, float((got[k].cpu() - sd[k]).abs().max()))
+    far, worst = far_parameters(got, traj['theta'], FULL, y)
+    moved = max(float((got[k].cpu() - sd[k]).abs().max()) for k in FULL if k.startswith('encoder.'))
     print('trajectory: %d of %d parameters further than 8 y_traj = %.3e from fp64 (cap %d); max distance %.3e; largest encoder move %.3e'
           % (far, N_PARAM, 8 * y, N_PARAM // 1000, worst, moved))
     assert far <= N_PARAM // 1000

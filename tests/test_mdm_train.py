@@ -11,20 +11,16 @@ Points: A  B = 4, T = 35, t = [37, 412, 655, 999] (M = 140 rows);  B  B = 3, T =
 t = 0, an odd batch).  Weights: fixtures.mdm_weights_wc(), with the rows of the sinusoidal table that the reference runs read taken from the recordings (``weights()``:
 sin / cos of fp32 arguments differ in the last bits between CPUs, and e_ref is that small).  Without the feature this module fails at import (interdiff_amd.mdm_train does not exist).
 """
-import os
-import re
-import numpy as np
 import pytest
 import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
+from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
 from interdiff_amd.mdm_train import PARAM_NAMES
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 DEV = 'cuda'
 N_PARAM = 7069900
-FLOOR = 1e-5
 NEW_SYMBOLS = {
     'interdiff_denoising_loss_grad': 'const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights16, float *d_pred, void *stream',
     'interdiff_mdm_train_param_table': 'int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param',
@@ -35,20 +31,6 @@ NEW_SYMBOLS = {
     'interdiff_mdm_train_step': 'float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, double lr, double beta1, double beta2, '
                                 'double eps, double weight_decay, void *stream',
 }
-
-
-def tn(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def rel(a, b):
-    a, b = (x.detach().cpu().double() if isinstance(x, torch.Tensor) else tn(x).double() for x in (a, b))
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-def betas():
-    from interdiff_amd.diffusion import get_named_beta_schedule
-    return get_named_beta_schedule('cosine', 1000, 1.)
 
 
 _POINTS = {}
@@ -71,10 +53,6 @@ def point(name):
         e_ref = dict(zip([str(k) for k in z['names']], z['e_ref']))
         _POINTS[name] = dict(z=z, x0=x0, cond=cond, t=t, eps=eps, x_t=x_t, ref=ref, e_ref=e_ref)
     return _POINTS[name]
-
-
-def gate(e_ref):
-    return max(4.0 * float(e_ref), FLOOR)
 
 
 # ------------------------------------------------------------------------------------------------------------ CPU
@@ -127,15 +105,7 @@ def test_closed_form_d_pred_vs_autograd(name):
 
 def test_new_symbols_declared_typed_and_exported():
     """Fails on the parent commit: the entries do not exist there."""
-    from interdiff_amd import _lib
-    src = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'include', 'interdiff_hip.h')).read())
-    for name, args in NEW_SYMBOLS.items():
-        assert '%s(%s);' % (name, args) in src, name
-        assert name in _lib._SIGS and len(_lib._SIGS[name][1]) == args.count(',') + 1, name
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name)
-    assert lib.interdiff_abi_version() == _lib.ABI_VERSION == 17          # additive entries: the ABI version does not move
+    check_new_symbols(NEW_SYMBOLS)
     assert 'mdm_train.hip' in __import__('interdiff_amd.csrc.build', fromlist=['sources']).sources()
 
 
@@ -272,11 +242,7 @@ def test_trajectory_vs_fp64(lib, traj):
         assert e <= 1e-5
     got = tr.state_dict()
     y = float(z['y_traj'])
-    far, worst = 0, 0.0
-    for k in PARAM_NAMES:
-        d = (got[k].cpu().double() - traj['theta'][k]).abs()
-        far += int((d > 8 * y).sum())
-        worst = max(worst, float(d.max()))
+    far, worst = far_parameters(got, traj['theta'], PARAM_NAMES, y)
     print('trajectory: %d of %d parameters further than 8 y_traj = %.3e from fp64 (cap %d); max distance %.3e' % (far, N_PARAM, 8 * y, N_PARAM // 1000, worst))
     assert far <= N_PARAM // 1000
 

@@ -10,19 +10,16 @@ gate tests/test_mdm_encoder_train.py holds the same comparison to (the sampler's
 Without the feature every test below fails: the module, the keyword and the entries do not exist.
 """
 import ctypes as C
-import os
-import re
 import numpy as np
 import pytest
 import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
+from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 DEV = 'cuda'
 N_PN, N_FULL = 113917, 11824392
-FLOOR = 1e-5
 NEW_SYMBOLS = {
     'interdiff_pointnet2_saves_bytes': 'int32_t B',
     'interdiff_pointnet2_encode_saved': 'const idf_pointnet2 *pn, const float *obj_points, int32_t B, int32_t P, float *out, void *saves, size_t saves_bytes, void *stream',
@@ -43,20 +40,6 @@ def po():
 def meo():
     from tests import mdm_encoder_train_oracle
     return mdm_encoder_train_oracle
-
-
-def tn(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def rel(a, b):
-    a, b = (x.detach().cpu().double() if isinstance(x, torch.Tensor) else tn(x).double() for x in (a, b))
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-def betas():
-    from interdiff_amd.diffusion import get_named_beta_schedule
-    return get_named_beta_schedule('cosine', 1000, 1.)
 
 
 def golden(name):
@@ -92,10 +75,6 @@ def point(name):
         p['ref'] = po().grads(weights(), pts, idx, p['d_pc'], taps=True)
         _POINTS[name] = p
     return _POINTS[name]
-
-
-def gate(e_ref):
-    return max(4.0 * float(e_ref), FLOOR)
 
 
 @pytest.fixture(scope='module')
@@ -188,13 +167,7 @@ def test_param_table_vs_reference_module():
 
 
 def test_new_symbols_declared_typed_and_exported():
-    from interdiff_amd import _lib
-    src = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'include', 'interdiff_hip.h')).read())
-    for name, args in NEW_SYMBOLS.items():
-        assert '%s(%s);' % (name, args) in src, name
-        assert name in _lib._SIGS and len(_lib._SIGS[name][1]) == args.count(',') + 1, name
-    lib = _lib.load()
-    assert lib.interdiff_abi_version() == _lib.ABI_VERSION == 17               # additive entries: the ABI version does not move
+    lib = check_new_symbols(NEW_SYMBOLS)
     assert lib.interdiff_pointnet2_saves_bytes(3) == 3 * 7156 * 4 and lib.interdiff_pointnet2_saves_bytes(0) == 0
     assert lib.interdiff_pointnet2_finetune_workspace_bytes(3) > 3 * 4 * (N_PN - 1472) and lib.interdiff_pointnet2_finetune_workspace_bytes(0) == 0
 
@@ -366,12 +339,8 @@ def test_trajectory_vs_fp64(lib, traj):
             assert all(not torch.equal(now[n].cpu(), sd[n]) for n in POINTNET_PARAM_NAMES)          # every one of the 38 tensors has moved after step 1
     got = tr.state_dict()
     y = float(z['y_traj'])
-    far, far_pn, worst = 0, 0, 0.0
-    for k in FULL_PARAM_NAMES + POINTNET_PARAM_NAMES:
-        dist = (got[k].cpu().double() - traj['theta'][k]).abs()
-        far += int((dist > 8 * y).sum())
-        far_pn += int((dist > 8 * y).sum()) if k in POINTNET_PARAM_NAMES else 0
-        worst = max(worst, float(dist.max()))
+    far, worst = far_parameters(got, traj['theta'], FULL_PARAM_NAMES + POINTNET_PARAM_NAMES, y)
+    far_pn = far_parameters(got, traj['theta'], POINTNET_PARAM_NAMES, y)[0]
     n = N_FULL + N_PN
     print('trajectory: %d of %d parameters further than 8 y_traj = %.3e from fp64 (cap %d; %d of them in pcEmbedding); max distance %.3e' % (far, n, 8 * y, n // 1000, far_pn, worst))
     assert far <= n // 1000

@@ -15,19 +15,16 @@ further than 8 y_traj from the fp64 trajectory.  Bit-identity claims are ``torch
 Points: S1  B = 3, T = 20, t = [37, 412, 875] (the scene of skel_losses.npz);  S2  B = 3, T = 70, t = [5, 500, 990] (more than one 64-key tile, an odd batch).
 Measured on MI355X: DESIGN.md 8.17.  Without the feature every test below fails: the module, the names and the entries do not exist.
 """
-import os
-import re
 import numpy as np
 import pytest
 import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import skeleton_losses_oracle as slo
+from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 DEV = 'cuda'
 N_PARAM, SEED, PAST = 5499582, 1106, 10                                   # SEED: make_golden_skeleton_mdm.SEED, the weights every skeleton-denoiser fixture uses
-FLOOR = 1e-5
 NEW_SYMBOLS = {
     'interdiff_skeleton_denoising_loss_grad': 'const float *pred, const float *target, int32_t B, int32_t T, int32_t past_len, const float *weights13, float *d_pred, '
                                               'void *stream',
@@ -42,20 +39,6 @@ NEW_SYMBOLS = {
 def so():
     from tests import skeleton_mdm_train_oracle
     return skeleton_mdm_train_oracle
-
-
-def tn(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def rel(a, b):
-    a, b = (x.detach().cpu().double() if isinstance(x, torch.Tensor) else tn(x).double() for x in (a, b))
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-def betas():
-    from interdiff_amd.diffusion import get_named_beta_schedule
-    return get_named_beta_schedule('cosine', 1000, 1.)
 
 
 def raw_weights():
@@ -96,10 +79,6 @@ def synthetic_point(seed, B, T, past=PAST):
     t, eps = tn(rs.randint(0, 1000, size=B).astype(np.int64)), fx._randn(rs, B, 1, 106, T)
     x_t = lo.q_sample(betas(), x0, t, eps)
     return dict(x0=x0, zpo=zpo, t=t, eps=eps, x_t=x_t, ref=so().grads(weights(), x_t, t, zpo, x0, past))
-
-
-def gate(e_ref):
-    return max(4.0 * float(e_ref), FLOOR)
 
 
 def flat_gate(ref, r32):
@@ -222,15 +201,7 @@ def test_param_names_and_table():
 
 
 def test_new_symbols_declared_typed_and_exported():
-    from interdiff_amd import _lib
-    src = re.sub(r'\s+', ' ', open(os.path.join(ROOT, 'include', 'interdiff_hip.h')).read())
-    for name, args in NEW_SYMBOLS.items():
-        assert '%s(%s);' % (name, args) in src, name
-        assert name in _lib._SIGS and len(_lib._SIGS[name][1]) == args.count(',') + 1, name
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name)
-    assert lib.interdiff_abi_version() == _lib.ABI_VERSION == 17          # additive entries: the ABI version does not move
+    lib = check_new_symbols(NEW_SYMBOLS)
     ok = lib.interdiff_skeleton_mdm_train_workspace_bytes
     assert ok(3, 20, 10) > 0 and ok(1, 12, 10) > 0 and ok(1, 128, 10) > 0 and ok(1, 4, 2) > 0
     assert ok(1, 129, 10) == 0 and ok(3, 12, 1) == 0 and ok(3, 30, 17) == 0 and ok(3, 11, 10) == 0 and ok(0, 12, 5) == 0
@@ -428,12 +399,8 @@ def test_trajectory_vs_fp64(lib, traj):
         assert e <= 1e-5
     got = tr.state_dict()
     y = float(z['y_traj'])
-    far, worst, moved = 0, 0.0, 0.0
-    for k in so().PARAM_NAMES:
-        dist = (got[k].cpu().double() - traj['theta'][k]).abs()
-        far += int((dist > 8 * y).sum())
-        worst = max(worst, float(dist.max()))
-        moved = max(moved, float((got[k].cpu() - sd[k]).abs().max()))
+    far, worst = far_parameters(got, traj['theta'], so().PARAM_NAMES, y)
+    moved = max(float((got[k].cpu() - sd[k]).abs().max()) for k in so().PARAM_NAMES)
     print('trajectory: %d of %d parameters further than 8 y_traj = %.3e from fp64 (cap %d); max distance %.3e; largest move %.3e'
           % (far, N_PARAM, 8 * y, N_PARAM // 1000, worst, moved))
     assert far <= N_PARAM // 1000 == 5499

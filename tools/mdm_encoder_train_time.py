@@ -81,21 +81,12 @@ def main():
         sides = dict(hip_full_step_ms=lambda: full.training_step(dict(gt=gt, pc=pc), t=t, noise=eps),
                      hip_decoder_only_step_ms=lambda: dec.training_step(dict(gt=gt, cond=cond), t=t, noise=eps),
                      torch_eager_full_step_ms=lambda: ts.step(x_t, t, pc, gt))
-        meds = {k: [] for k in sides}
-        for blk in range(a.blocks + 1):                                 # block 0 warms the sides up and is dropped
-            for k, fn in sides.items():
-                m = mtt.block_ms(fn, a.calls)
-                if blk:
-                    meds[k].append(m)
-        row = dict(B=B, T=T, first_loss_hip=first[0], first_loss_torch=first[1])
-        for k, v in meds.items():
-            row[k] = dict(median=float(np.median(v)), lo=float(min(v)), hi=float(max(v)))
+        row = dict(B=B, T=T, first_loss_hip=first[0], first_loss_torch=first[1], **mtt.alternate(sides, a.blocks, a.calls))
         row['encoder_adds_ms'] = row['hip_full_step_ms']['median'] - row['hip_decoder_only_step_ms']['median']
         row['torch_over_hip_full_step'] = row['torch_eager_full_step_ms']['median'] / row['hip_full_step_ms']['median']
         res['shapes'].append(row)
         print('B = %d, T = %d on %s: first-step loss hip %.6f, torch %.6f' % (B, T, res['device'], first[0], first[1]))
-        for k in sides:
-            print('  %-32s %9.3f  [%.3f, %.3f]' % (k, row[k]['median'], row[k]['lo'], row[k]['hi']))
+        mtt.print_sides(row, sides)
         print('  the encoder adds (ms)            %9.3f' % row['encoder_adds_ms'])
         print('  torch eager full / hip full step %9.2f' % row['torch_over_hip_full_step'])
     if a.json:

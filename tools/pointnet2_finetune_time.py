@@ -49,21 +49,12 @@ def main():
                      hip_encoder_step_ms=lambda: old.training_step(batch, t=t, noise=eps),
                      encode_ms=lambda: old.encode_points(pts), encode_saved_ms=lambda: ft.encode_saved(pts),
                      backward_ms=lambda: ft.grads(d_pc, flat=True), refold_ms=ft.refold)
-        meds = {k: [] for k in sides}
-        for blk in range(a.blocks + 1):                                 # block 0 warms the sides up and is dropped
-            for k, fn in sides.items():
-                m = mtt.block_ms(fn, a.calls)
-                if blk:
-                    meds[k].append(m)
-        row = dict(B=B, T=T, first_loss_pointnet=first[0], first_loss_encoder=first[1])
-        for k, v in meds.items():
-            row[k] = dict(median=float(np.median(v)), lo=float(min(v)), hi=float(max(v)))
+        row = dict(B=B, T=T, first_loss_pointnet=first[0], first_loss_encoder=first[1], **mtt.alternate(sides, a.blocks, a.calls))
         row['pointnet_adds_ms'] = row['hip_pointnet_step_ms']['median'] - row['hip_encoder_step_ms']['median']
         row['backward_over_encode'] = row['backward_ms']['median'] / row['encode_ms']['median']
         res['shapes'].append(row)
         print('B = %d, T = %d, P = %d on %s: first-step loss with the PointNet++ in the pass %.6f, without %.6f' % (B, T, P, res['device'], first[0], first[1]))
-        for k in sides:
-            print('  %-32s %9.3f  [%.3f, %.3f]' % (k, row[k]['median'], row[k]['lo'], row[k]['hi']))
+        mtt.print_sides(row, sides)
         print('  the feature adds (ms)            %9.3f' % row['pointnet_adds_ms'])
         print('  backward / encode                %9.3f' % row['backward_over_encode'])
     if a.json:

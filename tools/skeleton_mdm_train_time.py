@@ -22,7 +22,7 @@ from interdiff_amd.skeleton_mdm_train import SkeletonDenoiserTrainer, PARAM_NAME
 from interdiff_amd.mdm import positional_table                          # noqa: E402
 from interdiff_amd.skeleton_losses import SkeletonLossWeights           # noqa: E402
 from oracle import denoiser as od                                       # noqa: E402
-from tools.mdm_train_time import qan_block, block_ms                    # noqa: E402
+from tools.mdm_train_time import alternate, print_sides, qan_block      # noqa: E402
 
 DEV, PAST = 'cuda', 10
 SHAPES = ((32, 35), (16, 35))
@@ -121,20 +121,11 @@ def main():
         first = float(tr.training_step(clip, t=t, noise=eps)[0].mean()), float(ts.step(x_t, t, zpo, gt))
         sides = dict(hip_grads_ms=lambda: tr.grads_at(x_t, t, zpo, gt), hip_adamw_ms=tr.apply_gradients,
                      hip_training_step_ms=lambda: tr.training_step(clip, t=t, noise=eps), torch_eager_training_step_ms=lambda: ts.step(x_t, t, zpo, gt))
-        meds = {k: [] for k in sides}
-        for blk in range(a.blocks + 1):                                 # block 0 warms both sides up and is dropped
-            for k, fn in sides.items():
-                m = block_ms(fn, a.calls)
-                if blk:
-                    meds[k].append(m)
-        row = dict(B=B, T=T, first_loss_hip=first[0], first_loss_torch=first[1])
-        for k, v in meds.items():
-            row[k] = dict(median=float(np.median(v)), lo=float(min(v)), hi=float(max(v)))
+        row = dict(B=B, T=T, first_loss_hip=first[0], first_loss_torch=first[1], **alternate(sides, a.blocks, a.calls))
         row['torch_over_hip_step'] = row['torch_eager_training_step_ms']['median'] / row['hip_training_step_ms']['median']
         res['shapes'].append(row)
         print('B = %d, T = %d on %s: first-step loss hip %.6f, torch %.6f' % (B, T, res['device'], first[0], first[1]))
-        for k in sides:
-            print('  %-32s %9.3f  [%.3f, %.3f]' % (k, row[k]['median'], row[k]['lo'], row[k]['hi']))
+        print_sides(row, sides)
         print('  torch eager step / hip step     %9.2f' % row['torch_over_hip_step'])
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
