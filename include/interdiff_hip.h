@@ -1180,6 +1180,54 @@ int interdiff_debug_skeleton_setup(const idf_skel_view *view, const float *body,
 int interdiff_debug_skeleton_pixel(const int32_t *rec, int32_t n_rec, const int32_t *ij, int32_t *out, int32_t n);
 
 /* ------------------------------------------------------------------------------------
+ * Training batches from a device-resident clip set (csrc/clip_batch.hip, per-clip math csrc/clip_canon.h; interdiff_amd/dataset.py).
+ * Additive entries: interdiff_abi_version() stays what it was.
+ *
+ * idf_clip_set: the sequences of a split, concatenated over their frames (F = sum of the frame counts), all on the DEVICE:
+ *      seq_off int64 [n_seq + 1] first global frame of every sequence; pose fp32 [F][156]; betas fp32 [F][10];
+ *      fit64 double [F][12] = root axis-angle | body translation | object axis-angle | object translation (the four fields the
+ *      canonicalisation computes on, in the files' own precision); joints fp32 [F][9] = pelvis | left foot | right foot (SMPL joints 0, 10, 11);
+ *      obj_points6 fp32 [n_seq][P][6] = xyz | normal; first_label int32 [n_seq] the stored foot label of every sequence's frame 0 (10 or 11);
+ *      body_ptr int32 [F + 1], body_idx int32 [body_ptr[F]]: the per-frame body contact lists as CSR, every index < V;
+ *      markers_idx int32 [n_markers].
+ * clips int32 [2][B] (DEVICE) = sequence ids | start frames; clip b holds the sequence frames start + t * sample_rate, t < T <= 128.  The caller
+ *      checks that they lie inside the sequence; a clip that does not is skipped (nothing of it is written), never dereferenced.
+ *
+ *  interdiff_clip_batch   data/dataset_smpl.py:105-152 and :171-179 (Dataset.__getitem__: canonicalisation in the frame of the first pose, foot-ground
+ *      labels) plus model/diffusion_smpl.py:212-214 (the ground-truth token) for B clips in ONE launch: body_pose [T,B,66], hand_pose [T,B,90],
+ *      body_trans / obj_angles / obj_trans / pelvis [T,B,3], beta [T,B,10], gt [B,1,144,T], ground [T,B,2], centroid [B,3], rotation [B,3,3],
+ *      obj_points [B,P,3], obj_points6 [B,P,6]; contact_label uint8 [T,B,V] (:167-168) in a second launch unless the pointer is null (then
+ *      interdiff_clip_body_records writes it).  The arithmetic is double, rounded to fp32 once.  A first frame whose heading is undefined (global
+ *      orientation entries [0][0] = [2][0] = 0) gives non-finite output, as in the reference.
+ *  interdiff_clip_body_records   :134-139, :167-169, :189 in one launch: verts / normals fp32 [n_frames][V][3] (interdiff_smpl_forward on the canonical
+ *      pose, interdiff_vertex_normals) + the body CSR -> human_verts fp32 [T,B,V,7] (16-byte aligned) = vertex | normal | label, markers
+ *      [T,B,n_markers,7] = its rows markers_idx, contact_label uint8 [T,B,V] (or null).  frame_map int32 [n_frames] (or null: identity): the
+ *      destination frame t * B + b of every input frame -- a gender's subset of the clips writes into the batch's slots.
+ *  interdiff_debug_clip_canon   HOST instance of the per-clip math for the T gathered frames of one clip: fit double [T][12], pelvis fp32 [T][3],
+ *      pose fp32 [T][156] -> root / trans / obj_angle / obj_trans / pelvis_out fp32 [T][3], gt fp32 [144][T], centroid [3], rotation [9].
+ *      rotation_override fp32 [9] (or null): a rotation to compose with instead of the one frame 0's heading gives.
+ *  Returns: IDF_OK; IDF_E_INVAL (null pointer, B, T, sample_rate <= 0, T > 128, V > 65536, misaligned human_verts); IDF_E_LAUNCH.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_seq, P, V, n_markers;
+    const int64_t *seq_off;
+    const float *pose, *betas;
+    const double *fit64;
+    const float *joints, *obj_points6;
+    const int32_t *first_label, *body_ptr, *body_idx, *markers_idx;
+} idf_clip_set;
+typedef struct {
+    float *body_pose, *hand_pose, *body_trans, *obj_angles, *obj_trans, *pelvis, *beta, *gt, *ground, *centroid, *rotation, *obj_points, *obj_points6;
+    uint8_t *contact_label;
+} idf_clip_batch;
+int interdiff_clip_batch(const idf_clip_set *cs, const int32_t *clips, int32_t B, int32_t T, int32_t sample_rate, const idf_clip_batch *out, void *stream);
+int interdiff_clip_body_records(const idf_clip_set *cs, const int32_t *clips, int32_t B, int32_t T, int32_t sample_rate, const float *verts,
+                                const float *normals, const int32_t *frame_map, int64_t n_frames, float *human_verts, float *markers,
+                                uint8_t *contact_label, void *stream);
+int interdiff_debug_clip_canon(const double *fit, const float *pelvis, const float *pose, int32_t T, const float *rotation_override, float *root,
+                               float *trans, float *obj_angle, float *obj_trans, float *pelvis_out, float *gt, float *centroid, float *rotation);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

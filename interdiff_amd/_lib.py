@@ -103,7 +103,21 @@ class SkelView(C.Structure):
                 ('line_wd', i32), ('disc_wd', i32), ('style', i32), ('pred_from', i32), ('colour', (C.c_uint8 * 4) * 5)]
 
 
-SKEL_PLAIN, SKEL_PREDGT = 0, 1                             # idf_skel_view.style (IDF_SKEL_*)
+class ClipSet(C.Structure):
+    _fields_ = [('n_seq', i32), ('P', i32), ('V', i32), ('n_markers', i32), ('seq_off', vp), ('pose', vp), ('betas', vp), ('fit64', vp), ('joints', vp),
+                ('obj_points6', vp), ('first_label', vp), ('body_ptr', vp), ('body_idx', vp), ('markers_idx', vp)]
+
+
+CLIP_BATCH_FIELDS = ('body_pose', 'hand_pose', 'body_trans', 'obj_angles', 'obj_trans', 'pelvis', 'beta', 'gt', 'ground', 'centroid', 'rotation', 'obj_points',
+                     'obj_points6', 'contact_label')
+
+
+class ClipBatch(C.Structure):
+    _fields_ = [(k, vp) for k in CLIP_BATCH_FIELDS]
+
+
+CLIP_MAX_T = 128
+SKEL_PLAIN, SKEL_PREDGT = 0, 1                            # idf_skel_view.style (IDF_SKEL_*)
 SKEL_REC_INTS, SKEL_MAX_REC, SKEL_MAX_WIRES, SKEL_WD_MAX, SKEL_TILE = 8, 128, 40, 1024, 16
 RMESH_SCENE_SPACE, RMESH_VERTEX_RGB = 1, 2                 # idf_render_mesh.flags (IDF_RMESH_*)
 RENDER_SUBPIX, RENDER_GUARD, RENDER_MAX_DIM, RENDER_ZONE, RENDER_REC_INTS, RENDER_TILE = 16, 32768, 2048, 1 << 28, 20, 16
@@ -233,7 +247,10 @@ _SIGS = {
     'interdiff_optimize_step': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp]),
     'interdiff_optimize_finish': (C.c_int, [C.POINTER(OptCtx), C.POINTER(OptState), vp, vp, vp, vp, vp]),
     'interdiff_debug_joint_map_vjp': (C.c_int, [vp, vp, vp, i32]),
-    'interdiff_debug_lds_sentinel': (C.c_int, [vp, i32, i32, vp]),
+    'interdiff_clip_batch': (C.c_int, [C.POINTER(ClipSet), vp, i32, i32, i32, C.POINTER(ClipBatch), vp]),
+    'interdiff_clip_body_records': (C.c_int, [C.POINTER(ClipSet), vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]),
+    'interdiff_debug_clip_canon': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'interdiff_debug_lds_sentinel':(C.c_int, [vp, i32, i32, vp]),
     'interdiff_exclusive_cu_report': (C.c_int, [C.c_char_p, i32]),
     'interdiff_debug_deny_exclusive': (C.c_int, [C.c_char_p]),
     'interdiff_debug_f16_aggressor': (C.c_int, [vp, sz, vp, i32, i32, i32, vp]),

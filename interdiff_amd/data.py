@@ -10,7 +10,8 @@ dataset plumbing, not the hot path); the one heavy step, the per-frame pelvis = 
 normals and contact labels, foot-ground labels, human contact labels (:48-50,152-180; read by the reference's training code, never
 by the sampler, the hook or the metrics) -- come from ``clip_labels`` when the sequence has a ``contact.npz`` (written by ``contact_labels.generate_contact`` /
 ``write_contact_npz`` from the fits and an object mesh read by ``load_obj_mesh`` / ``load_ply_mesh``); the per-vertex ``human_verts`` records come
-from ``correction_losses.body_records``; rendering inputs are not produced."""
+from ``correction_losses.body_records``; rendering inputs are not produced.  Training batches are built on the GPU by ``dataset.DeviceClipSet``
+(csrc/clip_batch.hip); the functions here are the host route it is tested against."""
 import os
 import numpy as np
 import torch

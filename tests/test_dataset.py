@@ -1,0 +1,470 @@
+"""interdiff_amd/dataset.py: the clip index and start draw (host), the per-clip canonicalisation math of csrc/clip_canon.h on its host instance
+(interdiff_debug_clip_canon) against scipy / ``data.canonicalize_clip``, and -- on the GPU -- ``DeviceClipSet.assemble`` against the reference's recorded
+``__getitem__`` outputs (tests/golden/etl.npz), the host route (``canonicalize_clip`` + ``clip_labels`` + ``collate_raw`` + ``body_records``) and the trainers."""
+import functools
+import os
+import numpy as np
+import pytest
+import torch
+from scipy.spatial.transform import Rotation
+from interdiff_amd import data as D
+from interdiff_amd.dataset import ClipIndex, draw_starts
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
+DEV = 'cuda'
+
+
+def gate(got, ref):
+    """|got - ref| <= 1e-6 max(1, |ref|max): the gate of test_behave_etl_matches_reference_dataset.  -> the largest error"""
+    a, b = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    err = float(np.abs(a - b).max())
+    assert err <= 1e-6 * max(1.0, float(np.abs(b).max())), err
+    return err
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 1, 2: index and draw (host)
+def test_clip_index_matches_the_rule_worked_by_hand():
+    names, counts = ['Date01_a', 'Date03_b', 'Date02_c'], [100, 71, 34]
+    tr = ClipIndex(names, counts, 'train', 10, 25)
+    assert tr.entries == [(0, 0, 35), (0, 35, 31)] and tr.names == ['Date01_a', 'Date02_c'] and tr.source == [0, 2] and len(tr) == 2
+    te = ClipIndex(names, counts, 'test', 10, 25)
+    assert te.entries == [(0, 0, 1), (0, 35, 1)] and te.names == ['Date03_b'] and te.frame_counts == [71]
+    r2 = ClipIndex(names, counts, 'train', 10, 25, sample_rate=2)                 # fragment 70: one fragment of sequence 0, bias 100 + 1 - 70
+    assert r2.entries == [(0, 0, 31)] and r2.fragment == 70
+    assert ClipIndex(['Date01_a'], [210], 'train', 10, 25, sample_rate=2).entries == [(0, 0, 70), (0, 70, 70), (0, 140, 1)]
+    for idx in (tr, te, r2, ClipIndex(['Date04_x', 'Date05_y'], [209, 35], 'train', 4, 8, 3)):
+        T = idx.past_len + idx.future_len
+        for k, off, bias in idx.entries:
+            assert bias >= 1
+            for draw in range(bias):                                              # every admissible draw stays inside the sequence
+                assert off + draw + T * idx.sample_rate <= idx.frame_counts[k]
+    with pytest.raises(ValueError):
+        ClipIndex(names, counts, 'val')
+    with pytest.raises(ValueError):
+        ClipIndex(names, counts[:2], 'train')
+
+
+def test_draw_starts_is_the_reference_stream():
+    entries = ClipIndex(['Date01_a', 'Date02_b', 'Date02_c'], [100, 171, 36], 'train', 10, 25).entries
+    assert len(entries) == 7
+    for s in (0, 7, 1234):
+        np.random.seed(s)
+        want = [(k, int(np.random.choice(bias)) + off) for k, off, bias in entries]           # data/dataset_smpl.py:108, once per __getitem__
+        assert draw_starts(entries, np.random.RandomState(s)) == want
+    assert draw_starts(entries, np.random.RandomState(1)) != draw_starts(entries, np.random.RandomState(2))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 3: the per-clip math (host instance)
+def debug_canon(fit, pelvis, pose, rotation=None):
+    from interdiff_amd import _lib
+    lib = _lib.load()
+    fit, pelvis, pose = np.ascontiguousarray(fit, np.float64), np.ascontiguousarray(pelvis, np.float32), np.ascontiguousarray(pose, np.float32)
+    T = fit.shape[0]
+    assert fit.shape == (T, 12) and pelvis.shape == (T, 3) and pose.shape == (T, 156)
+    o = {k: np.zeros((T, 3), np.float32) for k in ('root', 'trans', 'obj_angles', 'obj_trans', 'pelvis')}
+    o.update(gt=np.zeros((144, T), np.float32), centroid=np.zeros(3, np.float32), rotation=np.zeros((3, 3), np.float32))
+    rot = None if rotation is None else np.ascontiguousarray(rotation, np.float32)
+    rc = lib.interdiff_debug_clip_canon(fit.ctypes.data, pelvis.ctypes.data, pose.ctypes.data, T, None if rot is None else rot.ctypes.data, o['root'].ctypes.data,
+                                        o['trans'].ctypes.data, o['obj_angles'].ctypes.data, o['obj_trans'].ctypes.data, o['pelvis'].ctypes.data, o['gt'].ctypes.data,
+                                        o['centroid'].ctypes.data, o['rotation'].ctypes.data)
+    assert rc == 0
+    return o
+
+
+def host_clip(fit, pelvis, rotation):
+    """``canonicalize_clip``'s expressions for a GIVEN fp32 rotation (the cases its heading rule cannot reach), float64."""
+    fit, pel, R = np.asarray(fit, np.float64), np.asarray(pelvis, np.float64), np.asarray(rotation, np.float32)
+    un = Rotation.from_matrix(R)
+    cen = pel[0]
+    t_rel, p_rel = fit[:, 3:6] - cen, pel - cen
+    p0 = p_rel - t_rel
+    R64 = R.astype(np.float64)
+    return dict(root=(un * Rotation.from_rotvec(fit[:, :3])).as_rotvec(), trans=(t_rel + p0) @ R64.T - p0, obj_angles=(un * Rotation.from_rotvec(fit[:, 6:9])).as_rotvec(),
+                obj_trans=(fit[:, 9:12] - cen) @ R64.T, pelvis=p_rel @ R64.T)
+
+
+def etl_sequence():
+    z = np.load(os.path.join(ROOT, 'tests', 'golden', 'etl.npz'))
+    sel = z['sel']
+    F = int(sel.max()) + 1
+
+    def full(a):
+        out = np.zeros((F,) + a.shape[1:], a.dtype)
+        out[sel] = a
+        return out
+    pos = {int(f): i for i, f in enumerate(sel)}
+    cuts_o, cuts_h = np.cumsum(z['obj_contact_n'])[:-1], np.cumsum(z['human_contact_n'])[:-1]
+    per_frame = lambda parts: [parts[pos[i]] if i in pos else np.zeros(0, np.int64) for i in range(F)]
+    seq = dict(poses=full(z['poses']), betas=full(z['betas']), trans=full(z['trans']), obj_angles=full(z['obj_angles']), obj_trans=full(z['obj_trans']),
+               obj_points=z['obj_points6'], obj_contact_label=per_frame(np.split(z['obj_contact_idx'], cuts_o)),
+               contact_label=per_frame(np.split(z['human_contact_idx'], cuts_h)), ground_joint_label=full(z['foot_label']).astype(np.int64),
+               gender='male', obj_name='backpack', seq_name='Date01_Sub01_backpack_back')
+    return z, seq, (full(z['pelvis']), full(z['left_foot']), full(z['right_foot']))
+
+
+def fit_rows(seq, idx):
+    return np.concatenate([np.asarray(seq[k], np.float64)[idx].reshape(len(idx), -1)[:, :3] for k in ('poses', 'trans', 'obj_angles', 'obj_trans')], axis=1)
+
+
+def test_clip_canon_host_instance_matches_canonicalize_clip_on_the_fixture():
+    """The three etl.npz windows: rotation vectors and translations within the 1e-6 gate of ``canonicalize_clip`` (and of the reference's recorded outputs); the
+    composed rotations stay >= 1e-3 away from pi on the host, so that no branch of the conversion is decided by rounding."""
+    z, seq, (pelvis, _, _) = etl_sequence()
+    for w, s0 in enumerate(z['starts']):
+        idx = int(s0) + np.arange(35)
+        c = D.canonicalize_clip(seq, pelvis, int(s0), 10, 25)
+        o = debug_canon(fit_rows(seq, idx), pelvis[idx], seq['poses'][idx])
+        for ours, ref, rec in (('root', c['pose'][:, :3], z['pose_%d' % w][:, :3]), ('trans', c['trans'], z['trans_%d' % w]), ('obj_angles', c['obj_angles'], z['angle_%d' % w]),
+                               ('obj_trans', c['obj_trans'], z['otrans_%d' % w]), ('pelvis', c['pelvis'], z['pelvis_%d' % w])):
+            gate(o[ours], ref)
+            gate(o[ours], rec)
+        assert np.allclose(o['centroid'], c['centroid']) and np.allclose(o['rotation'], c['rotation'])
+        for rv in (c['pose'][:, :3], c['obj_angles']):
+            ang = np.linalg.norm(np.asarray(rv, np.float64), axis=1)
+            assert (np.pi - ang).min() >= 1e-3 and ang.min() > 1e-3
+
+
+def yaw_frame(yaw):
+    """A first frame whose heading is ``yaw`` about y (plus a tilt that the heading rule ignores)."""
+    return (Rotation.from_euler('y', yaw) * Rotation.from_euler('x', 0.3)).as_rotvec()
+
+
+def test_clip_canon_host_instance_takes_every_scipy_branch():
+    """64 random rotations per branch of scipy's route: composed angle < 1e-3 (and an input angle < 1e-3), composed angle in (pi - 0.05, pi), composed w < 0,
+    and each of from_matrix's four cases (largest diagonal entry 0 / 1 / 2, trace) through ``rotation_override``.  Same gate, against scipy on float64."""
+    rs = np.random.RandomState(42)
+    n = 64
+    unit = lambda m: m / np.linalg.norm(m, axis=1, keepdims=True)
+
+    def clip_for(target, yaw):
+        """65 frames: frame 0 fixes the heading; frames 1.. have root / object rotations ``R^-1 target`` so that the composition lands on ``target``."""
+        root0 = yaw_frame(yaw)
+        G = Rotation.from_rotvec(root0).as_matrix()
+        c, s = G[0, 0] / np.hypot(G[0, 0], G[2, 0]), G[2, 0] / np.hypot(G[0, 0], G[2, 0])
+        un = Rotation.from_matrix(np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]]).T)
+        aa = (un.inv() * target).as_rotvec()
+        fit = np.zeros((n + 1, 12))
+        fit[0, :3], fit[1:, :3], fit[1:, 6:9] = root0, aa, aa[::-1]
+        fit[:, 3:6], fit[:, 9:12] = rs.uniform(-2, 2, (n + 1, 3)), rs.uniform(-2, 2, (n + 1, 3))
+        pelvis = np.float32(fit[:, 3:6] + rs.uniform(-0.3, 0.3, (n + 1, 3)))
+        pose = np.float32(rs.uniform(-1, 1, (n + 1, 156)))
+        pose[:, :3] = fit[:, :3]
+        fit[:, :3] = pose[:, :3]                                               # poses are fp32 on disk
+        return fit, pelvis, pose
+
+    def check(fit, pelvis, pose, want_angle=None, want_w_neg=False):
+        seq = dict(poses=pose.copy(), betas=np.zeros((n + 1, 10), np.float32), trans=fit[:, 3:6], obj_angles=fit[:, 6:9], obj_trans=fit[:, 9:12])
+        c = D.canonicalize_clip(seq, pelvis, 0, 1, n)
+        o = debug_canon(fit, pelvis, pose)
+        for ours, ref in (('root', c['pose'][:, :3]), ('trans', c['trans']), ('obj_angles', c['obj_angles']), ('obj_trans', c['obj_trans']), ('pelvis', c['pelvis'])):
+            gate(o[ours], ref)
+        assert np.allclose(o['rotation'], c['rotation']) and np.allclose(o['centroid'], c['centroid'])
+        ang = np.linalg.norm(np.asarray(c['pose'][1:, :3], np.float64), axis=1)
+        if want_angle is not None:
+            assert want_angle(ang).all(), ang
+        if want_w_neg:
+            un = Rotation.from_matrix(c['rotation'])
+            q = (un * Rotation.from_rotvec(fit[1:, :3])).as_quat()            # scipy hands out the composed quaternion as it is (w of either sign)
+            raw = _compose_w(un.as_quat(), Rotation.from_rotvec(fit[1:, :3]).as_quat())
+            assert (raw < 0).sum() >= n // 2, (raw < 0).sum()
+        # the gt rows of root and object are the first two rows of the composed matrices
+        for rows, rv in ((slice(0, 6), c['pose'][:, :3]), (slice(135, 141), c['obj_angles'])):
+            m = Rotation.from_rotvec(np.asarray(rv, np.float64)).as_matrix()[:, :2, :].reshape(-1, 6)
+            assert np.abs(o['gt'][rows].T - m).max() < 5e-6                    # (through the fp32-rounded rotation vector of the host: coarse; test 7 is the tight one)
+
+    # composed angle < 1e-3 (as_rotvec's series), with yaw so that from_matrix takes the trace case and the m11 case
+    for yaw in (0.4, 2.9):
+        tiny = Rotation.from_rotvec(unit(rs.standard_normal((n, 3))) * rs.uniform(1e-7, 9e-4, (n, 1)))
+        check(*clip_for(tiny, yaw), want_angle=lambda a: a < 1e-3)
+    # input angle < 1e-3 (from_rotvec's series): heading ~0, tiny inputs
+    fit, pelvis, pose = clip_for(Rotation.identity(n), 0.0)
+    small = np.float32(unit(rs.standard_normal((n, 3))) * rs.uniform(1e-6, 9e-4, (n, 1)))
+    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = small, small, small[::-1] * 0.5
+    check(fit, pelvis, pose)
+    # composed angle in (pi - 0.05, pi)
+    near_pi = Rotation.from_rotvec(unit(rs.standard_normal((n, 3))) * rs.uniform(np.pi - 0.05, np.pi - 1e-3, (n, 1)))
+    for yaw in (-1.1, 2.6):
+        check(*clip_for(near_pi, yaw), want_angle=lambda a: (a > np.pi - 0.05) & (a < np.pi))
+    # composed w < 0: a large yaw removed from large rotations about (nearly) the same axis
+    big = Rotation.from_rotvec((unit(np.array([[0.0, 1.0, 0.0]]) + 0.2 * rs.standard_normal((n, 3)))) * rs.uniform(2.4, 3.1, (n, 1)))
+    fit, pelvis, pose = clip_for(Rotation.identity(n), -2.7)
+    aa = np.float32(big.as_rotvec())
+    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = aa, aa, aa[::-1]
+    check(fit, pelvis, pose, want_w_neg=True)
+    # from_matrix: each of the four cases, any rotation as `rotation`
+    seen = set()
+    for case in range(4):
+        mats = []
+        while len(mats) < n:
+            m = np.float32(Rotation.random(random_state=rs).as_matrix())
+            if int(np.argmax([m[0, 0], m[1, 1], m[2, 2], m[0, 0] + m[1, 1] + m[2, 2]])) == case:
+                mats.append(m)
+        seen.add(case)
+        for m in mats:
+            T = 2
+            fit = np.concatenate([rs.uniform(-1.5, 1.5, (T, 3)), rs.uniform(-2, 2, (T, 3)), rs.uniform(-1.5, 1.5, (T, 3)), rs.uniform(-2, 2, (T, 3))], axis=1)
+            pelvis = np.float32(fit[:, 3:6] + rs.uniform(-0.3, 0.3, (T, 3)))
+            pose = np.float32(rs.uniform(-1, 1, (T, 156)))
+            fit[:, :3] = pose[:, :3]
+            o, h = debug_canon(fit, pelvis, pose, rotation=m), host_clip(fit, pelvis, m)
+            for k in h:
+                gate(o[k], h[k])
+            assert np.array_equal(o['rotation'], m)
+    assert seen == {0, 1, 2, 3}
+
+
+def _compose_w(p, q):
+    """w of the Hamilton product p * q, quaternions (x, y, z, w) [n,4] / [4]: before scipy's sign handling in as_rotvec."""
+    p = np.broadcast_to(p, q.shape)
+    return p[:, 3] * q[:, 3] - (p[:, :3] * q[:, :3]).sum(1)
+
+
+def test_clip_entries_are_declared_typed_and_exported():
+    from tests.denoiser_train_helpers import check_new_symbols
+    check_new_symbols({
+        'interdiff_clip_batch': 'const idf_clip_set *cs, const int32_t *clips, int32_t B, int32_t T, int32_t sample_rate, const idf_clip_batch *out, void *stream',
+        'interdiff_clip_body_records': 'const idf_clip_set *cs, const int32_t *clips, int32_t B, int32_t T, int32_t sample_rate, const float *verts, '
+                                       'const float *normals, const int32_t *frame_map, int64_t n_frames, float *human_verts, float *markers, uint8_t *contact_label, void *stream',
+        'interdiff_debug_clip_canon': 'const double *fit, const float *pelvis, const float *pose, int32_t T, const float *rotation_override, float *root, float *trans, '
+                                      'float *obj_angle, float *obj_trans, float *pelvis_out, float *gt, float *centroid, float *rotation'})
+
+
+# ------------------------------------------------------------------------------------------------------------------------ GPU
+@pytest.mark.gpu
+def test_etl_fixture_through_the_device_clip_set_matches_the_reference_dataset():
+    """5: tests/golden/etl.npz (the reference's own ``__getitem__`` on three windows of the shipped sequence) through ``DeviceClipSet(joints=...)``: B = 3, T = 35, P = 48."""
+    from interdiff_amd.dataset import DeviceClipSet
+    z, seq, joints = etl_sequence()
+    cs = DeviceClipSet([seq], None, 10, 25, device=DEV, joints=[joints])
+    starts = [int(s) for s in z['starts']]
+    bt = cs.assemble([0, 0, 0], starts, body=False)
+    assert 'human_verts' not in bt and bt['start_frame'] == starts and bt['seq_name'] == [seq['seq_name']] * 3 and bt['gender'] == ['male'] * 3 and bt['obj_name'] == ['backpack'] * 3
+    pose = torch.cat([bt['body_pose'], bt['hand_pose']], dim=2).cpu().numpy()
+    for w in range(3):
+        for got, ref in ((pose[:, w], 'pose_%d'), (bt['body_trans'][:, w], 'trans_%d'), (bt['obj_angles'][:, w], 'angle_%d'), (bt['obj_trans'][:, w], 'otrans_%d'),
+                         (bt['pelvis'][:, w], 'pelvis_%d')):
+            gate(got.cpu().numpy() if isinstance(got, torch.Tensor) else got, z[ref % w])
+        assert np.allclose(bt['centroid'][w].cpu().numpy(), z['centroid_%d' % w]) and np.allclose(bt['rotation'][w].cpu().numpy(), z['rotation_%d' % w])
+        assert np.array_equal(bt['ground_joint_label'][:, w].cpu().numpy(), z['ground_%d' % w])
+        lab = bt['contact_label'][:, w].cpu().numpy()
+        assert lab.dtype == np.uint8 and lab.shape == (35, 6890) and set(np.unique(lab)) <= {0, 1}
+        assert np.array_equal(lab.sum(1), z['contact_count_%d' % w])
+        assert np.array_equal(np.array([int(np.nonzero(r)[0][0]) if r.any() else -1 for r in lab]), z['contact_first_%d' % w])
+    assert torch.equal(bt['beta'][:, 0].cpu(), torch.from_numpy(seq['betas'][starts[0]:starts[0] + 35]))
+    assert torch.equal(bt['obj_points6'].cpu(), torch.from_numpy(z['obj_points6'])[None].expand(3, -1, -1)) and torch.equal(bt['obj_points'], bt['obj_points6'][..., :3])
+    assert bt['obj_angle'] is bt['obj_angles'] and all(v.is_contiguous() for v in bt.values() if isinstance(v, torch.Tensor))
+
+
+PAST, FUT, P_SYN = 4, 8, 64
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_set():
+    """Two sequences of different gender on two synthetic torus body models: F = 12 and 20, P = 64.  Contact lists are random index lists (an empty one, one
+    that names a vertex twice).  -> (sequences, layers)"""
+    from tests import contact_labels_oracle as co
+    from interdiff_amd import synthetic as syn
+    from interdiff_amd.smpl import SMPL_Layer
+    tv, tf = co.torus()
+    layers = {}
+    for gender, seed in (('male', 7), ('female', 8)):
+        model = syn.smplh_model(seed, coherent=True)
+        model['v_template'], model['faces'] = np.float32(tv * (1.0 if gender == 'male' else 0.93)), tf
+        layers[gender] = SMPL_Layer(model, device=DEV)
+    rs = np.random.RandomState(77)
+    seqs = []
+    for name, gender, F in (('Date01_Sub01_box_a', 'male', 12), ('Date02_Sub02_box_b', 'female', 20)):
+        poses = np.float32(rs.uniform(-0.05, 0.05, (F, 156)))
+        poses[:, :3] = np.float32(rs.uniform(-1.2, 1.2, (F, 3)))
+        trans = np.float32(rs.uniform(-0.3, 0.3, (F, 3)) + np.linspace(0, 0.02, F)[:, None])
+        if gender == 'female':
+            trans[5:9] = trans[5]                                            # a stretch where the feet stand still: ground labels of both kinds
+            poses[5:9] = poses[5]
+        body = [np.sort(rs.choice(6890, rs.randint(0, 300), replace=False)) for _ in range(F)]
+        body[1] = np.zeros(0, np.int64)
+        body[2] = np.array([17, 6889, 17, 0], np.int64)
+        seqs.append(dict(poses=poses, betas=np.float32(rs.uniform(-1, 1, (1, 10)).repeat(F, 0)), trans=trans, obj_angles=rs.uniform(-1.5, 1.5, (F, 3)),
+                         obj_trans=trans.astype(np.float64) + rs.uniform(-0.5, 0.5, (F, 3)), obj_points=np.float32(rs.standard_normal((P_SYN, 6))),
+                         obj_contact_label=[rs.choice(P_SYN, rs.randint(0, 9), replace=False) for _ in range(F)], contact_label=body,
+                         ground_joint_label=np.full(F, 10 if gender == 'male' else 11, np.int64), gender=gender, obj_name='box', seq_name=name))
+    return seqs, layers
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_batch():
+    """The B = 5 batch of test 6 and what the host route makes of the same clips.  Clips: a start at sequence frame 0 (the stored-label branch) for both genders,
+    one sequence three times, its last admissible start (8), mixed genders."""
+    from interdiff_amd.dataset import DeviceClipSet
+    seqs, layers = synthetic_set()
+    cs = DeviceClipSet(seqs, layers, PAST, FUT, device=DEV)
+    ids, starts = [0, 1, 1, 1, 0], [0, 0, 8, 5, 0]
+    bt = cs.assemble(ids, starts)
+    host = host_route(cs, seqs, ids, starts, PAST, FUT, 1)
+    return cs, ids, starts, bt, host
+
+
+def host_route(cs, seqs, ids, starts, past, fut, rate):
+    """``canonicalize_clip`` + ``clip_labels`` per clip on the set's own joints (downloaded): -> (clips, labels)."""
+    jt = cs.t['joints'].cpu().numpy().reshape(-1, 3, 3)
+    clips, labels = [], []
+    for k, s in zip(ids, starts):
+        j = jt[cs.seq_off[k]:cs.seq_off[k + 1]]
+        c = D.canonicalize_clip(seqs[k], j[:, 0], s, past, fut, rate)
+        clips.append(c)
+        labels.append(D.clip_labels(seqs[k], c, j[:, 1], j[:, 2], s, past, fut, rate))
+    return clips, labels
+
+
+def check_against_host(bt, clips, labels, pts6):
+    raw = D.collate_raw(clips, pts6[..., :3], device='cpu')
+    for k in ('body_pose', 'hand_pose', 'body_trans', 'obj_angles', 'obj_trans', 'beta', 'obj_points'):
+        gate(bt[k].cpu().numpy(), raw[k].numpy())
+    for k in ('hand_pose', 'beta', 'obj_points'):
+        assert torch.equal(bt[k].cpu(), raw[k]), k                          # copies
+    assert torch.equal(bt['body_pose'][..., 3:].cpu(), raw['body_pose'][..., 3:])
+    gate(bt['pelvis'].cpu().numpy(), np.stack([c['pelvis'] for c in clips], 1))
+    assert np.allclose(bt['centroid'].cpu().numpy(), np.stack([c['centroid'] for c in clips])) and np.allclose(bt['rotation'].cpu().numpy(), np.stack([c['rotation'] for c in clips]))
+    assert np.array_equal(bt['ground_joint_label'].cpu().numpy(), np.stack([l['ground_joint_label'] for l in labels], 1))
+    assert np.array_equal(bt['contact_label'].cpu().numpy().astype(bool), np.stack([l['contact_label'] for l in labels], 1))
+    assert np.array_equal(bt['obj_points6'].cpu().numpy(), pts6)
+
+
+@pytest.mark.gpu
+def test_synthetic_batch_matches_the_host_route_and_body_records_bit_for_bit():
+    """6: raw fields against ``canonicalize_clip`` + ``collate_raw`` at the 1e-6 gate, labels against ``clip_labels`` exactly, ``human_verts`` / ``markers`` bit-equal
+    to ``body_records`` (per gender, as ``assemble`` runs the body model) fed the device's own pose, beta, translation and labels.  ``sample_rate=2`` cannot hold
+    past 4 + future 8 inside 20 frames (23 are needed), so that case runs past 4 + future 5 on the longer sequence: starts 0 and 3, the last admissible one."""
+    from interdiff_amd import correction_losses as cl
+    from interdiff_amd.dataset import DeviceClipSet
+    seqs, layers = synthetic_set()
+    cs, ids, starts, bt, (clips, labels) = synthetic_batch()
+    pts6 = np.stack([np.float32(seqs[k]['obj_points']) for k in ids])
+    check_against_host(bt, clips, labels, pts6)
+    g = bt['ground_joint_label'].cpu().numpy()
+    assert g[0, 0].tolist() == [1, 0] and g[0, 1].tolist() == [0, 1] and g[:, 3].sum() > 0 and (g == 0).any()      # both label branches, still and moving feet
+    T, B = PAST + FUT, len(ids)
+    assert tuple(bt['human_verts'].shape) == (T, B, 6890, 7) and tuple(bt['markers'].shape) == (T, B, 67, 7) and tuple(bt['gt'].shape) == (B, 1, 144, T)
+    pose = torch.cat([bt['body_pose'], bt['hand_pose']], dim=2)
+    for gender in ('male', 'female'):
+        cols = [b for b in range(B) if bt['gender'][b] == gender]
+        hv, mk = cl.body_records(layers[gender], pose[:, cols].contiguous(), bt['beta'][:, cols].contiguous(), bt['body_trans'][:, cols].contiguous(),
+                                 bt['contact_label'][:, cols].contiguous())
+        assert torch.equal(bt['human_verts'][:, cols], hv) and torch.equal(bt['markers'][:, cols], mk), gender
+    assert bt['human_verts'][2, 0, 17, 6] == 1 and bt['human_verts'][1, 0, :, 6].sum() == 0                     # the doubly named vertex; the empty list
+    # sample_rate = 2
+    cs2 = DeviceClipSet(seqs, layers, PAST, 5, sample_rate=2, device=DEV)
+    bt2 = cs2.assemble([1, 1], [0, 3], body=False)
+    c2, l2 = host_route(cs2, seqs, [1, 1], [0, 3], PAST, 5, 2)
+    check_against_host(bt2, c2, l2, np.stack([np.float32(seqs[1]['obj_points'])] * 2))
+    with pytest.raises(ValueError):
+        cs2.assemble([1], [4])
+
+
+def gt_fp64(clips):
+    """The token of model/diffusion_smpl.py:212-214 evaluated in float64 from float64 host clips -> [B,144,T]."""
+    out = []
+    for c in clips:
+        pose = np.asarray(c['pose'], np.float64)[:, :66].reshape(-1, 22, 3)
+        body6 = Rotation.from_rotvec(pose.reshape(-1, 3)).as_matrix()[:, :2, :].reshape(pose.shape[0], 132)
+        obj6 = Rotation.from_rotvec(np.asarray(c['obj_angles'], np.float64)).as_matrix()[:, :2, :].reshape(-1, 6)
+        out.append(np.concatenate([body6, np.asarray(c['trans'], np.float64), obj6, np.asarray(c['obj_trans'], np.float64)], axis=1).T)
+    return np.stack(out)
+
+
+@pytest.mark.gpu
+def test_gt_token_is_as_close_to_fp64_as_the_existing_route():
+    """7: e_dev = the device token's largest distance from the float64 evaluation of the float64 host clips; e_old = the same for the existing route (``collate_raw``
+    -> ``MDM._get_embeddings``).  Required: e_dev <= 2 max(e_old, 2.4e-7) (two fp32 ulps at 1).  The host clips keep the root orientation in the fp32 pose array, so
+    their own float64 token carries that rounding; measured on the MI355X (this batch): e_dev 6.6e-8, e_old 2.7e-7."""
+    from interdiff_amd import synthetic as syn
+    from interdiff_amd.mdm import MDM
+    seqs, _ = synthetic_set()
+    cs, ids, starts, bt, (clips, _) = synthetic_batch()
+    ref = gt_fp64(clips)
+    e_dev = float(np.abs(bt['gt'][:, 0].cpu().numpy().astype(np.float64) - ref).max())
+    model = MDM({k: torch.from_numpy(v) for k, v in syn.mdm_state_dict(233).items()}, device=DEV)
+    raw = D.collate_raw(clips, np.stack([np.float32(seqs[k]['obj_points'][:, :3]) for k in ids]), device=DEV)
+    _, gt_old = model._get_embeddings(raw['body_pose'], raw['body_trans'], raw['obj_angles'], raw['obj_trans'], raw['obj_points'], PAST)
+    e_old = float(np.abs(gt_old.permute(1, 2, 0).cpu().numpy().astype(np.float64) - ref).max())
+    print('gt token: e_dev %.3e  e_old %.3e' % (e_dev, e_old))
+    assert e_dev <= 2 * max(e_old, 2.4e-7), (e_dev, e_old)
+
+
+@pytest.mark.gpu
+def test_assemble_contract():
+    """8: same bits twice; a permuted (seq_ids, starts) gives the permuted outputs; B = 1 and T = 2; bad input raises ValueError on the host."""
+    from interdiff_amd.dataset import DeviceClipSet
+    seqs, layers = synthetic_set()
+    cs, ids, starts, bt, _ = synthetic_batch()
+    again = cs.assemble(ids, starts)
+    tensors = [k for k, v in bt.items() if isinstance(v, torch.Tensor)]
+    assert all(torch.equal(bt[k], again[k]) for k in tensors)
+    perm = [3, 0, 4, 2, 1]
+    pb = cs.assemble([ids[i] for i in perm], [starts[i] for i in perm])
+    for k in tensors:
+        dim = 0 if bt[k].shape[0] == len(ids) and k in ('gt', 'centroid', 'rotation', 'obj_points', 'obj_points6') else 1
+        assert torch.equal(pb[k], bt[k].index_select(dim, torch.tensor(perm, device=DEV))), k
+    assert pb['start_frame'] == [starts[i] for i in perm] and pb['gender'] == [bt['gender'][i] for i in perm]
+    one = DeviceClipSet(seqs, layers, 1, 1, device=DEV).assemble([1], [18])                  # B = 1, T = 2, the last admissible start
+    assert tuple(one['gt'].shape) == (1, 1, 144, 2) and tuple(one['human_verts'].shape) == (2, 1, 6890, 7) and bool(torch.isfinite(one['human_verts']).all())
+    assert float(one['pelvis'][0].abs().max()) < 1e-6
+    for bad_ids, bad_starts in (([1], [9]), ([0], [1]), ([2], [0]), ([-1], [0]), ([1], [-1]), ([0, 1], [0]), ([], []), ([0.0], [0]),
+                                (torch.tensor([0]), torch.tensor([0]))):
+        with pytest.raises(ValueError):
+            cs.assemble(bad_ids, bad_starts)
+    uneven = [dict(seqs[0]), dict(seqs[1], obj_points=np.zeros((P_SYN + 1, 6), np.float32))]
+    with pytest.raises(ValueError, match='same P'):
+        DeviceClipSet(uneven, layers, PAST, FUT, device=DEV)
+    body = list(seqs[0]['contact_label'])
+    body[3] = np.array([5, 6890], np.int64)
+    with pytest.raises(ValueError, match='contact_label'):
+        DeviceClipSet([dict(seqs[0], contact_label=body)], layers, PAST, FUT, device=DEV)
+
+
+@pytest.mark.gpu
+def test_trainers_take_the_batch_as_it_comes_and_fit_drives_them(tmp_path):
+    """9: one ``training_step`` each with a finite loss -- ``DenoiserTrainer(train_encoder, train_pointnet)``, ``CorrectionFineTuner`` at epoch 1 and
+    ``CorrectionTrainer`` at epoch 10 (geometry terms on: reads ``obj_points`` and ``human_verts``) -- then ``fit`` for 2 epochs of 2 batches with each ready
+    ``validate`` helper: both checkpoint files, and ``best.pt`` loaded into a fresh trainer gives its ``state_dict()`` back bit for bit."""
+    from interdiff_amd import synthetic as syn, fit as F
+    from interdiff_amd.dataset import DeviceClipSet
+    from interdiff_amd.mdm_train import DenoiserTrainer
+    from interdiff_amd.correction_finetune import CorrectionFineTuner
+    from interdiff_amd.correction_train import CorrectionTrainer
+    from interdiff_amd.diffusion import create_gaussian_diffusion
+    from tests import fixtures as fx
+    seqs, layers = synthetic_set()
+    past, fut = 10, 2
+    T = past + fut
+    cs = DeviceClipSet(seqs, layers, past, fut, device=DEV)
+    bt = cs.assemble([0, 1, 1], [0, 0, 8])
+    msd = {k: torch.from_numpy(v) for k, v in syn.mdm_state_dict(233).items()}
+    osd = fx.objproj_weights()
+    den = DenoiserTrainer(msd, device=DEV, past_len=past, train_encoder=True, train_pointnet=True)
+    loss = den.training_step(bt, seed=3)[0]
+    assert tuple(loss.shape) == (3,) and bool(torch.isfinite(loss).all())
+    ft = CorrectionFineTuner(osd, T=T, past_len=past, device=DEV)
+    assert bool(torch.isfinite(ft.training_step(bt, current_epoch=1)))
+    ct = CorrectionTrainer(osd, T=T, past_len=past, seed=5, device=DEV)
+    assert bool(torch.isfinite(ct.training_step(bt, 10)))
+    # fit: 4 train entries -> 2 batches of 2; the test split is sequence-name based, so validation reuses the training sequences through a test-mode index
+    names, counts = [s['seq_name'] for s in seqs], cs.frame_counts
+    idx = ClipIndex(names + names, counts + counts, 'train', past, fut)
+    assert len(idx) == 4
+    idx.entries = [(k % 2, off, bias) for k, off, bias in idx.entries]
+    vidx = ClipIndex(['Date03_' + n for n in names], counts, 'test', past, fut)
+    short = create_gaussian_diffusion('cosine', 1000, '4')                      # a 4-step respaced schedule keeps the denoiser's validation sample within seconds
+    runs = ((lambda: DenoiserTrainer(msd, device=DEV, past_len=past, train_encoder=True), None, F.denoiser_validate(short, past_len=past, seed=1)),
+            (lambda: CorrectionFineTuner(osd, T=T, past_len=past, device=DEV), F.correction_step, F.correction_validate()))
+    for k, (make, step, validate) in enumerate(runs):
+        d = str(tmp_path / ('run%d' % k))
+        tr = make()
+        out = F.fit(tr, cs, idx, batch_size=2, max_epochs=2, seed=9, step=step, validate=validate, val_index=vidx, check_val_every_n_epoch=1, ckpt_dir=d)
+        assert out['steps'] == 4 and len(out['val']) == 2 and all(np.isfinite(v) for _, v in out['val']) and sorted(os.listdir(d)) == ['best.pt', 'last.pt']
+        best = torch.load(os.path.join(d, 'best.pt'))
+        fresh = type(tr)(best, **({'device': DEV, 'past_len': past, 'train_encoder': True} if k == 0 else {'T': T, 'past_len': past, 'device': DEV}))
+        back = fresh.state_dict()
+        assert sorted(back) == sorted(best) and all(torch.equal(back[n].cpu(), best[n].cpu()) for n in best)
+        last = torch.load(os.path.join(d, 'last.pt'))
+        now = tr.state_dict()
+        assert all(torch.equal(now[n].cpu(), last[n].cpu()) for n in last)
