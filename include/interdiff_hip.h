@@ -1228,6 +1228,48 @@ int interdiff_debug_clip_canon(const double *fit, const float *pelvis, const flo
                                float *trans, float *obj_angle, float *obj_trans, float *pelvis_out, float *gt, float *centroid, float *rotation);
 
 /* ------------------------------------------------------------------------------------
+ * The skeleton-mode training set on the device (csrc/skeleton_clip_batch.hip; interdiff_amd/skeleton_dataset.py SkeletonClipSet).
+ * Additive entries: interdiff_abi_version() stays what it was.
+ *
+ *  interdiff_skeleton_video_prepare   data/dataset_skeleton.py:40-65 (recover_init_obj, get_consistent_poses), :85-104 (check_sequences) and the
+ *      down-sampling of :148-151 for every video of a set in ONE launch, one workgroup per video.  All pointers DEVICE.  Inputs: the raw float64
+ *      arrays of the pickles, concatenated over the videos' frames (F = sum of the frame counts): skel [F][J][3], obj [F][P][3], pose [F][7]
+ *      (translation | quaternion xyzw), contact [F]; seq_off int64 [n_video + 1] the first frame of every video, row_off int64 [n_video + 1] its first
+ *      row, with rows = ceil(frames / stride) per video (a video whose two table entries disagree is skipped).  Outputs:
+ *      table fp32 [rows total][3 J + 3 P + 7] = body | object | pose of the frames stride * r, the quaternion multiplied by the sign s of
+ *          get_consistent_poses: s_0 = 1, s_{i+1} = s_i * (q_i . q_{i+1} < 0 ? -1 : 1) on the raw quaternions in double (a tie keeps the sign, as the
+ *          reference's strict > does), a prefix parity over ALL frames.  Every value is rounded from float64 once.  Frames that are no multiple of
+ *          stride are read for the quaternion and the contact value only;
+ *      zero_pose_obj fp32 [n_video][P][3]: recover_init_obj on frame 0 (the quaternion normalised, inverted, as a matrix) in double, rounded once;
+ *      report double [n_video][3] = the discrepancy of :98-99 (mean over rows x P of |t + R(q) zero_pose - obj|), the check sum of :93 (the signed sum
+ *          of |q| - 1 over the rows), the sum of contact over all frames -- each summed in a fixed order (256 strided partial sums, one tree);
+ *      row_contact double [rows total]: contact at the frames stride * r;  signs int8 [F] (or null): s of every frame.
+ *      P <= 64.
+ *  interdiff_debug_skeleton_video_prepare   HOST instance of the same per-video code for ONE video of F frames (host pointers): the same operations in
+ *      the same order, compiled without contraction on both sides, so the outputs are the device's bit for bit.
+ *  interdiff_skeleton_window_batch   B windows in ONE launch.  idf_skel_clip_set: what prepare wrote (row_off, table, zero_pose_obj; DEVICE).
+ *      clips int32 [2][B] (DEVICE) = video | first row; window b holds the T <= 128 consecutive rows from first row on.  Writes body [B,T,J,3],
+ *      obj [B,T,P,3], pose [B,T,7], zero_pose_obj [B,P,3] -- the collated tuple of data/dataset_skeleton.py:157-158 -- and the token
+ *      gt [B,1,3J+3P+7,T] of model/diffusion_skeleton.py:206 as train_diffusion_skeleton.py permutes it.  The caller checks that the rows lie inside
+ *      the video; a window whose rows do not is skipped (nothing of it is written), never dereferenced.
+ *  Returns: IDF_OK; IDF_E_INVAL (null pointer, a count <= 0, P > 64, T > 128, a T x (3J+3P+7) tile beyond 64 KiB of LDS); IDF_E_LAUNCH.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_video, J, P, reserved;
+    const int64_t *row_off;
+    const float *table, *zero_pose_obj;
+} idf_skel_clip_set;
+typedef struct {
+    float *body, *obj, *pose, *zero_pose_obj, *gt;
+} idf_skel_window_batch;
+int interdiff_skeleton_video_prepare(const double *skel, const double *obj, const double *pose, const double *contact, const int64_t *seq_off,
+                                     const int64_t *row_off, int32_t n_video, int32_t J, int32_t P, int32_t stride, float *table, float *zero_pose_obj,
+                                     double *report, double *row_contact, int8_t *signs, void *stream);
+int interdiff_debug_skeleton_video_prepare(const double *skel, const double *obj, const double *pose, const double *contact, int64_t F, int32_t J, int32_t P,
+                                           int32_t stride, float *table, float *zero_pose_obj, double *report, double *row_contact, int8_t *signs);
+int interdiff_skeleton_window_batch(const idf_skel_clip_set *cs, const int32_t *clips, int32_t B, int32_t T, const idf_skel_window_batch *out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Live per-kernel timing for bench.py's `roofline` block (not on the product path).
  * Between profile_begin and profile_end every kernel launch of the library is preceded by a
  * hipEventRecord on its stream; profile_end synchronises and attributes the time between

@@ -116,7 +116,19 @@ class ClipBatch(C.Structure):
     _fields_ = [(k, vp) for k in CLIP_BATCH_FIELDS]
 
 
+class SkelClipSet(C.Structure):
+    _fields_ = [('n_video', i32), ('J', i32), ('P', i32), ('reserved', i32), ('row_off', vp), ('table', vp), ('zero_pose_obj', vp)]
+
+
+SKEL_WINDOW_FIELDS = ('body', 'obj', 'pose', 'zero_pose_obj', 'gt')
+
+
+class SkelWindowBatch(C.Structure):
+    _fields_ = [(k, vp) for k in SKEL_WINDOW_FIELDS]
+
+
 CLIP_MAX_T = 128
+SKEL_SET_MAX_P, SKEL_WINDOW_LDS = 64, 64 * 1024              # csrc/skeleton_clip_batch.hip: SKV_MAX_P, SKW_LDS_BYTES
 SKEL_PLAIN, SKEL_PREDGT = 0, 1                            # idf_skel_view.style (IDF_SKEL_*)
 SKEL_REC_INTS, SKEL_MAX_REC, SKEL_MAX_WIRES, SKEL_WD_MAX, SKEL_TILE = 8, 128, 40, 1024, 16
 RMESH_SCENE_SPACE, RMESH_VERTEX_RGB = 1, 2                 # idf_render_mesh.flags (IDF_RMESH_*)
@@ -250,6 +262,9 @@ _SIGS = {
     'interdiff_clip_batch': (C.c_int, [C.POINTER(ClipSet), vp, i32, i32, i32, C.POINTER(ClipBatch), vp]),
     'interdiff_clip_body_records': (C.c_int, [C.POINTER(ClipSet), vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]),
     'interdiff_debug_clip_canon': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'interdiff_skeleton_video_prepare': (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'interdiff_debug_skeleton_video_prepare': (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    'interdiff_skeleton_window_batch': (C.c_int, [C.POINTER(SkelClipSet), vp, i32, i32, C.POINTER(SkelWindowBatch), vp]),
     'interdiff_debug_lds_sentinel':(C.c_int, [vp, i32, i32, vp]),
     'interdiff_exclusive_cu_report': (C.c_int, [C.c_char_p, i32]),
     'interdiff_debug_deny_exclusive': (C.c_int, [C.c_char_p]),

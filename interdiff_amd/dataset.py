@@ -12,7 +12,7 @@ host route this one is tested against.
 
 NOT built, on purpose: the per-frame posed object cloud ``frames[t]['obj_points']`` [T,B,P,7] (:155-165).  No model, loss or trainer reads it -- they read the
 top-level [B,P,6] cloud; ``data.clip_labels`` still produces it on the host.  The object contact lists are uploaded (CSR) for whoever builds it.  The skeleton
-dataset (data/dataset_skeleton.py) is not part of this module.
+dataset (data/dataset_skeleton.py) is interdiff_amd/skeleton_dataset.py.
 """
 import ctypes as C
 import numpy as np

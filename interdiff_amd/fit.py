@@ -1,9 +1,11 @@
-"""The epoch loop that drives a trainer from a ``DeviceClipSet``: what ``DataLoader(shuffle=True, drop_last=True)`` + ``Trainer.fit`` with
+"""The epoch loop that drives a trainer from a ``DeviceClipSet`` or a ``skeleton_dataset.SkeletonClipSet``: what ``DataLoader(shuffle=True, drop_last=True)`` + ``Trainer.fit`` with
 ``ModelCheckpoint(monitor='val_loss', save_last=True, save_weights_only=True)`` and ``EarlyStopping(monitor='val_loss', min_delta=0)`` do in
 train_diffusion_smpl.py:612-651 and train_correction_smpl.py.  Host only.  Lightning is not a dependency and nothing here is pinned against it: the loop
 RESTATES those semantics (validation every ``check_val_every_n_epoch`` epochs, lowest value kept as ``best.pt``, the final weights as ``last.pt``, stop after
 ``patience`` validations without improvement).  The shuffle is a seeded numpy permutation per epoch, not torch's sampler stream.  Learning-rate schedules are
-not built (the reference constructs ``ReduceLROnPlateau`` and never returns it from ``configure_optimizers``).
+not built (the reference constructs ``ReduceLROnPlateau`` and never returns it from ``configure_optimizers``).  The skeleton half: ``fit`` takes a
+``SkeletonWindowIndex`` as it takes a ``ClipIndex`` (train_diffusion_skeleton.py / train_correction_skeleton.py); ``skeleton_denoiser_validate`` /
+``skeleton_correction_validate`` are its ``validate``, ``skeleton_evaluate`` is eval_skeleton.py's loop over a test split.
 """
 import os
 import numpy as np
@@ -103,3 +105,53 @@ def correction_validate():
             clips += B
         return total / max(clips, 1)
     return validate
+
+
+def skeleton_denoiser_validate(diffusion, past_len=10, seed=0, **loop_kw):
+    """``validate`` for a ``SkeletonDenoiserTrainer`` over a ``skeleton_dataset.SkeletonClipSet``: ``export_mdm`` -> ``skeleton_losses.validation_step`` (one full
+    sample per batch, scored by the 13-term val_loss), the clip-weighted mean over the batches.  ``diffusion`` / ``loop_kw`` as in ``denoiser_validate``."""
+    from . import skeleton_losses
+
+    def validate(trainer, batches):
+        model = trainer.export_mdm()
+        total, clips = 0.0, 0
+        for batch in batches:
+            B = batch[0].shape[0]
+            total += B * float(skeleton_losses.validation_step(model, diffusion, batch, past_len, seed=seed, **loop_kw)[0])
+            clips += B
+        return total / max(clips, 1)
+    return validate
+
+
+def skeleton_correction_validate():
+    """``validate`` for ``SkeletonTrainer`` / ``SkeletonFineTuner``: ``skeleton.skeleton_validation_step(trainer.predictor, batch)``, the clip-weighted mean."""
+    from . import skeleton
+
+    def validate(trainer, batches):
+        total, clips = 0.0, 0
+        for batch in batches:
+            B = batch[0].shape[0]
+            total += B * float(skeleton.skeleton_validation_step(trainer.predictor, batch)[0])
+            clips += B
+        return total / max(clips, 1)
+    return validate
+
+
+def skeleton_evaluate(model, diffusion, obj_model, clip_set, index, batch_size, seed=None, past_len=10, **loop_kw):
+    """The loop of eval_skeleton.py:145-165 (``sample(t, dataloader, data_size)``) over the windows of ``index`` (a ``SkeletonWindowIndex`` or a ``subset`` of one)
+    in ``clip_set``: batches in index order, the last partial one KEPT (the script's loaders do not drop it); per batch ``skeleton.sample_once_proj`` ->
+    ``skeleton.skeleton_metrics``, every metric times the batch's B, summed, divided by ``len(index)``.  ``obj_model=None``: eval_skeleton_no_correction.py.
+    ``seed``: the sampler's, the same for every batch.  -> dict(mpjpe_h, mpjpe_o, translation_error, rotation_error)."""
+    from . import skeleton
+    if batch_size <= 0 or len(index) == 0:
+        raise ValueError('batch_size > 0 and a non-empty index')
+    entries = [index[i] for i in range(len(index))]
+    total = {}
+    for s in range(0, len(entries), batch_size):
+        part = entries[s:s + batch_size]
+        batch = clip_set.assemble([int(k) for k, _, _ in part], [int(r) for _, r, _ in part])
+        obj_pred, body_pred, pose_pred, obj_gt, body_gt, pose_gt = skeleton.sample_once_proj(batch, model, diffusion, obj_model, seed=seed, past_len=past_len, **loop_kw)
+        metric = skeleton.skeleton_metrics(body_pred, body_gt, obj_pred, obj_gt, pose_pred, pose_gt)
+        for k, v in metric.items():
+            total[k] = total.get(k, 0.0) + len(part) * v
+    return {k: v / len(entries) for k, v in total.items()}
