@@ -7,6 +7,7 @@ import torch
 from oracle import denoiser as od
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
+from tests.mdm_train_oracle import token_shares
 from interdiff_amd.mdm_train import PARAM_NAMES, ENCODER_PARAM_NAMES, FULL_PARAM_NAMES
 
 
@@ -23,32 +24,6 @@ def encode(p, x0, pc, past_len, n_body=135):
 
 
 WK_NAMES = tuple(k for k in FULL_PARAM_NAMES if k.endswith('.wk'))
-
-
-class token_shares:
-    """While active, ``oracle.denoiser.qan_block`` computes what it computes with ``wk[n] + z[b,n,t,c]`` in the place of ``wk[n]``, z a zero leaf per layer: the gradient
-    of z is the share of token (b, t) and channel c in d wk[n] = sum_{b,t,c} d block[t,b,c] o_n[b,t,c], so the sum of the products' magnitudes -- the scale on which that
-    near-cancelling sum is well conditioned (the post-norm LayerNorm behind the block makes d block orthogonal to the row it normalises, so already one token's
-    256 products cancel) -- can be read off autograd.  ``self.z``: {'<layer prefix>.wk': leaf}."""
-
-    def __enter__(self):
-        self.z, self.real = {}, od.qan_block
-
-        def qan_block(x, sd, p, rotary=od.ROTARY_DEFAULT):
-            T, B, D = x.shape
-            q = od.qan_queries(sd, p)
-            nq = q.shape[0]
-            qq = q[None, :, None, :].expand(B, nq, T, D).reshape(B * nq, T, D)
-            xx = x.permute(1, 0, 2)[:, None].expand(B, nq, T, D).reshape(B * nq, T, D)
-            o = od.local_attention(qq, xx, xx, rotary=rotary).reshape(B, nq, T, D)
-            z = torch.zeros(B, nq, T, D, dtype=x.dtype, requires_grad=True)
-            self.z[p + '.wk'] = z
-            return (o * (sd[p + '.wk'][None, :, None, :] + z)).sum(1).permute(1, 0, 2)
-        od.qan_block = qan_block
-        return self
-
-    def __exit__(self, *exc):
-        od.qan_block = self.real
 
 
 def grads(sd, x_t, ts, pc, target, past_len=10, weights=None, dtype=torch.float64, d_pred=None, detach_cond=False):

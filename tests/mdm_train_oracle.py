@@ -37,11 +37,41 @@ def loss_of(pred, target, past_len, weights=None):
     return (stack * w[:, None]).sum(0).mean(), stack
 
 
+WK_NAMES = tuple(k for k in PARAM_NAMES if k.endswith('.wk'))
+
+
+class token_shares:
+    """While active, ``oracle.denoiser.qan_block`` computes what it computes with ``wk[n] + z[b,n,t,c]`` in the place of ``wk[n]``, z a zero leaf per layer: the gradient
+    of z is the share of token (b, t) and channel c in d wk[n] = sum_{b,t,c} d block[t,b,c] o_n[b,t,c], so the sum of the products' magnitudes -- the scale on which that
+    near-cancelling sum is well conditioned (the post-norm LayerNorm behind the block makes d block orthogonal to the row it normalises, so already one token's
+    256 products cancel) -- can be read off autograd.  ``self.z``: {'<layer prefix>.wk': leaf}."""
+
+    def __enter__(self):
+        self.z, self.real = {}, od.qan_block
+
+        def qan_block(x, sd, p, rotary=od.ROTARY_DEFAULT):
+            T, B, D = x.shape
+            q = od.qan_queries(sd, p)
+            nq = q.shape[0]
+            qq = q[None, :, None, :].expand(B, nq, T, D).reshape(B * nq, T, D)
+            xx = x.permute(1, 0, 2)[:, None].expand(B, nq, T, D).reshape(B * nq, T, D)
+            o = od.local_attention(qq, xx, xx, rotary=rotary).reshape(B, nq, T, D)
+            z = torch.zeros(B, nq, T, D, dtype=x.dtype, requires_grad=True)
+            self.z[p + '.wk'] = z
+            return (o * (sd[p + '.wk'][None, :, None, :] + z)).sum(1).permute(1, 0, 2)
+        od.qan_block = qan_block
+        return self
+
+    def __exit__(self, *exc):
+        od.qan_block = self.real
+
+
 def grads(sd, x_t, ts, cond, target, past_len=10, weights=None, dtype=torch.float64, d_pred=None):
     """Autograd of the weighted loss (or of <pred, d_pred> when ``d_pred`` is given) with respect to the 144 tensors and ``cond``.
-    Returns dict(loss, terms [16,B], pred, d_pred, d_cond, grads {name: tensor}), everything in ``dtype``."""
+    Returns dict(loss, terms [16,B], pred, d_pred, d_cond, grads {name: tensor}, wk_scale), everything in ``dtype``; wk_scale
+    {name: max_n sum_{b,t,c} |d block[t,b,c] o_n[b,t,c]|} for the six decoder ``wk`` tensors (``token_shares``)."""
     p = cast(sd, dtype)
-    with torch.enable_grad():                                      # (other test modules switch autograd off process-wide)
+    with torch.enable_grad(), token_shares() as ts_:               # (other test modules switch autograd off process-wide)
         leaves = {k: p[k].clone().requires_grad_(True) for k in PARAM_NAMES}
         p.update(leaves)
         c = cond.to(dtype).clone().requires_grad_(True)
@@ -49,10 +79,13 @@ def grads(sd, x_t, ts, cond, target, past_len=10, weights=None, dtype=torch.floa
         loss, terms = loss_of(pred, target.to(dtype), past_len, weights)
         dp = torch.autograd.grad(loss, pred, retain_graph=True)[0]
         head = dp if d_pred is None else d_pred.to(dtype)
-        g = torch.autograd.grad(pred, list(leaves.values()) + [c], grad_outputs=head, allow_unused=True)
+        zs = [ts_.z[k] for k in WK_NAMES]
+        g = torch.autograd.grad(pred, list(leaves.values()) + [c] + zs, grad_outputs=head, allow_unused=True)
+        g, gz = g[:-len(zs)], g[-len(zs):]
     assert all(v is not None for v in g)
     return dict(loss=loss.detach(), terms=terms.detach(), pred=pred.detach(), d_pred=dp.detach(), d_cond=g[-1].detach(),
-                grads={k: v.detach() for k, v in zip(PARAM_NAMES, g[:-1])})
+                grads={k: v.detach() for k, v in zip(PARAM_NAMES, g[:-1])},
+                wk_scale={k: (float(v.abs().sum(dim=(0, 2, 3)).max()) if v is not None else 0.0) for k, v in zip(WK_NAMES, gz)})
 
 
 def d_pred_closed_form(pred, target, past_len, weights=None):

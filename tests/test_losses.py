@@ -5,7 +5,8 @@ calc_loss and gaussian_diffusion.py's training_losses / q_sample) and against th
 Gate: the project's per-op rule max|d| / max|ref| <= 1e-4 (SURVEY.md section 8(d)), applied PER TERM (a [B] vector or a scalar);
 bit-identity claims are ``torch.equal``.  The fixture keeps every two samples of a clip more than 1e-3 apart in every term (asserted
 by the generator on the reference's own numbers), so no ``_min`` term is excluded from any comparison.  Every figure is printed
-before it is asserted."""
+before it is asserted.  EDGE_SHAPES: both kernels against the fp64 restatement where the frame split and the normalisers can go wrong; worst term on
+MI355X 8.4e-6, and an unmarked test holds the restatement's own fp32 run to a quarter of the gate at every one of them."""
 import os
 import re
 import numpy as np
@@ -71,14 +72,42 @@ def betas():
     return get_named_beta_schedule('cosine', 1000, 1.)
 
 
-def big_case(seed=9100, B=16, T=100, K=4):
+def big_case(seed=9100, B=16, T=100, K=4, past=fx.PAST, scales=(0.02, 0.03, 0.045, 0.07)):
     """The second, seeded scoring input: B = 16, T = 100, K = 4 -- ground truth of a synthetic clip batch, samples = gt + N(0, s_k)."""
     from interdiff_amd import synthetic as syn
-    bt = syn.make_clip_batch(seed=seed, B=B, T=T, past_len=fx.PAST, n_points=8)
+    bt = syn.make_clip_batch(seed=seed, B=B, T=T, past_len=past, n_points=8)
     rs = np.random.RandomState(seed + 1)
     gt, hands = tn(bt['gt']), tn(bt['hand_pose'])
-    samples = torch.stack([gt + s * fx._randn(rs, *gt.shape) for s in (0.02, 0.03, 0.045, 0.07)[:K]])
+    samples = torch.stack([gt + s * fx._randn(rs, *gt.shape) for s in scales[:K]])
     return samples, gt, hands
+
+
+# (B, T, past_len, K).  (1,3,1,1): sample_losses only (denoising_losses needs past_len >= 2); (1,4,2,1): the smallest shape both kernels admit; (1,12,10,1): T = P + 2, one
+# frame in _v_future, and the test variant starts one frame later still; (3,9,4,2): frame runs of 2, a one-frame last run, three empty waves, P on a run boundary;
+# (65,20,10,1): more clips than a wave has lanes; (2,131,10,2): a prime T past 128 (these kernels have no T limit).
+EDGE_SHAPES = [(1, 3, 1, 1), (1, 4, 2, 1), (1, 12, 10, 1), (3, 9, 4, 2), (65, 20, 10, 1), (5, 35, 10, 3), (2, 131, 10, 2)]
+# At (1,4,2,1) obj_rot_past is the mean of two frames of nine squared differences of O(1) matrix entries that lie 0.02 apart: fp32 itself computes it only to 2.9e-5.
+# The noise scale 0.07 (big_case's largest) in the place of 0.02 conditions the difference 3.5 times better; the gate stays where it is.
+EDGE_SCALES = {(1, 4, 2, 1): (0.07,)}
+FP32_CAP = 2.5e-5                                                  # a quarter of GATE: what the restatement's own fp32 arithmetic may use up at an edge shape
+_EDGE = {}
+
+
+def edge_case(shape):
+    B, T, P, K = shape
+    return big_case(seed=9200 + T, B=B, T=T, K=K, past=P, **({'scales': EDGE_SCALES[shape]} if shape in EDGE_SCALES else {}))
+
+
+def edge_ref(shape, dtype=torch.float64):
+    """The restatement at an edge shape, computed once per (shape, dtype) and never modified: 'test' on all K samples, 'val' and the denoising terms on samples[0]."""
+    if (shape, dtype) not in _EDGE:
+        P = shape[2]
+        samples, gt, hands = (a.to(dtype) for a in edge_case(shape))
+        t_test, per_test = lo.sample_terms(samples, gt, hands, P, 'test')
+        t_val, per_val = lo.sample_terms(samples[:1], gt, hands, P, 'val')
+        den = torch.stack(list(lo.denoising_terms(samples[0], gt, P).values())) if P >= 2 else None
+        _EDGE[(shape, dtype)] = dict(test=torch.stack(list(t_test.values())), per_test=per_test, val=torch.stack(list(t_val.values())), per_val=per_val, den=den)
+    return _EDGE[(shape, dtype)]
 
 
 # ------------------------------------------------------------------------------------------------------------ CPU
@@ -157,6 +186,28 @@ def test_new_symbols_declared_typed_and_exported():
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name)
     assert 'losses.hip' in __import__('interdiff_amd.csrc.build', fromlist=['sources']).sources()
+
+
+@pytest.mark.parametrize('shape', EDGE_SHAPES, ids=str)
+def test_fp32_restatement_at_edge_shapes(shape):
+    """The condition the edge-shape GPU test rests on: the restatement run in fp32 on the same inputs is within FP32_CAP = GATE / 4 of fp64 on every term and every
+    per-clip mean, so the inputs and not the gate carry the margin; and two samples of a clip are never so close that the ``_min`` pick could turn on rounding."""
+    r32, r64 = edge_ref(shape, torch.float32), edge_ref(shape)
+    worst = 0.0
+    for name in ('test', 'val', 'den'):
+        if r64[name] is not None:
+            for i in range(r64[name].shape[0]):
+                worst = max(worst, rel(r32[name][i], r64[name][i]))
+    for name in ('per_test', 'per_val'):
+        for i in range(16):
+            worst = max(worst, rel(r32[name][:, i], r64[name][:, i]))
+    gap = 1.0
+    if shape[3] > 1:
+        two = r64['per_test'].sort(dim=0)[0]
+        gap = float(((two[1] - two[0]) / two[0]).min())
+    print('B=%d T=%d past=%d K=%d: fp32 restatement vs fp64, worst term %.3e (cap %.1e); smallest best-of-K margin %.3e' % (*shape, worst, FP32_CAP, gap))
+    assert worst <= FP32_CAP and gap >= 1e-3
+    assert torch.equal(r32['per_test'].argmin(dim=0), r64['per_test'].argmin(dim=0))
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU
@@ -308,6 +359,53 @@ def test_calc_losses_vs_oracle_large(lib):
     assert float(vd['body_rot_v_future']) != float(L.calc_loss(samples[1:2].to(DEV), bt, fx.PAST)[1]['body_rot_v_future'])      # the two variants' future-velocity frames differ
     again = L.calc_loss(samples.to(DEV), bt, fx.PAST, return_per_clip=True)
     assert torch.equal(again[3], per) and torch.equal(again[0], loss)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape', EDGE_SHAPES, ids=str)
+def test_kernels_vs_restatement_at_edge_shapes(lib, shape):
+    """Both scoring kernels against the fp64 restatement at the shapes where the eight-wave frame split, the normalisers and the two variants' future-velocity
+    windows can go wrong (EDGE_SHAPES): GATE per term and per clip, the ``_min`` picks equal to the oracle's argmin, two calls the same bits.
+    Measured on MI355X: worst term over the seven shapes 8.4e-6 (0.084 of the gate; obj_rot_past at (1, 3, 1, 1), where the fp32 restatement is 8.3e-6 itself),
+    per clip 8.4e-6 (0.084), the denoising entry 4.4e-7 (0.004)."""
+    from interdiff_amd import losses as L, _lib
+    B, T, P, K = shape
+    tag = 'B=%d T=%d past=%d K=%d' % shape
+    ref = edge_ref(shape)
+    samples, gt, hands = (a.to(DEV) for a in edge_case(shape))
+    bt = dict(gt=gt, hand_pose=hands)
+    loss, ld, wd, per = L.calc_loss(samples, bt, P, return_per_clip=True)
+    assert list(ld) == list(L.LOSS_KEYS + L.MIN_KEYS) and per.shape == (K, 16, B)
+    close_terms(torch.stack(list(ld.values())), ref['test'], list(ld), 'calc_loss %s vs fp64 restatement' % tag)
+    close_terms(per.permute(1, 0, 2), ref['per_test'].permute(1, 0, 2), L.LOSS_KEYS, '... per-clip means')
+    l64, w64 = lo.weighted(dict(zip(L.LOSS_KEYS, ref['test'][:16])))
+    close_terms(torch.stack(list(wd.values())), torch.stack(list(w64.values())), L.LOSS_KEYS, '... weighted')
+    close(loss, l64, GATE, '... loss')
+    assert torch.equal(per.argmin(dim=0).cpu(), ref['per_test'].argmin(dim=0))                     # every _min term picks the oracle's sample
+    again = L.calc_loss(samples, bt, P, return_per_clip=True)
+    assert torch.equal(again[3], per) and torch.equal(again[0], loss) and torch.equal(torch.stack(list(again[1].values())), torch.stack(list(ld.values())))
+    vloss, vd, vw, vper = L._score(samples[:1], bt, P, L.LossWeights(), _lib.LOSS_VAL)
+    assert list(vd) == list(L.LOSS_KEYS)
+    close_terms(torch.stack(list(vd.values())), ref['val'], list(vd), 'calc_val_loss %s vs fp64 restatement' % tag)
+    close_terms(vper.permute(1, 0, 2), ref['per_val'].permute(1, 0, 2), L.LOSS_KEYS, '... per-clip means')
+    close(vloss, lo.weighted(dict(zip(L.LOSS_KEYS, ref['val'])))[0], GATE, '... val_loss')
+    v2 = L.calc_val_loss(samples[0], bt, P)
+    assert torch.equal(v2[0], vloss) and all(torch.equal(v2[1][k], vd[k]) for k in L.LOSS_KEYS)
+    # the raw teacher-forced entry on pred = samples[0]
+    sentinel = -7.0
+    out = [torch.full((16, B), sentinel, device=DEV) for _ in range(2)]
+    pred = samples[0].contiguous()
+    rc = [lib.interdiff_denoising_losses(_lib.dptr(pred), _lib.dptr(gt), B, T, P, _lib.dptr(o), _lib.stream()) for o in out]
+    torch.cuda.synchronize()
+    if P < 2:
+        assert rc == [-22, -22] and bool((out[0] == sentinel).all())                               # IDF_E_INVAL, nothing launched
+        return
+    assert rc == [0, 0] and torch.equal(out[0], out[1])
+    close_terms(out[0], ref['den'], L.LOSS_KEYS, 'interdiff_denoising_losses %s on samples[0] vs fp64 restatement' % tag)
+    if B == 65:                                                                                     # a clip's numbers are its own
+        for b in (0, 31, 64):
+            alone = L.calc_loss(samples[:, b:b + 1].contiguous(), dict(gt=gt[b:b + 1].contiguous(), hand_pose=hands[:, b:b + 1].contiguous()), P, return_per_clip=True)[3]
+            assert torch.equal(alone[:, :, 0], per[:, :, b]), 'clip %d' % b
 
 
 @pytest.mark.gpu

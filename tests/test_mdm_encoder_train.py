@@ -16,6 +16,10 @@ claims are ``torch.equal``.  Every figure is printed before it is asserted.
 Points: E1  B = 4, T = 35, past_len 10, t = [37, 412, 655, 999] (the scene of mdm_train_A; 40 encoder rows);  E2  B = 3, T = 12, past_len 5, t = [0, 500, 999] (an
 odd batch, a memory length other than 10, the shortest decoder the limits allow, t = 0; 15 encoder rows, one 32-row GEMM tile not filled).  pc_embedding is a recorded leaf.
 Measured on MI355X: DESIGN.md 8.16.  Without the feature every test below fails: the keyword, the names and the entries do not exist.
+
+Edge shapes (no recording, the fp64 oracle on synthetic points, SHAPES): pred / cond / terms / d_cond / d_pc 1e-4, the 228 tensors under helpers.shape_gate, whose wider
+part an unmarked test caps at 1e-2 of max|g64|.  Worst on MI355X: a tensor at 0.514 of its gate (``encoder.layers.6.queries`` at past_len 2), pred 1.2e-7, cond 5.5e-7,
+terms 1.1e-7, d_cond 6.9e-7, d_pc 5.0e-7.  ``test_limits_raise``: refused shapes touch nothing.
 """
 import numpy as np
 import pytest
@@ -23,10 +27,20 @@ import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
-from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
+from tests.denoiser_train_helpers import betas, check_new_symbols, compare_all, far_parameters, gate, rel, shape_gate, synthetic_point, tn, worst_d32
 
 DEV = 'cuda'
 N_PARAM, N_PARAM_DEC = 11824392, 7069900
+# (B, T, past_len) of the full entry: one clip, an odd length, the T limit, the smallest clip with the shortest memory (every QaN token of the encoder has a masked
+# neighbour), that memory under a longer clip, the memory-length limit
+SHAPES = [(1, 12, 10), (2, 33, 10), (1, 128, 10), (2, 4, 2), (2, 12, 2), (1, 18, 16)]
+FP32_CAP, D32_CAP = 2.5e-5, 1e-2
+# The seed of a shape's synthetic point is 9300 + T + past_len, but for the two past_len 2 shapes.  There the gradient of the encoder's ``queries`` shrinks about threefold per
+# layer (7e-8 in layer 1, 1e-9 .. 2e-8 in layer 6, by the seed) while fp32 leaves about 1e-12 on each, so 4 d32 / max|g64| of ``encoder.layers.6.queries`` is 3.7e-3 / 1.4e-3 at
+# seeds 9306 / 9314 on one CPU and 1.3e-2 / 3.2e-3 on another (the fp32 oracle's rounding is not the same on every CPU): past D32_CAP.  These two seeds are chosen on the fp64 oracle alone -- of the twelve seeds from
+# 9300 + T + past_len on, the one where max|g64| of that tensor is largest (2.0e-8 and 1.5e-8 against 1.6e-9 and 3.2e-9) -- so the point and not the cap carries the margin.
+SEEDS = {(2, 4, 2): 9312, (2, 12, 2): 9324}
+_SHAPE_POINTS = {}
 NEW_SYMBOLS = {
     'interdiff_mdm_train_full_param_table': 'int64_t *offsets, int64_t *sizes, int32_t *n_tensors, int64_t *n_param',
     'interdiff_mdm_train_full_workspace_bytes': 'int32_t B, int32_t T, int32_t past_len',
@@ -81,7 +95,35 @@ def traj():
     return dict(z=z, ts=ts, noises=noises, losses=losses, theta=theta)
 
 
+def shape_point(shape):
+    """A synthetic point (seed 9300 + T + past_len, or SEEDS) with the oracle on it in fp64 and in fp32, computed once per process and never modified."""
+    if shape not in _SHAPE_POINTS:
+        B, T, past = shape
+        p = synthetic_point(SEEDS.get(shape, 9300 + T + past), B, T, past)
+        run = lambda dtype: meo().grads(weights(), p['x_t'], p['t'], p['pc'], p['x0'], past, dtype=dtype)
+        _SHAPE_POINTS[shape] = dict(p, ref=run(torch.float64), r32=run(torch.float32))
+    return _SHAPE_POINTS[shape]
+
+
 # ------------------------------------------------------------------------------------------------------------ CPU
+
+@pytest.mark.parametrize('shape', SHAPES)
+def test_fp32_oracle_cap_at_shapes(shape):
+    """The condition ``test_shapes_vs_fp64`` rests on: the oracle in fp32 -- the reference arithmetic, not the code under test -- is within FP32_CAP of the fp64 oracle on
+    pred, cond, terms, d_cond and d_pc, and 4 d32(k), the part of ``shape_gate`` that can exceed the flat 1e-4, stays under D32_CAP = 1e-2 of max|g64| for every
+    non-``wk`` tensor (it exceeds 1e-4 for ``encoder.layers.6.queries`` at past_len 2 alone: 6.0e-4 .. 8.8e-4 on two CPUs at SEEDS)."""
+    _, _, FULL = names()
+    s = shape_point(shape)
+    ref, r32 = s['ref'], s['r32']
+    worst, name, wk_top, wk_scale = worst_d32(ref, r32, meo().WK_NAMES)
+    e = {k: rel(r32[k], ref[k]) for k in ('pred', 'cond', 'd_cond', 'd_pc')}
+    e['terms'] = rel(r32['terms'], ref['terms'])                       # (the [16,B] stack on its largest entry, as tests/test_skeleton_mdm_train.py measures it)
+    print('B=%d T=%d past_len=%d: fp32 oracle vs fp64: 4 d32 worst %.3e of max|g64| (%s; cap %.0e); wk %.3e of max|g64|, %.3e on wk_scale; pred %.3e, cond %.3e, '
+          'terms %.3e, d_cond %.3e, d_pc %.3e (cap %.1e)' % (*shape, worst, name, D32_CAP, wk_top, wk_scale, e['pred'], e['cond'], e['terms'], e['d_cond'], e['d_pc'],
+                                                           FP32_CAP))
+    assert worst <= D32_CAP and max(e.values()) <= FP32_CAP
+    assert all(float(ref['grads'][k].abs().max()) > 0 for k in FULL) and min(ref['wk_scale'].values()) > 0
+
 
 @pytest.mark.parametrize('name', ['E1', 'E2'])
 def test_oracle_vs_reference_samples(name):
@@ -262,6 +304,109 @@ def test_composition_with_the_decoder_only_entry(trainers):
             assert not torch.equal(full[k], part[k]), k
         else:
             assert torch.equal(full[k], part[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape', SHAPES, ids=str)
+def test_shapes_vs_fp64(trainers, shape):
+    """The full entry at (B, T, past_len) where the encoder's glue (gather_past, swap_rows, add_into) and the shared stack on past_len tokens can go wrong (SHAPES),
+    against the fp64 oracle on a synthetic point: pred, cond, terms, d_cond and d_pc at 1e-4, the 228 tensors under ``shape_gate`` (1e-4 of max|g64| or four times the
+    fp32 oracle's own distance; ``test_fp32_oracle_cap_at_shapes`` caps the latter).  At (2, 12, 2) the decoder-only entry fed ``tr.cond`` must reproduce the bits of the
+    full entry's decoder path (the property of ``test_composition_with_the_decoder_only_entry``, at a memory of two rows).
+    Measured on MI355X: worst tensor 0.514 of its gate (``encoder.layers.6.queries`` at (2, 12, 2): 4.5e-4 of max|g64| under a gate of 8.8e-4, the one tensor whose
+    gate is wider than the flat 1e-4; 0.149 at (2, 4, 2), at most 0.112 elsewhere); pred 1.2e-7, cond 5.5e-7, terms 1.1e-7, d_cond 6.9e-7, d_pc 5.0e-7.  The wk gate at
+    past_len 2 is 0.36 and 1.1 of max|g64| (the fp32 oracle is 0.09 away there, the kernel 0.03 and 0.07): it holds them on ``wk_scale`` alone."""
+    from interdiff_amd.mdm_train import DenoiserTrainer
+    DEC, _, FULL = names()
+    B, T, past = shape
+    s = shape_point(shape)
+    ref, tag = s['ref'], 'B=%d T=%d past_len=%d' % shape
+    d = on_dev(s)
+    tr = trainer_for(trainers, past)
+    pred, terms, d_cond, d_pc = tr.grads_at(d['x_t'], d['t'], d['pc'], d['x0'])
+    e = {k: rel(v, ref[k]) for k, v in (('pred', pred), ('cond', tr.cond), ('d_cond', d_cond), ('d_pc', d_pc))}
+    e['terms'] = rel(terms, ref['terms'])
+    gate_abs, widest_wk, widest = shape_gate(ref, s['r32'], meo().WK_NAMES)
+    print('%s: pred %.3e, cond %.3e, terms %.3e, d_cond %.3e, d_pc %.3e (1e-4); widest wk gate %.3e, widest other gate %.3e of max|g64|' % (
+        tag, e['pred'], e['cond'], e['terms'], e['d_cond'], e['d_pc'], widest_wk, widest))
+    compare_all(tr.named_views(tr.grads), ref, FULL, gate_abs, tag)
+    assert max(e.values()) <= 1e-4
+    assert tuple(tr.cond.shape) == tuple(d_cond.shape) == (past, B, 256) and d_pc.shape == d['pc'].shape and pred.shape == d['x0'].shape
+    if shape == (2, 12, 2):
+        full = {k: v.clone() for k, v in tr.named_views(tr.grads).items()}
+        dec = DenoiserTrainer(weights(), device=DEV, past_len=past)
+        pred2, terms2, d_cond2 = dec.grads_at(d['x_t'], d['t'], tr.cond, d['x0'])
+        assert torch.equal(pred, pred2) and torch.equal(terms, terms2) and torch.equal(d_cond, d_cond2)
+        part = dec.named_views(dec.grads)
+        for k in DEC:
+            if k in SHARED:
+                assert not torch.equal(full[k], part[k]), k
+            else:
+                assert torch.equal(full[k], part[k]), k
+
+
+@pytest.mark.gpu
+def test_limits_raise(lib, trainers):
+    """Refused shapes are refused -- ValueError from the wrapper or the RuntimeError of ``_lib.check``, whichever the code raises -- and touch nothing: the flat gradient
+    and ``tr.cond`` keep their bits.  The raw entry refuses a workspace that is too small (IDF_E_NOMEM) or misaligned (IDF_E_INVAL) and writes no output; the sizing
+    entry returns 0 past the limits."""
+    from interdiff_amd import _lib
+    tr = trainer_for(trainers, 10)
+    s = on_dev(synthetic_point(9399, 2, 12, 10))
+    pred, terms, d_cond, d_pc = tr.grads_at(s['x_t'], s['t'], s['pc'], s['x0'])
+    before, cond = tr.grads.clone(), tr.cond.clone()
+    assert bool(before.ne(0).any())
+    zeros = lambda *shape: torch.zeros(*shape, device=DEV)
+    t1 = torch.zeros(1, dtype=torch.int64, device=DEV)
+    refused = [
+        ('T = 129', lambda: tr.grads_at(zeros(1, 1, 144, 129), t1, zeros(1, 256), zeros(1, 1, 144, 129))),
+        ('T = past_len + 1', lambda: tr.grads_at(zeros(1, 1, 144, 11), t1, zeros(1, 256), zeros(1, 1, 144, 11))),
+        ('pc of another B', lambda: tr.grads_at(s['x_t'], s['t'], zeros(3, 256), s['x0'])),
+        ('pc of another width', lambda: tr.grads_at(s['x_t'], s['t'], zeros(2, 255), s['x0'])),
+        ('pc with a memory axis', lambda: tr.grads_at(s['x_t'], s['t'], zeros(10, 2, 256), s['x0'])),
+        ('d_pred of another shape', lambda: tr.grads_at(s['x_t'], s['t'], s['pc'], s['x0'], d_pred=zeros(2, 1, 144, 11))),
+        ('target of another shape', lambda: tr.grads_at(s['x_t'], s['t'], s['pc'], zeros(2, 1, 144, 11))),
+        ('cond and pc', lambda: tr.grads_at(s['x_t'], s['t'], zeros(10, 2, 256), s['x0'], pc=s['pc'])),
+    ]
+    for what, call in refused:
+        with pytest.raises((ValueError, RuntimeError)):
+            call()
+        torch.cuda.synchronize()
+        assert torch.equal(tr.grads, before) and torch.equal(tr.cond, cond), what
+    for past in (1, 17):                                                   # a trainer built for a memory the stack does not take refuses every call
+        bad = new_trainer(past)
+        with pytest.raises((ValueError, RuntimeError)):
+            bad.grads_at(zeros(2, 1, 144, 24), s['t'], s['pc'], zeros(2, 1, 144, 24))
+        assert not bool(bad.grads.ne(0).any()) and bad.cond is None
+    # the raw entry and its workspace
+    B, T, S = 2, 12, 10
+    need = lib.interdiff_mdm_train_full_workspace_bytes(B, T, S)
+    assert need > lib.interdiff_mdm_train_workspace_bytes(B, T, S) > 0
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=DEV)
+    sentinel = -7.0
+    outs = [torch.full(shape, sentinel, device=DEV) for shape in ((S, B, 256), (S, B, 256), (B, 256), (B, 1, 144, T), (16, B))]
+    def raw(ws_ptr, ws_bytes, T_=T, past=S):
+        return lib.interdiff_mdm_train_full_grads(_lib.dptr(tr.params), _lib.dptr(tr.pe), tr.pe.shape[0], _lib.dptr(s['x_t']), _lib.dptr(s['t']), _lib.dptr(s['pc']),
+                                                  _lib.dptr(s['x0']), B, T_, past, tr._wvec, _lib.vp(None), _lib.dptr(tr.grads), *[_lib.dptr(o) for o in outs],
+                                                  ws_ptr, ws_bytes, _lib.stream())
+    base = ws.data_ptr()
+    assert base % 256 == 0
+    assert raw(_lib.vp(base), need - 1) == -12                             # one byte short: IDF_E_NOMEM
+    assert raw(_lib.vp(base), lib.interdiff_mdm_train_workspace_bytes(B, T, S)) == -12             # the decoder-only entry's size
+    assert raw(_lib.vp(base + 4), need) == -22                             # not 256-byte aligned: IDF_E_INVAL
+    assert raw(_lib.vp(None), need) == -22
+    assert raw(_lib.vp(base), need, past=11) == -22 and raw(_lib.vp(base), need, T_=129) == -22 and raw(_lib.vp(base), need, past=1) == -22
+    with pytest.raises(RuntimeError):
+        _lib.check(raw(_lib.vp(base), need - 1))
+    torch.cuda.synchronize()
+    assert torch.equal(tr.grads, before) and all(bool((o == sentinel).all()) for o in outs)
+    assert raw(_lib.vp(base), need) == 0                                   # the same call with its workspace runs, and gives the wrapper's bits
+    torch.cuda.synchronize()
+    assert torch.equal(tr.grads, before)
+    assert all(torch.equal(o, w) for o, w in zip(outs, (cond, d_cond, d_pc, pred, terms)))
+    size = lib.interdiff_mdm_train_full_workspace_bytes
+    assert size(1, 11, 10) == 0 and size(1, 3, 2) == 0 and size(1, 129, 10) == 0 and size(1, 19, 17) == 0
+    assert size(1, 12, 10) > 0 and size(1, 4, 2) > 0
 
 
 @pytest.mark.gpu

@@ -10,13 +10,19 @@ MDM.forward.  Trajectory: 6 AdamW steps, losses 1e-5 relative, at most 0.1 % of 
 Points: A  B = 4, T = 35, t = [37, 412, 655, 999] (M = 140 rows);  B  B = 3, T = 100, t = [0, 500, 999] (M = 300: self-attention over more than one 64-key tile,
 t = 0, an odd batch).  Weights: fixtures.mdm_weights_wc(), with the rows of the sinusoidal table that the reference runs read taken from the recordings (``weights()``:
 sin / cos of fp32 arguments differ in the last bits between CPUs, and e_ref is that small).  Without the feature this module fails at import (interdiff_amd.mdm_train does not exist).
+
+Edge shapes (no recording, the fp64 oracle on synthetic points): the loss-gradient entry at LOSS_GRAD_SHAPES (1e-5 of max|d|; worst on MI355X 8.1e-8), the decoder-only
+entry with a free memory length at SHAPES (pred / terms / d_cond 1e-4, the tensors under helpers.shape_gate; worst tensor 0.164 of its gate, pred 9.6e-8, terms 2.8e-7,
+d_cond 5.6e-7), AdamW on injected gradients against torch.optim.AdamW (worst 0.998 of the one-ulp gate, moments 9.9e-8 of max), and the refused shapes.
 """
+import numpy as np
 import pytest
 import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import mdm_train_oracle as mo
-from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
+from tests.denoiser_train_helpers import (adam_vectors, betas, check_new_symbols, compare_all, far_parameters, gate, rel, shape_gate, synthetic_point, tn,
+                                          worst_d32)
 from interdiff_amd.mdm_train import PARAM_NAMES
 
 DEV = 'cuda'
@@ -55,7 +61,54 @@ def point(name):
     return _POINTS[name]
 
 
+NONDEFAULT = dict(weight_smplx_rot=0.7, weight_smplx_nonrot=1.3, weight_obj_rot=0.4, weight_obj_nonrot=2.0, weight_past=0.5, weight_v=3.0)
+# (B, T, past_len) of the loss-gradient entry: the smallest shape, T = P + 2, P = 2 with more than one future frame, the T limit of the trainer, and a P whose
+# P - 1 and T - P - 1 normalisers both differ from the recorded points'
+LOSS_GRAD_SHAPES = [(1, 4, 2), (1, 12, 10), (2, 5, 2), (3, 128, 10), (2, 12, 9)]
+# (B, T, past_len, mem_len) of the decoder-only entry, whose memory length is free: one memory row (softmax over one key), the memory-length limit, an odd batch with an
+# odd memory, the T limit, the smallest clip
+SHAPES = [(2, 12, 10, 1), (1, 35, 10, 16), (3, 20, 10, 7), (1, 128, 10, 10), (2, 4, 2, 3)]
+FP32_CAP, D32_CAP = 2.5e-5, 1e-2
+_SHAPE_POINTS = {}
+
+
+def shape_point(shape):
+    """A synthetic point (seed 9400 + T + mem_len) with the oracle on it in fp64 and in fp32, computed once per process and never modified."""
+    if shape not in _SHAPE_POINTS:
+        B, T, past, mem = shape
+        p = synthetic_point(9400 + T + mem, B, T, past, mem)
+        run = lambda dtype: mo.grads(weights(), p['x_t'], p['t'], p['cond'], p['x0'], past, dtype=dtype)
+        _SHAPE_POINTS[shape] = dict(p, ref=run(torch.float64), r32=run(torch.float32))
+    return _SHAPE_POINTS[shape]
+
+
+def loss_grad_case(B, T, P):
+    """gt = the tokens of a synthetic clip batch, pred = gt + 0.3 N(0, 1)."""
+    from interdiff_amd import synthetic as syn
+    gt = tn(syn.make_clip_batch(9500 + T + P, B, T, past_len=P, n_points=8)['gt'])
+    return gt + 0.3 * fx._randn(np.random.RandomState(9501 + T + P), *gt.shape), gt
+
+
 # ------------------------------------------------------------------------------------------------------------ CPU
+
+@pytest.mark.parametrize('shape', SHAPES)
+def test_fp32_oracle_cap_at_shapes(shape):
+    """The condition ``test_shapes_vs_fp64`` rests on: the oracle in fp32 -- the reference arithmetic, not the code under test -- is within FP32_CAP of the fp64 oracle on
+    pred, terms and d_cond, and 4 d32(k), the part of ``shape_gate`` that can exceed the flat 1e-4, stays under D32_CAP = 1e-2 of max|g64| for every non-``wk`` tensor."""
+    s = shape_point(shape)
+    ref, r32 = s['ref'], s['r32']
+    worst, name, wk_top, wk_scale = worst_d32(ref, r32, mo.WK_NAMES)
+    e = {k: rel(r32[k], ref[k]) for k in ('pred', 'd_cond')}
+    e['terms'] = rel(r32['terms'], ref['terms'])                       # (the [16,B] stack on its largest entry, as tests/test_skeleton_mdm_train.py measures it)
+    print('B=%d T=%d past_len=%d mem_len=%d: fp32 oracle vs fp64: 4 d32 worst %.3e of max|g64| (%s; cap %.0e); wk %.3e of max|g64|, %.3e on wk_scale; pred %.3e, '
+          'terms %.3e, d_cond %.3e (cap %.1e)' % (*shape, worst, name, D32_CAP, wk_top, wk_scale, e['pred'], e['terms'], e['d_cond'], FP32_CAP))
+    assert worst <= D32_CAP and max(e.values()) <= FP32_CAP
+    assert all(float(ref['grads'][k].abs().max()) > 0 for k in PARAM_NAMES) and min(ref['wk_scale'].values()) > 0
+    if shape[3] == 1:                                                      # one key: dS = 0, so the q and k rows of every cross-attention in-projection get exactly nothing
+        for l in range(8):
+            for k in ('decoder.layers.%d.multihead_attn.in_proj_weight' % l, 'decoder.layers.%d.multihead_attn.in_proj_bias' % l):
+                assert not bool(ref['grads'][k][:512].ne(0).any()) and bool(ref['grads'][k][512:].ne(0).any()), k
+
 
 @pytest.mark.parametrize('name', ['A', 'B'])
 def test_oracle_vs_reference_samples(name):
@@ -96,11 +149,20 @@ def test_closed_form_d_pred_vs_autograd(name):
     g = torch.Generator().manual_seed(5)
     gt = torch.randn(2, 1, 144, 17, generator=g, dtype=torch.float64)
     pred = gt + 0.3 * torch.randn(2, 1, 144, 17, generator=g, dtype=torch.float64)
-    wts = dict(weight_smplx_rot=0.7, weight_smplx_nonrot=1.3, weight_obj_rot=0.4, weight_obj_nonrot=2.0, weight_past=0.5, weight_v=3.0)
+    wts = NONDEFAULT
     with torch.enable_grad():
         pr = pred.clone().requires_grad_(True)
         auto = torch.autograd.grad(mo.loss_of(pr, gt, 4, wts)[0], pr)[0]
     assert rel(mo.d_pred_closed_form(pred, gt, 4, wts), auto) <= 1e-12
+    # ... and so do the edges: the smallest shape (one second-difference term on either side of the boundary) and P = 2 with T = P + 3
+    for T, P in ((4, 2), (5, 2)):
+        gt = torch.randn(2, 1, 144, T, generator=g, dtype=torch.float64)
+        pred = gt + 0.3 * torch.randn(2, 1, 144, T, generator=g, dtype=torch.float64)
+        for w in (None, wts):
+            with torch.enable_grad():
+                pr = pred.clone().requires_grad_(True)
+                auto = torch.autograd.grad(mo.loss_of(pr, gt, P, w)[0], pr)[0]
+            assert rel(mo.d_pred_closed_form(pred, gt, P, w), auto) <= 1e-12, (T, P)
 
 
 def test_new_symbols_declared_typed_and_exported():
@@ -147,12 +209,37 @@ def on_dev(p):
     return {k: p[k].to(DEV) for k in ('x0', 'cond', 't', 'eps', 'x_t')}
 
 
+@pytest.fixture(scope='module')
+def trainers(trainer):
+    return {(10, False): trainer}                                          # (past_len, non-default loss weights) -> a trainer that is never stepped
+
+
+def trainer_for(trainers, past, nondefault=False):
+    from interdiff_amd.losses import LossWeights
+    if (past, nondefault) not in trainers:
+        trainers[(past, nondefault)] = new_trainer(past_len=past, **({'weights': LossWeights(**NONDEFAULT)} if nondefault else {}))
+    return trainers[(past, nondefault)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['A', 'B'])
-def test_loss_grad_entry_vs_closed_form(trainer, name):
+@pytest.mark.parametrize('name', ['A', 'B'] + LOSS_GRAD_SHAPES, ids=str)
+def test_loss_grad_entry_vs_closed_form(trainers, name):
+    """The recorded points at their own gate; the synthetic (B, T, past_len) at 1e-5 of max|d|, with the default weights and, through a second trainer, with others.
+    Measured on MI355X: worst of the ten synthetic cases 8.1e-8 (0.008 of the gate)."""
+    if isinstance(name, tuple):
+        B, T, P = name
+        pred, gt = loss_grad_case(B, T, P)
+        for nondefault in (False, True):
+            want = mo.d_pred_closed_form(pred.double(), gt.double(), P, NONDEFAULT if nondefault else None)
+            got = trainer_for(trainers, P, nondefault).loss_grad(pred.to(DEV), gt.to(DEV))
+            e = rel(got, want)
+            print('B=%d T=%d past_len=%d, %s weights: interdiff_denoising_loss_grad vs the fp64 closed form: %.3e of max|d| (gate 1e-5)' % (
+                B, T, P, 'other' if nondefault else 'default', e))
+            assert got.shape == pred.shape and e <= 1e-5
+        return
     p = point(name)
     want = mo.d_pred_closed_form(p['ref']['pred'], p['x0'].double(), 10)
-    got = trainer.loss_grad(p['ref']['pred'].float().to(DEV), p['x0'].to(DEV))
+    got = trainers[(10, False)].loss_grad(p['ref']['pred'].float().to(DEV), p['x0'].to(DEV))
     e, g = rel(got, want), gate(p['e_ref']['d_pred'])
     print('point %s: interdiff_denoising_loss_grad vs the fp64 closed form: %.3e (gate %.1e)' % (name, e, g))
     assert e <= g
@@ -207,6 +294,187 @@ def test_d_pred_seam(trainer):
     assert torch.equal(g0, trainer.grads) and torch.equal(dc0, dc1)        # the default path IS the loss-gradient entry's output fed to the seam
     _, _, dc2 = trainer.grads_at(d['x_t'], d['t'], d['cond'], d['x0'], d_pred=2 * dp)
     assert torch.equal(2 * g0, trainer.grads) and torch.equal(2 * dc0, dc2)                        # the backward is linear in d_pred, bit for bit
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape', SHAPES, ids=str)
+def test_shapes_vs_fp64(trainers, shape):
+    """The decoder-only entry at (B, T, past_len, mem_len) where its kernels can go wrong (SHAPES), against the fp64 oracle on a synthetic point: pred, terms and d_cond
+    at 1e-4, the 144 tensors under ``shape_gate`` (1e-4 of max|g64| or four times the fp32 oracle's own distance; ``test_fp32_oracle_cap_at_shapes`` caps the latter).
+    Measured on MI355X: worst tensor 0.164 of its gate (at (2, 4, 2, 3)); pred 9.6e-8, terms 2.8e-7, d_cond 5.6e-7; no gate was wider than the flat 1e-4 but wk's
+    (at most 1.8e-3 of max|g64|, at (1, 128, 10, 10); the kernel's wk is at most 1.0e-4 of max|g64| away)."""
+    B, T, past, mem = shape
+    s = shape_point(shape)
+    ref, tag = s['ref'], 'B=%d T=%d past_len=%d mem_len=%d' % shape
+    tr = trainer_for(trainers, past)
+    pred, terms, d_cond = tr.grads_at(s['x_t'].to(DEV), s['t'].to(DEV), s['cond'].to(DEV), s['x0'].to(DEV))
+    e_pred, e_cond = rel(pred, ref['pred']), rel(d_cond, ref['d_cond'])
+    e_terms = rel(terms, ref['terms'])
+    gate_abs, widest_wk, widest = shape_gate(ref, s['r32'], mo.WK_NAMES)
+    print('%s: pred %.3e, terms %.3e, d_cond %.3e (1e-4); widest wk gate %.3e, widest other gate %.3e of max|g64|' % (tag, e_pred, e_terms, e_cond, widest_wk, widest))
+    grads = tr.named_views(tr.grads)
+    compare_all(grads, ref, PARAM_NAMES, gate_abs, tag)
+    assert e_pred <= 1e-4 and e_terms <= 1e-4 and e_cond <= 1e-4
+    assert pred.shape == s['x0'].shape and tuple(d_cond.shape) == (mem, B, 256) and tuple(terms.shape) == (16, B)
+    if mem == 1:                                                           # softmax over one key: dS = 0 exactly, in the oracle and in the kernel
+        for l in range(8):
+            for k in ('decoder.layers.%d.multihead_attn.in_proj_weight' % l, 'decoder.layers.%d.multihead_attn.in_proj_bias' % l):
+                assert not bool(ref['grads'][k][:512].ne(0).any()) and not bool(grads[k][:512].ne(0).any()), k
+
+
+def adamw_entry(lib, p, g, m, v, n, step, wd, lr=3e-4):
+    from interdiff_amd import _lib
+    ptr = lambda t: _lib.vp(None) if t is None else _lib.dptr(t)
+    return lib.interdiff_mdm_train_step(ptr(p), ptr(g), ptr(m), ptr(v), n, step, lr, 0.9, 0.999, 1e-8, wd, _lib.stream())
+
+
+ADAMW_PAD = 64
+
+
+def padded(a):
+    """A device buffer of len(a) + ADAMW_PAD floats: ``a`` and a tail the entry must not touch."""
+    return torch.cat([a.float(), torch.linspace(-3.0, 3.0, ADAMW_PAD)]).to(DEV)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', ['wd0', 'wd_resync', 'late'])
+@pytest.mark.parametrize('n', [1, 255, 257, 70001])
+def test_adamw_on_injected_gradients(lib, n, case):
+    """``interdiff_mdm_train_step`` on small device vectors against torch.optim.AdamW (``_single_tensor_adamw``) on CPU fp32 tensors, three steps; each step's
+    parameter change within 2^-20 relative of torch's change plus one ulp of the parameter, the moments within 1e-6 of their largest entry (the gate of
+    tests/test_skeleton_finetune.py::test_adam_on_injected_gradients; the allowed differences are the association of value * m / denom and FMA contraction).
+    'wd0': weight_decay 0, one uninterrupted run from zero moments.  'wd_resync': weight_decay 1e-2; before steps 2 and 3 torch starts from the kernel's own
+    parameters and moments, for the reason that test's docstring records (with decay the one-ulp differences the gate allows feed the next step's moments).
+    'late': weight_decay 0, both sides start from given non-zero moments with 99,998 steps behind them, where both bias corrections have long been 1; resynchronised
+    like 'wd_resync', because from non-zero moments a gradient near -9 m cancels exp_avg to a few ulps of its old size, and a one-ulp difference of the moment that the
+    1e-6 gate allows then is a relative difference of the NEXT step's move far above 2^-20 (seen in a numpy restatement of the kernel: 3e-5 on an entry with |p| = 9e-5).
+    n: one element, one short of a block, one past a block, many blocks with a tail.  Every buffer carries 64 more floats than n, which must keep their bits.
+    Measured on MI355X: worst |d_hip - d_torch| over all cases 0.998 of its gate (one ulp of the parameter: the two sums round to neighbouring floats); moments
+    9.9e-8 of max (0.099 of the gate)."""
+    rs = np.random.RandomState(7500 + n)
+    wd, step0 = (1e-2 if case == 'wd_resync' else 0.0), (99998 if case == 'late' else 0)
+    p0 = tn((0.05 * rs.standard_normal(n)).astype(np.float32))
+    m0 = tn((1e-3 * rs.standard_normal(n)).astype(np.float32)) if case == 'late' else torch.zeros(n)
+    # (moments a run can have: an average of g^2 is never below the square of the average of g, so |m| / sqrt(v) <= 1 and a step moves at most lr)
+    v0 = (m0 ** 2 + tn((1e-3 * rs.standard_normal(n)).astype(np.float32)) ** 2) if case == 'late' else torch.zeros(n)
+    pd, md, vd = padded(p0), padded(m0), padded(v0)
+    tails = [t[n:].clone() for t in (pd, md, vd)]
+    p = torch.nn.Parameter(p0.clone())
+    opt = torch.optim.AdamW([p], lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=wd, foreach=False)
+    opt.state[p] = dict(step=torch.tensor(float(step0)), exp_avg=m0.clone(), exp_avg_sq=v0.clone())
+    worst, worst_m = 0.0, 0.0
+    for k, gv in enumerate(adam_vectors(n)):
+        if k and case != 'wd0':
+            with torch.no_grad():
+                p.copy_(pd[:n].cpu())
+                opt.state[p]['exp_avg'].copy_(md[:n].cpu())
+                opt.state[p]['exp_avg_sq'].copy_(vd[:n].cpu())
+        before_t, before_h = p.detach().clone().double(), pd[:n].cpu().double()
+        assert case == 'wd0' or torch.equal(before_t, before_h)
+        p.grad = tn(gv.copy())
+        opt.step()
+        gd = padded(tn(gv))
+        assert adamw_entry(lib, pd, gd, md, vd, n, step0 + k + 1, wd) == 0
+        assert int(opt.state[p]['step']) == step0 + k + 1
+        dt, dh = p.detach().double() - before_t, pd[:n].cpu().double() - before_h
+        ulp = tn(np.spacing(np.abs(p.detach().numpy()))).double()
+        allowed = 2.0 ** -20 * dt.abs() + ulp
+        worst = max(worst, float(((dh - dt).abs() / allowed).max()))
+        for mine, theirs in ((md, opt.state[p]['exp_avg']), (vd, opt.state[p]['exp_avg_sq'])):
+            worst_m = max(worst_m, float((mine[:n].cpu() - theirs).abs().max()) / float(theirs.abs().max()))
+        print('n=%d %s step %d: worst |d_hip - d_torch| %.3f of its gate; moments %.3e of max (gate 1e-6); largest move %.3e' % (
+            n, case, step0 + k + 1, worst, worst_m, float(dt.abs().max())))
+        assert worst <= 1.0 and worst_m <= 1e-6
+        assert float(dt.abs().max()) > 1e-5                                # (the step moved something)
+        assert all(torch.equal(t[n:], tail) for t, tail in zip((pd, md, vd), tails)) and torch.equal(gd[n:], padded(tn(gv))[n:])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('n', [1, 255, 257, 70001])
+def test_adamw_zero_gradient_and_refusals(lib, n):
+    """Bit for bit: with g = 0 and zero moments the entry leaves p as it was at weight_decay 0 and gives p * float32(1 - lr wd) with decay; the 64 floats behind n keep
+    their bits.  n <= 0, step < 1 and a null pointer return IDF_E_INVAL and change nothing."""
+    rs = np.random.RandomState(7600 + n)
+    p0 = tn((0.05 * rs.standard_normal(n)).astype(np.float32))
+    for wd in (0.0, 1e-2):
+        pd, gd, md, vd = padded(p0), padded(torch.zeros(n)), padded(torch.zeros(n)), padded(torch.zeros(n))
+        start = [t.clone() for t in (pd, gd, md, vd)]
+        assert adamw_entry(lib, pd, gd, md, vd, n, 1, wd) == 0
+        want = p0 if wd == 0.0 else p0 * torch.tensor(np.float32(1.0 - 3e-4 * wd))
+        assert torch.equal(pd[:n].cpu(), want) and (wd == 0.0 or not torch.equal(want, p0))
+        assert not bool(md[:n].ne(0).any()) and not bool(vd[:n].ne(0).any())
+        assert all(torch.equal(t[n:], s[n:]) for t, s in zip((pd, gd, md, vd), start))
+    pd, gd, md, vd = (padded(tn(rs.standard_normal(n).astype(np.float32))) for _ in range(4))
+    vd.abs_()
+    start = [t.clone() for t in (pd, gd, md, vd)]
+    assert adamw_entry(lib, pd, gd, md, vd, 0, 1, 0.0) == -22 and adamw_entry(lib, pd, gd, md, vd, -1, 1, 0.0) == -22
+    assert adamw_entry(lib, pd, gd, md, vd, n, 0, 0.0) == -22 and adamw_entry(lib, pd, gd, md, vd, n, -3, 0.0) == -22
+    for hole in range(4):
+        args = [pd, gd, md, vd]
+        args[hole] = None
+        assert adamw_entry(lib, *args, n, 1, 0.0) == -22
+    torch.cuda.synchronize()
+    assert all(torch.equal(t, s) for t, s in zip((pd, gd, md, vd), start))
+    assert adamw_entry(lib, pd, gd, md, vd, n, 1, 0.0) == 0 and not torch.equal(pd[:n], start[0][:n])       # (the same buffers, accepted, do move)
+
+
+@pytest.mark.gpu
+def test_limits_raise(lib, trainers):
+    """Refused shapes are refused -- ValueError from the wrapper or the RuntimeError of ``_lib.check``, whichever the code raises -- and touch nothing: the flat gradient
+    keeps its bits.  The raw entry refuses a workspace that is too small (IDF_E_NOMEM) or misaligned (IDF_E_INVAL) and writes no output; the sizing entry returns 0
+    past the limits."""
+    from interdiff_amd import _lib
+    tr = trainer_for(trainers, 10)
+    s = {k: v.to(DEV) for k, v in synthetic_point(9499, 2, 12, 10, 3).items() if k != 'past'}
+    pred, terms, d_cond = tr.grads_at(s['x_t'], s['t'], s['cond'], s['x0'])
+    before = tr.grads.clone()
+    assert bool(before.ne(0).any())
+    zeros = lambda *shape: torch.zeros(*shape, device=DEV)
+    t1 = torch.zeros(1, dtype=torch.int64, device=DEV)
+    refused = [
+        ('T = 129', lambda: tr.grads_at(zeros(1, 1, 144, 129), t1, zeros(10, 1, 256), zeros(1, 1, 144, 129))),
+        ('T = past_len + 1', lambda: tr.grads_at(zeros(1, 1, 144, 11), t1, zeros(10, 1, 256), zeros(1, 1, 144, 11))),
+        ('mem_len = 17', lambda: tr.grads_at(s['x_t'], s['t'], zeros(17, 2, 256), s['x0'])),
+        ('mem_len = 0', lambda: tr.grads_at(s['x_t'], s['t'], zeros(0, 2, 256), s['x0'])),
+        ('cond of another B', lambda: tr.grads_at(s['x_t'], s['t'], zeros(3, 3, 256), s['x0'])),
+        ('cond of another width', lambda: tr.grads_at(s['x_t'], s['t'], zeros(3, 2, 255), s['x0'])),
+        ('d_pred of another shape', lambda: tr.grads_at(s['x_t'], s['t'], s['cond'], s['x0'], d_pred=zeros(2, 1, 144, 11))),
+        ('target of another shape', lambda: tr.grads_at(s['x_t'], s['t'], s['cond'], zeros(2, 1, 144, 11))),
+        ('143 channels', lambda: tr.grads_at(zeros(2, 1, 143, 12), s['t'], s['cond'], zeros(2, 1, 143, 12))),
+    ]
+    for what, call in refused:
+        with pytest.raises((ValueError, RuntimeError)):
+            call()
+        torch.cuda.synchronize()
+        assert torch.equal(tr.grads, before), what
+    # the raw entry and its workspace
+    B, T, S = 2, 12, 3
+    need = lib.interdiff_mdm_train_workspace_bytes(B, T, S)
+    assert need > 0
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=DEV)
+    sentinel = -7.0
+    outs = [torch.full(shape, sentinel, device=DEV) for shape in ((S, B, 256), (B, 1, 144, T), (16, B))]
+    def raw(ws_ptr, ws_bytes, T_=T, S_=S, past=10):
+        return lib.interdiff_mdm_train_grads(_lib.dptr(tr.params), _lib.dptr(tr.pe), tr.pe.shape[0], _lib.dptr(s['x_t']), _lib.dptr(s['t']), _lib.dptr(s['cond']),
+                                             _lib.dptr(s['x0']), B, T_, S_, past, tr._wvec, _lib.vp(None), _lib.dptr(tr.grads), _lib.dptr(outs[0]), _lib.dptr(outs[1]),
+                                             _lib.dptr(outs[2]), ws_ptr, ws_bytes, _lib.stream())
+    base = ws.data_ptr()
+    assert base % 256 == 0
+    assert raw(_lib.vp(base), need - 1) == -12                             # one byte short: IDF_E_NOMEM
+    assert raw(_lib.vp(base + 4), need) == -22                             # not 256-byte aligned: IDF_E_INVAL
+    assert raw(_lib.vp(None), need) == -22
+    assert raw(_lib.vp(base), need, past=11) == -22 and raw(_lib.vp(base), need, T_=129) == -22 and raw(_lib.vp(base), need, S_=17) == -22
+    assert raw(_lib.vp(base), need, S_=0) == -22 and raw(_lib.vp(base), need, past=1) == -22
+    with pytest.raises(RuntimeError):
+        _lib.check(raw(_lib.vp(base), need - 1))
+    torch.cuda.synchronize()
+    assert torch.equal(tr.grads, before) and all(bool((o == sentinel).all()) for o in outs)
+    assert raw(_lib.vp(base), need) == 0                                   # the same call with its workspace runs, and gives the wrapper's bits
+    torch.cuda.synchronize()
+    assert torch.equal(tr.grads, before) and torch.equal(outs[0], d_cond) and torch.equal(outs[1], pred) and torch.equal(outs[2], terms)
+    size = lib.interdiff_mdm_train_workspace_bytes
+    assert size(1, 129, 10) == 0 and size(1, 12, 17) == 0 and size(1, 12, 0) == 0 and size(0, 12, 10) == 0
+    assert size(1, 128, 16) > size(1, 128, 1) > 0 and size(1, 4, 3) > 0
 
 
 @pytest.fixture(scope='module')

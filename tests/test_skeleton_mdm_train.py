@@ -21,7 +21,7 @@ import torch
 from tests import fixtures as fx
 from tests import losses_oracle as lo
 from tests import skeleton_losses_oracle as slo
-from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, gate, rel, tn
+from tests.denoiser_train_helpers import betas, check_new_symbols, far_parameters, flat_gate, gate, rel, tn
 
 DEV = 'cuda'
 N_PARAM, SEED, PAST = 5499582, 1106, 10                                   # SEED: make_golden_skeleton_mdm.SEED, the weights every skeleton-denoiser fixture uses
@@ -79,23 +79,6 @@ def synthetic_point(seed, B, T, past=PAST):
     t, eps = tn(rs.randint(0, 1000, size=B).astype(np.int64)), fx._randn(rs, B, 1, 106, T)
     x_t = lo.q_sample(betas(), x0, t, eps)
     return dict(x0=x0, zpo=zpo, t=t, eps=eps, x_t=x_t, ref=so().grads(weights(), x_t, t, zpo, x0, past))
-
-
-def flat_gate(ref, r32):
-    """The absolute gate of the tests that have no recorded e_ref: 1e-4 max|g64| on every tensor.  For the twelve ``wk`` tensors that figure is below what fp32 can
-    compute (the oracle run in fp32 is itself up to 2.9e-2 of max|g64| away at past_len 2), so theirs is four times the fp32 rounding noise of the same point: the
-    rounding error of d wk[n] is proportional to the sum of the magnitudes of the products it adds up, the constant c32 is the worst of the fp32 oracle's twelve
-    ``wk`` tensors on that scale (``r32``: the oracle on the same point in fp32), and 4 is the project's multiple of a reference's own error.  Never below
-    1e-4 max|g64| and never above 1e-4 of the sum of magnitudes.  Returns (gate_abs(k), the widest ``wk`` gate as a fraction of max|g64|)."""
-    WK = so().WK_NAMES
-    top = lambda k: float(ref['grads'][k].abs().max())
-    c32 = max(float((r32['grads'][k].double() - ref['grads'][k]).abs().max()) / ref['wk_scale'][k] for k in WK)
-
-    def gate_abs(k):
-        if k not in WK:
-            return 1e-4 * top(k)
-        return max(1e-4 * top(k), min(1e-4, 4.0 * c32) * ref['wk_scale'][k])
-    return gate_abs, max(gate_abs(k) / top(k) for k in WK)
 
 
 @pytest.fixture(scope='module')
@@ -332,7 +315,7 @@ def test_head_alone(trainers, case):
     qq = (pred[:, 0, -4:] ** 2).sum(1)
     if case == 'qq_quarter':
         assert float((qq - 0.25).abs().max()) <= 1e-6
-    gate_abs, widest = flat_gate(ref, so().grads(sd, p['x_t'], p['t'], p['zpo'], p['x0'], PAST, dtype=torch.float32, d_pred=d_pred))
+    gate_abs, widest = flat_gate(ref, so().grads(sd, p['x_t'], p['t'], p['zpo'], p['x0'], PAST, dtype=torch.float32, d_pred=d_pred), so().WK_NAMES)
     print('head alone, %s: pred vs fp64 %.3e; q.q in [%.3f, %.3f]; widest wk gate %.3e of max|g64|' % (
         case, rel(pred, ref['pred']), float(qq.min()), float(qq.max()), widest))
     compare_all(tr, ref, gate_abs, 'head alone, ' + case)
@@ -349,7 +332,7 @@ def test_shapes_vs_fp64(trainers, B, T, past):
     tr = trainer_for(trainers, past)
     pred, terms = tr.grads_at(d['x_t'], d['t'], d['zpo'], d['x0'])
     e_pred, e_cond, e_terms = rel(pred, ref['pred']), rel(tr.cond, ref['cond']), rel(terms, ref['terms'])
-    gate_abs, widest = flat_gate(ref, so().grads(weights(), p['x_t'], p['t'], p['zpo'], p['x0'], past, dtype=torch.float32))
+    gate_abs, widest = flat_gate(ref, so().grads(weights(), p['x_t'], p['t'], p['zpo'], p['x0'], past, dtype=torch.float32), so().WK_NAMES)
     print('B=%d T=%d past_len=%d: pred %.3e, cond %.3e, terms %.3e (1e-4); widest wk gate %.3e of max|g64|' % (B, T, past, e_pred, e_cond, e_terms, widest))
     compare_all(tr, ref, gate_abs, 'B=%d T=%d past_len=%d' % (B, T, past))
     assert e_pred <= 1e-4 and e_cond <= 1e-4 and e_terms <= 1e-4
