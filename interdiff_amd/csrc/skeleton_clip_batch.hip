@@ -2,10 +2,14 @@
 // windows in one launch.
 //
 // skeleton_video_prepare_kernel   data/dataset_skeleton.py:40-65, 85-104 and the down-sampling of :148-151 for every video of a set: one workgroup per video.
-//      1. the quaternion sign of get_consistent_poses (:53-65).  The reference flips frame i+1 when |s_i q_i - q_{i+1}| > |s_i q_i + q_{i+1}|, i.e. when
-//         s_i (q_i . q_{i+1}) < 0, so s_{i+1} = s_i * (d_i < 0 ? -1 : 1) with d_i the dot product of the RAW quaternions in double: a prefix parity.  The
-//         workgroup scans it in chunks of SKV_THREADS frames (ballot + popcount inside a wave, the waves' parities through LDS, a carry between chunks):
-//         integers only.  Frames that are no multiple of `stride` are read for this and for the contact sum, nothing else of them is touched.
+//      1. the quaternion sign of get_consistent_poses (:53-65).  The reference flips frame i+1 iff |s_i q_i - q_{i+1}| > |s_i q_i + q_{i+1}|, and otherwise
+//         leaves it AS STORED.  With d_i the dot product of the RAW quaternions in double that is: d_i < 0 -> s_{i+1} = -s_i; d_i > 0 -> s_{i+1} = s_i;
+//         a tie (d_i == 0: a zero quaternion, an orthogonal pair) or a NaN -> s_{i+1} = +1 whatever s_i was.  So the sign is a SEGMENTED prefix parity:
+//         a tie / NaN transition resets it.  The workgroup scans it in chunks of SKV_THREADS transitions: two ballots per wave (flip, reset); a lane with
+//         a reset at or below it counts the flips above the highest such reset and ignores what came before, any other lane counts the flips at or below
+//         it and adds the incoming parity; a wave's summary (has a reset, parity after its last reset) goes through LDS, and the waves and the carry
+//         between chunks are folded in order by the same composition: integers only, one pass.  Without a tie / NaN it is the plain prefix parity.
+//         Frames that are no multiple of `stride` are read for this and for the contact sum, nothing else of them is touched.
 //      2. the resident table fp32 [rows][3 J + 3 P + 7] = body | object | pose, row r = frame stride * r, the quaternion times its sign: every float64 is
 //         rounded once, so an entry is the reference's batch[i].float() bit for bit.
 //      3. zero_pose_obj = recover_init_obj on frame 0 (:40-51) in double, rounded once.
@@ -57,10 +61,12 @@ struct Video {
     int J, P, stride;
 };
 
-SK_HD int flip_bit(const double *pose, int64_t i) {          // does frame i + 1 change sign relative to frame i (a tie or a NaN keeps the sign)
+// what the transition frame i -> i + 1 does to the sign: 0 keeps it, 1 flips it, 2 resets it to + (a tie or a NaN: the reference's `>` is false, and it then
+// leaves frame i + 1 as stored -- it does NOT carry frame i's sign over)
+SK_HD int flip_bit(const double *pose, int64_t i) {
     const double *a = pose + 7 * i + 3, *b = a + 7;
     const double d = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-    return d < 0.0 ? 1 : 0;
+    return d < 0.0 ? 1 : (d > 0.0 ? 0 : 2);
 }
 
 SK_HD Quat unit_quat(const double *pose) {             // Rot.from_quat normalises
@@ -154,26 +160,34 @@ __global__ __launch_bounds__(SKV_THREADS) void skeleton_video_prepare_kernel(con
     const int W = 3 * J + 3 * P + 7;
     float *tab = table + r0 * W;
 
-    // 1. the sign of every frame: prefix parity of the flip bits, one chunk of SKV_THREADS transitions at a time
+    // 1. the sign of every frame: segmented prefix parity of the flip bits (a reset starts a new segment), one chunk of SKV_THREADS transitions at a time
     if (tid == 0) {
         write_pose_row(v, tab, W, 0, 0);
         if (signs) signs[f0] = 1;
     }
-    unsigned carry = 0;                                           // parity of the flips before this chunk (the same in every lane)
+    unsigned carry = 0;                                           // is the last frame before this chunk negated (the same in every lane)
     const int lane = tid & (IDF_WAVE - 1), wave = tid / IDF_WAVE;
     for (int64_t base = 0; base < F - 1; base += SKV_THREADS) {
         const int64_t i = base + tid;
-        const int bit = i < F - 1 ? flip_bit(v.pose, i) : 0;
-        const unsigned long long m = __ballot(bit);
-        unsigned par = (unsigned)__popcll(m & (~0ull >> (IDF_WAVE - 1 - lane))) & 1u;      // inclusive, inside the wave
-        if (lane == 0) wave_par[wave] = (unsigned)__popcll(m) & 1u;
+        const int kind = i < F - 1 ? flip_bit(v.pose, i) : 0;
+        const unsigned long long flips = __ballot(kind == 1), resets = __ballot(kind == 2);
+        const unsigned long long upto = ~0ull >> (IDF_WAVE - 1 - lane);                   // this lane and the ones below it
+        const unsigned long long mine = resets & upto;
+        // the flips that count for this lane: those above the highest reset at or below it (all of them without one); ((2 << h) - 1 covers bits 0 .. h, h = 63 too)
+        const unsigned long long after = mine ? ~((2ull << (63 - __clzll((long long)mine))) - 1ull) : ~0ull;
+        unsigned par = (unsigned)__popcll(flips & upto & after) & 1u;                      // inclusive, inside the wave
+        if (lane == 0) {
+            const unsigned long long tail = resets ? ~((2ull << (63 - __clzll((long long)resets))) - 1ull) : ~0ull;
+            wave_par[wave] = ((unsigned)__popcll(flips & tail) & 1u) | (resets ? 2u : 0u);   // bit 0: parity after the wave's last reset; bit 1: it has a reset
+        }
         __syncthreads();
         unsigned before = carry, total = carry;
         for (int w = 0; w < SKV_THREADS / IDF_WAVE; ++w) {
-            if (w < wave) before ^= wave_par[w];
-            total ^= wave_par[w];
+            const unsigned s = wave_par[w];
+            total = (s & 2u) ? (s & 1u) : (total ^ s);
+            if (w + 1 == wave) before = total;
         }
-        par ^= before;                                            // frame i + 1 is negated iff par
+        if (!mine) par ^= before;                                 // frame i + 1 is negated iff par; a reset at or below the lane cuts the incoming parity off
         if (i < F - 1) {
             if (signs) signs[f0 + i + 1] = par ? -1 : 1;
             if ((i + 1) % stride == 0) write_pose_row(v, tab, W, (i + 1) / stride, (int)par);
@@ -281,7 +295,8 @@ extern "C" int interdiff_debug_skeleton_video_prepare(const double *skel, const 
     write_pose_row(v, table, W, 0, 0);
     if (signs) signs[0] = 1;
     for (int64_t i = 0; i < F - 1; ++i) {
-        neg ^= flip_bit(pose, i);
+        const int kind = flip_bit(pose, i);
+        neg = kind == 2 ? 0 : neg ^ kind;
         if (signs) signs[i + 1] = neg ? -1 : 1;
         if ((i + 1) % stride == 0) write_pose_row(v, table, W, (i + 1) / stride, neg);
     }

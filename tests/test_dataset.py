@@ -1,6 +1,8 @@
 """interdiff_amd/dataset.py: the clip index and start draw (host), the per-clip canonicalisation math of csrc/clip_canon.h on its host instance
 (interdiff_debug_clip_canon) against scipy / ``data.canonicalize_clip``, and -- on the GPU -- ``DeviceClipSet.assemble`` against the reference's recorded
-``__getitem__`` outputs (tests/golden/etl.npz), the host route (``canonicalize_clip`` + ``clip_labels`` + ``collate_raw`` + ``body_records``) and the trainers."""
+``__getitem__`` outputs (tests/golden/etl.npz), the host route (``canonicalize_clip`` + ``clip_labels`` + ``collate_raw`` + ``body_records``) and the trainers;
+the canonicalisation kernel through every scipy branch on its 128-lane block (T = 65, 128) and the body-record kernel at every alignment phase of a frame's run
+(V = 1 .. 257), contact-list shape and ``frame_map``, both against scipy / numpy."""
 import functools
 import os
 import numpy as np
@@ -129,28 +131,60 @@ def yaw_frame(yaw):
     return (Rotation.from_euler('y', yaw) * Rotation.from_euler('x', 0.3)).as_rotvec()
 
 
+# The clip builders of the branch tests (host instance and device): every one draws from the ``rs`` it is handed, in a fixed order.
+def unit_rows(m):
+    return m / np.linalg.norm(m, axis=1, keepdims=True)
+
+
+def clip_for(rs, n, target, yaw):
+    """n + 1 frames: frame 0 fixes the heading; frames 1.. have root / object rotations ``R^-1 target`` so that the composition lands on ``target``."""
+    root0 = yaw_frame(yaw)
+    G = Rotation.from_rotvec(root0).as_matrix()
+    c, s = G[0, 0] / np.hypot(G[0, 0], G[2, 0]), G[2, 0] / np.hypot(G[0, 0], G[2, 0])
+    un = Rotation.from_matrix(np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]]).T)
+    aa = (un.inv() * target).as_rotvec()
+    fit = np.zeros((n + 1, 12))
+    fit[0, :3], fit[1:, :3], fit[1:, 6:9] = root0, aa, aa[::-1]
+    fit[:, 3:6], fit[:, 9:12] = rs.uniform(-2, 2, (n + 1, 3)), rs.uniform(-2, 2, (n + 1, 3))
+    pelvis = np.float32(fit[:, 3:6] + rs.uniform(-0.3, 0.3, (n + 1, 3)))
+    pose = np.float32(rs.uniform(-1, 1, (n + 1, 156)))
+    pose[:, :3] = fit[:, :3]
+    fit[:, :3] = pose[:, :3]                                               # poses are fp32 on disk
+    return fit, pelvis, pose
+
+
+def tiny_targets(rs, n):
+    """Composed angle < 1e-3: as_rotvec's series."""
+    return Rotation.from_rotvec(unit_rows(rs.standard_normal((n, 3))) * rs.uniform(1e-7, 9e-4, (n, 1)))
+
+
+def tiny_input_clip(rs, n):
+    """Input angle < 1e-3 (from_rotvec's series): heading ~0, tiny inputs."""
+    fit, pelvis, pose = clip_for(rs, n, Rotation.identity(n), 0.0)
+    small = np.float32(unit_rows(rs.standard_normal((n, 3))) * rs.uniform(1e-6, 9e-4, (n, 1)))
+    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = small, small, small[::-1] * 0.5
+    return fit, pelvis, pose
+
+
+def near_pi_targets(rs, n):
+    """Composed angle in (pi - 0.05, pi - 1e-3)."""
+    return Rotation.from_rotvec(unit_rows(rs.standard_normal((n, 3))) * rs.uniform(np.pi - 0.05, np.pi - 1e-3, (n, 1)))
+
+
+def w_negative_clip(rs, n):
+    """Composed w < 0: a large yaw removed from large rotations about (nearly) the same axis."""
+    big = Rotation.from_rotvec((unit_rows(np.array([[0.0, 1.0, 0.0]]) + 0.2 * rs.standard_normal((n, 3)))) * rs.uniform(2.4, 3.1, (n, 1)))
+    fit, pelvis, pose = clip_for(rs, n, Rotation.identity(n), -2.7)
+    aa = np.float32(big.as_rotvec())
+    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = aa, aa, aa[::-1]
+    return fit, pelvis, pose
+
+
 def test_clip_canon_host_instance_takes_every_scipy_branch():
     """64 random rotations per branch of scipy's route: composed angle < 1e-3 (and an input angle < 1e-3), composed angle in (pi - 0.05, pi), composed w < 0,
     and each of from_matrix's four cases (largest diagonal entry 0 / 1 / 2, trace) through ``rotation_override``.  Same gate, against scipy on float64."""
     rs = np.random.RandomState(42)
     n = 64
-    unit = lambda m: m / np.linalg.norm(m, axis=1, keepdims=True)
-
-    def clip_for(target, yaw):
-        """65 frames: frame 0 fixes the heading; frames 1.. have root / object rotations ``R^-1 target`` so that the composition lands on ``target``."""
-        root0 = yaw_frame(yaw)
-        G = Rotation.from_rotvec(root0).as_matrix()
-        c, s = G[0, 0] / np.hypot(G[0, 0], G[2, 0]), G[2, 0] / np.hypot(G[0, 0], G[2, 0])
-        un = Rotation.from_matrix(np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]]).T)
-        aa = (un.inv() * target).as_rotvec()
-        fit = np.zeros((n + 1, 12))
-        fit[0, :3], fit[1:, :3], fit[1:, 6:9] = root0, aa, aa[::-1]
-        fit[:, 3:6], fit[:, 9:12] = rs.uniform(-2, 2, (n + 1, 3)), rs.uniform(-2, 2, (n + 1, 3))
-        pelvis = np.float32(fit[:, 3:6] + rs.uniform(-0.3, 0.3, (n + 1, 3)))
-        pose = np.float32(rs.uniform(-1, 1, (n + 1, 156)))
-        pose[:, :3] = fit[:, :3]
-        fit[:, :3] = pose[:, :3]                                               # poses are fp32 on disk
-        return fit, pelvis, pose
 
     def check(fit, pelvis, pose, want_angle=None, want_w_neg=False):
         seq = dict(poses=pose.copy(), betas=np.zeros((n + 1, 10), np.float32), trans=fit[:, 3:6], obj_angles=fit[:, 6:9], obj_trans=fit[:, 9:12])
@@ -174,23 +208,15 @@ def test_clip_canon_host_instance_takes_every_scipy_branch():
 
     # composed angle < 1e-3 (as_rotvec's series), with yaw so that from_matrix takes the trace case and the m11 case
     for yaw in (0.4, 2.9):
-        tiny = Rotation.from_rotvec(unit(rs.standard_normal((n, 3))) * rs.uniform(1e-7, 9e-4, (n, 1)))
-        check(*clip_for(tiny, yaw), want_angle=lambda a: a < 1e-3)
+        check(*clip_for(rs, n, tiny_targets(rs, n), yaw), want_angle=lambda a: a < 1e-3)
     # input angle < 1e-3 (from_rotvec's series): heading ~0, tiny inputs
-    fit, pelvis, pose = clip_for(Rotation.identity(n), 0.0)
-    small = np.float32(unit(rs.standard_normal((n, 3))) * rs.uniform(1e-6, 9e-4, (n, 1)))
-    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = small, small, small[::-1] * 0.5
-    check(fit, pelvis, pose)
+    check(*tiny_input_clip(rs, n))
     # composed angle in (pi - 0.05, pi)
-    near_pi = Rotation.from_rotvec(unit(rs.standard_normal((n, 3))) * rs.uniform(np.pi - 0.05, np.pi - 1e-3, (n, 1)))
+    near_pi = near_pi_targets(rs, n)
     for yaw in (-1.1, 2.6):
-        check(*clip_for(near_pi, yaw), want_angle=lambda a: (a > np.pi - 0.05) & (a < np.pi))
+        check(*clip_for(rs, n, near_pi, yaw), want_angle=lambda a: (a > np.pi - 0.05) & (a < np.pi))
     # composed w < 0: a large yaw removed from large rotations about (nearly) the same axis
-    big = Rotation.from_rotvec((unit(np.array([[0.0, 1.0, 0.0]]) + 0.2 * rs.standard_normal((n, 3)))) * rs.uniform(2.4, 3.1, (n, 1)))
-    fit, pelvis, pose = clip_for(Rotation.identity(n), -2.7)
-    aa = np.float32(big.as_rotvec())
-    pose[1:, :3], fit[1:, :3], fit[1:, 6:9] = aa, aa, aa[::-1]
-    check(fit, pelvis, pose, want_w_neg=True)
+    check(*w_negative_clip(rs, n), want_w_neg=True)
     # from_matrix: each of the four cases, any rotation as `rotation`
     seen = set()
     for case in range(4):
@@ -468,3 +494,223 @@ def test_trainers_take_the_batch_as_it_comes_and_fit_drives_them(tmp_path):
         last = torch.load(os.path.join(d, 'last.pt'))
         now = tr.state_dict()
         assert all(torch.equal(now[n].cpu(), last[n].cpu()) for n in last)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ GPU: the kernels at their edges
+def one_sequence_set(fit, pelvis, pose, rs, P):
+    """One clip as a one-sequence ``DeviceClipSet`` (past 1, future T - 1) on injected joints -> (set, seq); the clip is start 0."""
+    from interdiff_amd.dataset import DeviceClipSet
+    T = len(fit)
+    none = [np.zeros(0, np.int64)] * T
+    seq = dict(poses=pose, betas=np.float32(rs.uniform(-1, 1, (T, 10))), trans=fit[:, 3:6], obj_angles=fit[:, 6:9], obj_trans=fit[:, 9:12],
+               obj_points=np.float32(rs.standard_normal((P, 6))), obj_contact_label=none, contact_label=none, ground_joint_label=np.full(T, 10, np.int64), gender='male',
+               obj_name='box', seq_name='Date01_Sub01_box_x')
+    feet = (np.float32(rs.uniform(-1, 1, (T, 3))), np.float32(rs.uniform(-1, 1, (T, 3))))
+    return DeviceClipSet([seq], None, 1, T - 1, device=DEV, joints=[(pelvis,) + feet]), seq
+
+
+def branch_clips(n, seed):
+    """The clips of the host branch test at n + 1 frames: [(name, (fit, pelvis, pose), branch)].  Joints 1, 2, 3 of every frame get axis-angles of exactly 0 and of
+    norms 1e-7 and 1e-5: both sides of the 1e-6 series switch of ``rot6d_of_axis_angle``."""
+    rs = np.random.RandomState(seed)
+    near_pi = near_pi_targets(rs, n)
+    clips = [('tiny composed, yaw 0.4 (from_matrix by trace)', clip_for(rs, n, tiny_targets(rs, n), 0.4), 'tiny'),
+             ('tiny composed, yaw 2.9 (from_matrix by m11)', clip_for(rs, n, tiny_targets(rs, n), 2.9), 'tiny'),
+             ('tiny input', tiny_input_clip(rs, n), 'input'),
+             ('near pi, yaw -1.1', clip_for(rs, n, near_pi, -1.1), 'pi'), ('near pi, yaw 2.6', clip_for(rs, n, near_pi, 2.6), 'pi'),
+             ('composed w < 0', w_negative_clip(rs, n), 'w')]
+    for _, (fit, pelvis, pose), _ in clips:
+        axes = unit_rows(rs.standard_normal((n + 1, 3)))
+        pose[:, 3:6], pose[:, 6:9], pose[:, 9:12] = 0.0, np.float32(axes * 1e-7), np.float32(axes[::-1] * 1e-5)
+    return clips
+
+
+def check_device_clip(name, branch, fit, pelvis, pose, bt, b, yaw_case=None):
+    """Column b of a device batch against ``canonicalize_clip`` (scipy on float64) at the ETL gate, the gt token against scipy matrices at 1e-6 absolute, and the
+    assertions that the branch was really taken.  Printed before asserted.  -> (worst error / gate, largest distance from the host twin)"""
+    n = len(fit) - 1
+    seq = dict(poses=pose.copy(), betas=np.zeros((n + 1, 10), np.float32), trans=fit[:, 3:6], obj_angles=fit[:, 6:9], obj_trans=fit[:, 9:12])
+    c = D.canonicalize_clip(seq, pelvis, 0, 1, n)
+    o = debug_canon(fit, pelvis, pose)
+    dev = dict(root=bt['body_pose'][:, b, :3], trans=bt['body_trans'][:, b], obj_angles=bt['obj_angles'][:, b], obj_trans=bt['obj_trans'][:, b], pelvis=bt['pelvis'][:, b])
+    dev = {k: v.cpu().numpy() for k, v in dev.items()}
+    gt = bt['gt'][b, 0].cpu().numpy()
+    refs = dict(root=c['pose'][:, :3], trans=c['trans'], obj_angles=c['obj_angles'], obj_trans=c['obj_trans'], pelvis=c['pelvis'])
+    worst, twin = 0.0, float(np.abs(gt.astype(np.float64) - o['gt']).max())
+    for k, ref in refs.items():
+        ref = np.asarray(ref, np.float64)
+        err, lim = float(np.abs(dev[k].astype(np.float64) - ref).max()), 1e-6 * max(1.0, float(np.abs(ref).max()))
+        worst, twin = max(worst, err / lim), max(twin, float(np.abs(dev[k].astype(np.float64) - o[k]).max()))
+        print('%s (T %d) %s: err %.3e, gate %.3e' % (name, n + 1, k, err, lim))
+    un = Rotation.from_matrix(c['rotation'])
+    six = lambda m: m[..., :2, :].reshape(n + 1, -1).T
+    joints = Rotation.from_rotvec(pose[:, 3:66].astype(np.float64).reshape(-1, 3)).as_matrix().reshape(n + 1, 21, 3, 3)
+    e_gt = {}
+    for what, rows, ref in (('root', slice(0, 6), six((un * Rotation.from_rotvec(fit[:, :3])).as_matrix())), ('joints', slice(6, 132), six(joints)),
+                            ('object', slice(135, 141), six((un * Rotation.from_rotvec(fit[:, 6:9])).as_matrix()))):
+        e_gt[what] = float(np.abs(gt[rows].astype(np.float64) - ref).max())
+        worst = max(worst, e_gt[what] / 1e-6)
+    print('%s (T %d) gt rows: root %.3e, joints %.3e, object %.3e (gate 1e-6); largest distance from the host twin %.3e' % (name, n + 1, e_gt['root'], e_gt['joints'], e_gt['object'], twin))
+    for k, ref in refs.items():
+        gate(dev[k], ref)
+    assert max(e_gt.values()) <= 1e-6, e_gt
+    assert np.allclose(bt['rotation'][b].cpu().numpy(), c['rotation']) and np.allclose(bt['centroid'][b].cpu().numpy(), c['centroid'])
+    # the branch is really taken
+    ang = np.linalg.norm(np.asarray(c['pose'][1:, :3], np.float64), axis=1)
+    if branch == 'tiny':
+        assert (ang < 1e-3).all(), ang
+        R = c['rotation']
+        assert int(np.argmax([R[0, 0], R[1, 1], R[2, 2], R[0, 0] + R[1, 1] + R[2, 2]])) == yaw_case, R
+    elif branch == 'input':
+        assert (np.linalg.norm(fit[1:, :3], axis=1) < 1e-3).all() and (np.linalg.norm(fit[1:, 6:9], axis=1) < 1e-3).all()
+    elif branch == 'pi':
+        assert ((ang > np.pi - 0.05) & (ang < np.pi)).all(), ang
+    else:
+        raw = _compose_w(un.as_quat(), Rotation.from_rotvec(fit[1:, :3]).as_quat())
+        assert (raw < 0).sum() >= n // 2, (raw < 0).sum()
+    small = np.linalg.norm(pose[:, 3:12].astype(np.float64).reshape(-1, 3, 3), axis=2)
+    assert (small[:, 0] == 0).all() and (small[:, 1] < 1e-6).all() and (small[:, 1] > 0).all() and (small[:, 2] > 1e-6).all() and (small[:, 2] < 1e-4).all()
+    return worst, twin
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('T,P', [(65, 1), (128, 64)])
+def test_clip_canon_device_takes_every_scipy_branch(T, P):
+    """C: the branch clips of the host test, each as a one-sequence ``DeviceClipSet``, on the 128-lane block (T = 65: the first size that takes it; T = 128: all its
+    lanes), P = 1 and P = 64 for the cloud copy; then the near-pi clip twice in a B = 3 batch with the tiny-angle clip between, so that neighbouring workgroups take
+    different branches.  Against scipy on float64: raw fields at the ETL gate, gt rows at 1e-6 absolute.  The distance from the host twin is printed, not asserted.
+    Measured on the MI355X: worst error 0.118 of its gate at T = 65 and 0.105 at T = 128 (a translation; the gt rows stay below 3.0e-8 = 0.03 of theirs).  The
+    device's largest distance from the host twin is 8.9e-16, on one clip (near pi, yaw -1.1) and 0 on the others: the device's double sin / cos / atan2 / sqrt do
+    NOT always round to the host's fp32, but a difference that small can only sit in an entry below ~1.5e-8 in magnitude (one fp32 ulp there), i.e. rounding noise
+    of an entry that is zero in exact arithmetic."""
+    from interdiff_amd.dataset import DeviceClipSet
+    n = T - 1
+    assert T > 64                                                                  # the launcher takes the 128-lane block above 64 frames
+    clips = branch_clips(n, 4200 + T)
+    rs = np.random.RandomState(T)
+    worst, twin, seqs, joints = 0.0, 0.0, {}, {}
+    for k, (name, (fit, pelvis, pose), branch) in enumerate(clips):
+        cs, seq = one_sequence_set(fit, pelvis, pose, rs, P)
+        assert cs.T == T and cs.P == P
+        bt = cs.assemble([0], [0], body=False)
+        w, d = check_device_clip(name, branch, fit, pelvis, pose, bt, 0, yaw_case={0: 3, 1: 1}.get(k))
+        worst, twin = max(worst, w), max(twin, d)
+        assert torch.equal(bt['obj_points6'].cpu(), torch.from_numpy(seq['obj_points'])[None]) and torch.equal(bt['obj_points'], bt['obj_points6'][..., :3])
+        assert torch.equal(bt['hand_pose'][:, 0].cpu(), torch.from_numpy(pose[:, 66:])) and torch.equal(bt['body_pose'][:, 0, 3:].cpu(), torch.from_numpy(pose[:, 3:66]))
+        assert torch.equal(bt['beta'][:, 0].cpu(), torch.from_numpy(seq['betas']))
+        seqs[k], joints[k] = seq, (pelvis, cs.t['joints'].cpu().numpy().reshape(T, 3, 3)[:, 1], cs.t['joints'].cpu().numpy().reshape(T, 3, 3)[:, 2])
+    both = DeviceClipSet([seqs[3], seqs[0]], None, 1, n, device=DEV, joints=[joints[3], joints[0]])
+    bt = both.assemble([0, 1, 0], [0, 0, 0], body=False)
+    for b, k in enumerate((3, 0, 3)):
+        name, (fit, pelvis, pose), branch = clips[k]
+        w, d = check_device_clip('B = 3, column %d: %s' % (b, name), branch, fit, pelvis, pose, bt, b, yaw_case=3)
+        worst, twin = max(worst, w), max(twin, d)
+    assert torch.equal(bt['gt'][0], bt['gt'][2]) and not torch.equal(bt['gt'][0], bt['gt'][1])
+    print('clip_canon on the device, T %d: worst error %.3f of its gate; largest distance from interdiff_debug_clip_canon %.3e' % (T, worst, twin))
+
+
+def record_case(V, seed):
+    """A one-sequence set of F = 6 frames on a V-vertex mesh (T = 4, B = 2: clips at starts 0 and 2, so T B = 8 frames) whose contact lists are: empty; one vertex
+    twice; vertex V - 1; more than 256 entries when V = 257 (every even vertex twice, then 256 and 0 again); a random list; a random list plus V - 1.
+    -> (set, lists, clips tensor [2,B], ids, starts)"""
+    from interdiff_amd.dataset import DeviceClipSet
+    rs = np.random.RandomState(seed)
+    F = 6
+    even = np.arange(0, V, 2)
+    lists = [np.zeros(0, np.int64), np.array([V // 2, V // 2]), np.array([V - 1]), np.concatenate([even, even, [V - 1, 0]]) if V == 257 else rs.randint(0, V, 3),
+             rs.randint(0, V, max(1, V // 3)), np.concatenate([rs.randint(0, V, max(1, V // 2)), [V - 1]])]
+    assert V != 257 or len(lists[3]) > 256
+    seq = dict(poses=np.float32(rs.uniform(-1, 1, (F, 156))), betas=np.zeros((F, 10), np.float32), trans=rs.uniform(-1, 1, (F, 3)), obj_angles=rs.uniform(-1, 1, (F, 3)),
+               obj_trans=rs.uniform(-1, 1, (F, 3)), obj_points=np.float32(rs.standard_normal((4, 6))), obj_contact_label=[np.zeros(0, np.int64)] * F, contact_label=lists,
+               ground_joint_label=np.full(F, 11, np.int64), gender='male', obj_name='box', seq_name='Date01_Sub01_box_r')
+    jt = tuple(np.float32(rs.uniform(-1, 1, (F, 3))) for _ in range(3))
+    markers = [0, V - 1, V // 2, 0]
+    cs = DeviceClipSet([seq], None, 2, 2, device=DEV, joints=[jt], n_verts=V, markers=markers)
+    ids, starts = [0, 0], [0, 2]
+    clips = torch.from_numpy(np.stack([ids, starts]).astype(np.int32)).to(DEV)
+    return cs, lists, markers, clips, ids, starts
+
+
+SENTINEL, SENTINEL_U8 = -777.0, 9
+
+
+def run_records(cs, clips, B, T, verts, normals, fmap, out=None, hv_offset=0, n_frames=None):
+    """``interdiff_clip_body_records`` as ``DeviceClipSet.assemble`` calls it, on sentinel-filled outputs (or on ``out``) -> (return code, (human_verts, markers, labels))"""
+    import ctypes as C
+    from interdiff_amd import _lib
+    V = cs.V
+    if out is None:
+        out = (torch.full((T, B, V, 7), SENTINEL, device=DEV), torch.full((T, B, cs.n_markers, 7), SENTINEL, device=DEV),
+               torch.full((T, B, V), SENTINEL_U8, dtype=torch.uint8, device=DEV))
+    dv, dn = torch.from_numpy(verts).to(DEV), torch.from_numpy(normals).to(DEV)
+    dm = None if fmap is None else torch.tensor(fmap, dtype=torch.int32, device=DEV)
+    rc = cs.lib.interdiff_clip_body_records(C.byref(cs.cset), _lib.dptr(clips, torch.int32), B, T, 1, _lib.dptr(dv, torch.float32), _lib.dptr(dn, torch.float32),
+                                            _lib.dptr(dm, torch.int32, allow_none=True), len(verts) if n_frames is None else n_frames,
+                                            C.c_void_p(out[0].data_ptr() + hv_offset), _lib.dptr(out[1]), _lib.dptr(out[2]), _lib.stream())
+    torch.cuda.synchronize()
+    return rc, out
+
+
+def numpy_records(lists, V, markers, B, T, starts, verts, normals, frames):
+    """[v | n | label] per vertex of the destination frames ``frames`` (n = t B + b, source frame starts[b] + t), markers = rows of it; every other frame the
+    sentinel -> (human_verts [T,B,V,7], markers [T,B,M,7], labels [T,B,V])"""
+    hv, lab = np.full((T * B, V, 7), SENTINEL, np.float32), np.full((T * B, V), SENTINEL_U8, np.uint8)
+    mk = np.full((T * B, len(markers), 7), SENTINEL, np.float32)
+    for i, nn in enumerate(frames):
+        t, b = divmod(nn, B)
+        lab[nn] = 0
+        lab[nn][np.asarray(lists[starts[b] + t], np.int64)] = 1
+        hv[nn] = np.concatenate([verts[i], normals[i], lab[nn][:, None].astype(np.float32)], axis=1)
+        mk[nn] = hv[nn][markers]
+    return hv.reshape(T, B, V, 7), mk.reshape(T, B, len(markers), 7), lab.reshape(T, B, V)
+
+
+def same_records(got, want):
+    return all(np.array_equal(np.ascontiguousarray(g.cpu().numpy()).view(np.uint8), np.ascontiguousarray(w).view(np.uint8)) for g, w in zip(got, want))
+
+
+@pytest.mark.gpu
+def test_body_records_at_every_alignment_list_shape_and_frame_map():
+    """D: ``interdiff_clip_body_records`` called directly on V = 1, 2, 3, 5, 7, 257 (T B = 8 frames): an odd V starts consecutive frames 0, 3, 2, 1 floats off a
+    16-byte quad, V = 257 is more vertices (and a longer contact list) than the workgroup has lanes.  Bit-equal to numpy; under a ``frame_map`` every float outside
+    the named frames keeps its sentinel.  Then the labels-only path and the refusals."""
+    import ctypes as C
+    from interdiff_amd import _lib
+    B, T = 2, 4
+    starts_seen, ends_seen = set(), set()
+    for V in (1, 2, 3, 5, 7, 257):
+        cs, lists, markers, clips, ids, starts = record_case(V, 60 + V)
+        rs = np.random.RandomState(V)
+        verts, normals = np.float32(rs.standard_normal((T * B, V, 3))), np.float32(rs.standard_normal((T * B, V, 3)))
+        every = list(range(T * B))
+        rc, full = run_records(cs, clips, B, T, verts, normals, None)
+        want = numpy_records(lists, V, markers, B, T, starts, verts, normals, every)
+        assert rc == 0 and same_records(full, want), V
+        assert not (want[0] == SENTINEL).any() and (want[2] <= 1).all()
+        for nn in every:
+            starts_seen.add((V, 7 * V * nn % 4))
+            ends_seen.add((V, 7 * V * (nn + 1) % 4))
+        labels = want[2]
+        assert labels[1, 0].sum() == 1 and labels[0, 0].sum() == 0 and labels[0, 1, V - 1] == 1 and labels[2, 0, V - 1] == 1      # the doubled vertex, the empty list, V - 1
+        # frame_map: the last slot alone; a strict subset in descending order; two disjoint subsets in two calls
+        for fmap in ([T * B - 1], [6, 3, 1]):
+            rc, got = run_records(cs, clips, B, T, verts[fmap], normals[fmap], fmap)
+            assert rc == 0 and same_records(got, numpy_records(lists, V, markers, B, T, starts, verts[fmap], normals[fmap], fmap)), (V, fmap)
+        first, second = [7, 2, 4, 0], [1, 3, 5, 6]
+        rc, got = run_records(cs, clips, B, T, verts[first], normals[first], first)
+        rc2, got = run_records(cs, clips, B, T, verts[second], normals[second], second, out=got)
+        assert rc == 0 and rc2 == 0 and all(torch.equal(a, b) for a, b in zip(got, full)), V
+        if V in (1, 257):                                                             # the labels-only kernel, through ``assemble(body=False)``
+            lab = cs.assemble(ids, starts, body=False)['contact_label']
+            assert lab.dtype == torch.uint8 and np.array_equal(lab.cpu().numpy(), want[2]), V
+        if V == 5:                                                                    # refusals: host return codes, the outputs keep the sentinel
+            for kw in (dict(hv_offset=4), dict(n_frames=T * B + 1)):
+                rc, got = run_records(cs, clips, B, T, verts, normals, None, **kw)
+                assert rc == -22 and all(bool((g == s).all()) for g, s in zip(got, (SENTINEL, SENTINEL, SENTINEL_U8))), kw
+            rc, got = run_records(cs, clips, B, 129, verts, normals, None)
+            assert rc == -22
+    odd = {V for V in (1, 3, 5, 7, 257)}
+    print('record runs: start phases %s, end phases %s' % (sorted({p for _, p in starts_seen}), sorted({p for _, p in ends_seen})))
+    for V in odd:
+        assert {p for v, p in starts_seen if v == V} == {0, 1, 2, 3} and {p for v, p in ends_seen if v == V} == {0, 1, 2, 3}, V
+    assert {p for v, p in starts_seen if v == 2} == {0, 2}

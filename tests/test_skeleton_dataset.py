@@ -8,6 +8,11 @@ within 1e-12 max(1, ref) (two float64 evaluations of the same ~250-term mean in 
 ``skeleton_evaluate`` on fake pieces.  GPU: the device prepare against the host instance bit for bit; ``assemble`` at B = 1, 3, 4 (one window twice) and 70 against the reference's windows bit
 for bit; the call contract; the three skeleton trainers; ``fit``; ``skeleton_evaluate``.
 
+The kernels at their edges, on seeded synthetic videos (``synth_video``; references: a sequential numpy loop of get_consistent_poses' rule, scipy ``Rotation``, numpy):
+flips on the wave seam (63 | 64) and the chunk seam (255 | 256) of the sign scan, in runs, F = 1 and 2, stride 1 and 7, P = 1 and 64; degenerate transitions (a zero
+quaternion, a NaN quaternion, an exactly orthogonal pair), after which the reference leaves the next frame as stored -- host instance on the CPU, device on the GPU,
+all videos of a geometry in one launch; the window kernel at W odd (no padding column), T = 1 and 128, a 65,224 B tile, B = 1 and 65.
+
 The skeleton / object arrays are NaN in every frame that is no multiple of 12 -- the reference reads none of them -- so a kernel that does shows in its own output.
 Without the feature every test below fails: the module, the loops and the entries do not exist.
 """
@@ -17,6 +22,7 @@ import pickle
 import numpy as np
 import pytest
 import torch
+from scipy.spatial.transform import Rotation
 from tests import fixtures as fx
 from tests.test_dataset import gate
 
@@ -197,6 +203,173 @@ def test_host_prepare_instance_matches_the_reference():
         assert abs(p['report'].quat_check) < 1e-4
         assert abs(p['report'].quat_check - float((np.linalg.norm(z[k + 'pose'][::STRIDE, 3:], axis=-1) - 1).sum())) < 1e-13
     assert host_prepared()[3]['report'].discrepancy >= 5e-2 and all(host_prepared()[v]['report'].discrepancy < 1e-3 for v in (0, 1, 2, 4, 5))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ synthetic adversarial videos
+# (F, J, P, stride, flips): transition i = frames i | i + 1.  Flips sit on the wave seam (63 | 64), the chunk seam (255 | 256), in runs, at the ends; F = 1 and 2;
+# stride 1 and a stride that does not divide 256; P = 1 and P = 64 (the LDS limit of the kernel's double zero pose).
+GEOMETRIES = ((21, 12, 12), (1, 1, 1), (3, 64, 7))
+A1_CASES = (
+    (1, 21, 12, 12, ()), (2, 21, 12, 12, (0,)), (13, 21, 12, 12, (11,)), (64, 21, 12, 12, (62,)), (65, 21, 12, 12, (62, 63)), (66, 21, 12, 12, (63, 64)),
+    (256, 21, 12, 12, (254,)), (257, 21, 12, 12, (254, 255)), (258, 21, 12, 12, (255, 256)), (513, 21, 12, 12, (0, 63, 64, 127, 128, 255, 256, 257, 511)),
+    (700, 21, 12, 12, tuple(range(699))), (700, 21, 12, 12, tuple(range(0, 699, 2))), (300, 1, 1, 1, (5, 6, 7, 255)), (300, 3, 64, 7, (100, 255, 256)),
+    (523, 21, 12, 12, (191, 192, 319, 383, 447, 448, 511, 512, 521)))
+# On top of the fifteen: ONE flip early on, so that an odd parity is carried across every chunk seam (and wave seam) after it.  In the fifteen the flips before
+# a chunk seam are mostly even in number, and a scan that dropped the carry between chunks would pass all of them but F = 258 and F = 523.
+CARRY_CASES = ((700, 21, 12, 12, (3,)), (300, 1, 1, 1, (10,)), (300, 3, 64, 7, (10,)))
+# A2: (F, J, P, stride, flips, degenerate frames {frame: kind}).  'zero' / 'nan' replace ONE frame's quaternion (both its transitions are degenerate) and sit off
+# the sampled frames; 'ortho' replaces frames f and f + 1 by two different basis quaternions (d_f == 0 exactly; valid unit quaternions, so also on sampled frames).
+# Every degenerate frame follows an odd number of flips since the last reset, which is where the reference's rule and a pure parity part.
+A2_CASES = (
+    (400, 21, 12, 12, (5, 100), {64: 'zero', 256: 'nan'}),
+    (300, 21, 12, 12, (3, 70, 200), {63: 'ortho', 131: 'ortho', 255: 'ortho'}),           # frame 132 = row 11 is the second of an orthogonal pair
+    (300, 1, 1, 1, (3, 70, 200), {63: 'ortho', 131: 'ortho', 255: 'ortho'}),
+    (300, 3, 64, 7, (9, 80, 150), {64: 'zero', 100: 'ortho', 256: 'nan'}))
+SIX_FRAMES = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1], [np.nan] * 4, [0, 0, 0, -1]], np.float64)
+
+
+def synth_video(F, J, P, stride, flips, seed, degenerate=None, quats=None):
+    """A slowly drifting unit-quaternion track, continuous (every consecutive dot product > 0), then negated from frame i + 1 on for every i of ``flips`` -- the
+    stored data needs exactly those flips undone -- then the degenerate frames.  obj = t + R(q) z for a seeded z; skeleton and the 0/1 contact column random.
+    Skeleton and obj are NaN off the sampled frames, as in ``recorded``.  ``quats``: the stored quaternions given outright.  -> (video dict, sign the flips imply)"""
+    rs = np.random.RandomState(seed)
+    q, cur = np.empty((F, 4)), rs.standard_normal(4)
+    for i in range(F):
+        cur = cur + 0.02 * rs.standard_normal(4)
+        cur = cur / np.linalg.norm(cur)
+        q[i] = cur if i == 0 or cur @ q[i - 1] > 0 else -cur
+    for f, kind in sorted((degenerate or {}).items()):
+        if kind == 'ortho':                                                        # the two largest components of the track there, signs kept: the neighbours' dots stay large
+            a, b = np.argsort(-np.abs(q[f]))[:2]
+            q[f], q[f + 1] = np.eye(4)[a] * np.sign(q[f, a]), np.eye(4)[b] * np.sign(q[f, b])
+    implied = np.ones(F)
+    for i in flips:
+        implied[i + 1:] *= -1
+    q = q * implied[:, None]
+    for f, kind in (degenerate or {}).items():
+        if kind != 'ortho':
+            assert f % stride, 'a zero or NaN quaternion on a sampled frame has no rotation'
+            q[f] = 0.0 if kind == 'zero' else np.nan
+    if quats is not None:
+        q = np.array(quats, np.float64)
+    t = np.cumsum(0.01 * rs.standard_normal((F, 3)), axis=0) + rs.uniform(-1, 1, 3)
+    z = rs.standard_normal((P, 3))
+    obj, skel = np.full((F, P, 3), np.nan), np.full((F, J, 3), np.nan)
+    obj[::stride] = t[::stride, None] + np.einsum('fij,pj->fpi', Rotation.from_quat(q[::stride]).as_matrix(), z)
+    skel[::stride] = rs.standard_normal((len(skel[::stride]), J, 3))
+    video = dict(skeleton=skel, obj=obj, pose=np.concatenate([t, q], axis=1), contact=rs.randint(0, 2, (F, 1)).astype(np.float64), filename='sub%d_box_%03d' % (seed, F),
+                 obj_name='box')
+    return video, implied
+
+
+def reference_signs(quat):
+    """get_consistent_poses' rule, one frame after the other on float64 norms: frame i + 1 is negated iff the corrected frame i is farther from it than from its
+    negative; in every other case (a tie, a NaN) it is left as stored."""
+    sign = np.ones(len(quat), np.int8)
+    for i in range(len(quat) - 1):
+        prev = sign[i] * quat[i]
+        if np.linalg.norm(prev - quat[i + 1]) > np.linalg.norm(prev + quat[i + 1]):
+            sign[i + 1] = -1
+    return sign
+
+
+def synth_reference(video, stride):
+    """Signs by the loop above, the table as float32 of the strided sign-corrected rows, zero_pose_obj and the discrepancy through scipy ``Rotation`` on float64,
+    check sum and contact sums by numpy."""
+    pose, obj = video['pose'], video['obj']
+    sign = reference_signs(pose[:, 3:])
+    rows = pose[::stride].copy()
+    rows[:, 3:] *= sign[::stride, None]
+    n = len(rows)
+    table = np.concatenate([video['skeleton'][::stride].reshape(n, -1), obj[::stride].reshape(n, -1), rows], axis=1).astype(np.float32)
+    zpo = Rotation.from_quat(pose[0, 3:]).inv().apply(obj[0] - pose[0, :3])
+    pred = pose[::stride, None, :3] + np.stack([Rotation.from_quat(qq).apply(zpo) for qq in pose[::stride, 3:]])
+    return dict(signs=sign, table=table, zero_pose_obj=zpo, discrepancy=float(np.linalg.norm(pred - obj[::stride], axis=-1).mean()),
+                quat_check=float((np.linalg.norm(pose[::stride, 3:], axis=-1) - 1).sum()), contact_sum=float(video['contact'].sum()), row_contact=video['contact'][::stride, 0])
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_videos():
+    """Every A1 and A2 video with its geometry, its references and what the host instance makes of it: [dict(name, geom, video, implied, degenerate, ref, host)].
+    Computed once, never modified."""
+    cases = [('A1.%d' % k, c[:4], c[4], None, None) for k, c in enumerate(A1_CASES)] + [('A2.%d' % k, c[:4], c[4], c[5], None) for k, c in enumerate(A2_CASES)]
+    cases += [('carry.%d' % k, c[:4], c[4], None, None) for k, c in enumerate(CARRY_CASES)]
+    cases.append(('A2.six', (6, 21, 12, 12), (), None, SIX_FRAMES))
+    out = []
+    for k, (name, (F, J, P, stride), flips, degenerate, quats) in enumerate(cases):
+        video, implied = synth_video(F, J, P, stride, flips, 500 + k, degenerate, quats)
+        host = sd_mod().prepare_host(video, stride=stride, n_joints=J, n_points=P)
+        out.append(dict(name=name, geom=(J, P, stride), video=video, implied=implied, degenerate=bool(degenerate) or quats is not None, ref=synth_reference(video, stride),
+                        host=host))
+    return out
+
+
+def check_transitions(item):
+    """What the tests assert about their own inputs: a transition is either far from a tie (|d| >= 1e-3, where the dot-sign form and the norm comparison must
+    agree) or EXACTLY degenerate (d == 0 or NaN).  -> the number of degenerate transitions"""
+    q = item['video']['pose'][:, 3:]
+    d = (q[:-1] * q[1:]).sum(1)
+    exact = np.isnan(d) | (d == 0.0)
+    assert (np.abs(d[~exact]) >= 1e-3).all(), (item['name'], np.abs(d[~exact]).min())
+    assert bool(exact.any()) == item['degenerate'], item['name']
+    if not item['degenerate']:
+        assert np.array_equal(item['ref']['signs'], item['implied']), item['name']      # the generator's flips are what the reference's rule undoes
+    return int(exact.sum())
+
+
+def check_prepared(item, got, what):
+    """The A1 assertions on one video: ``got`` = dict(table, zero_pose_obj, report, signs) of the host instance or of the device.  Printed before asserted."""
+    ref, (J, P, stride) = item['ref'], item['geom']
+    F = len(item['video']['pose'])
+    rep = got['report']
+    e_z = float(np.abs(got['zero_pose_obj'].astype(np.float64) - ref['zero_pose_obj']).max())
+    e_d, e_c = abs(rep.discrepancy - ref['discrepancy']), abs(rep.quat_check - ref['quat_check'])
+    print('%s %s (F %d, J %d, P %d, stride %d): %d negated frames, %d signs differ, zero_pose_obj err %.2e (gate %.1e), discrepancy diff %.2e (gate %.1e), check sum diff %.2e'
+          % (what, item['name'], F, J, P, stride, int((got['signs'] < 0).sum()), int((got['signs'] != ref['signs']).sum()), e_z,
+             1e-6 * max(1.0, float(np.abs(ref['zero_pose_obj']).max())), e_d, 1e-12 * max(1.0, ref['discrepancy']), e_c))
+    assert got['signs'].shape == (F,) and np.array_equal(got['signs'], ref['signs']), item['name']
+    assert got['table'].dtype == np.float32 and got['table'].shape == ref['table'].shape == (-(-F // stride), 3 * (J + P) + 7)
+    assert np.array_equal(got['table'].view(np.uint32), ref['table'].view(np.uint32)), item['name']
+    gate(got['zero_pose_obj'], ref['zero_pose_obj'])
+    assert e_d <= 1e-12 * max(1.0, ref['discrepancy']) and e_c < 1e-13, item['name']
+    assert rep.contact_sum == ref['contact_sum'] and np.array_equal(rep.row_contact, ref['row_contact']), item['name']
+
+
+def test_host_prepare_on_adversarial_videos_matches_the_references():
+    """A1: the fifteen (F, J, P, stride, flips) cases -- flips on the wave seam, on the chunk seam, in runs, F = 1 and 2, stride 1 and 7, P = 1 and 64 -- on the host
+    instance against the sequential sign loop, scipy and numpy.  None has a degenerate transition."""
+    items = [it for it in synthetic_videos() if it['name'].startswith('A1')]
+    assert len(items) == 15 and [len(it['video']['pose']) for it in items] == [c[0] for c in A1_CASES]
+    for it in items:
+        assert check_transitions(it) == 0
+        check_prepared(it, it['host'], 'host')
+    assert int((items[10]['ref']['signs'] < 0).sum()) == 350 and int((items[11]['ref']['signs'] < 0).sum()) == 350      # every / every second transition
+    for it in [it for it in synthetic_videos() if it['name'].startswith('carry')]:
+        assert check_transitions(it) == 0 and it['ref']['signs'][256] == -1 and it['ref']['signs'][-1] == -1
+        check_prepared(it, it['host'], 'host')
+
+
+def test_host_prepare_follows_the_reference_on_degenerate_transitions():
+    """A2: after a tie or a NaN the reference leaves the next frame as stored (+1), whatever the sign before; a pure prefix parity carries a -1 over.  The six
+    quoted frames, and longer videos with a zero quaternion, a NaN quaternion and exactly orthogonal basis pairs after an odd number of flips -- one degenerate
+    transition at 63 | 64 and one at 255 | 256 in each, an orthogonal pair on a sampled row, stride 1 included.  Fails with the pure-parity recurrence."""
+    items = [it for it in synthetic_videos() if it['name'].startswith('A2')]
+    assert len(items) == 5
+    six = items[-1]
+    assert six['ref']['signs'].tolist() == [1, 1, -1, 1, 1, 1]
+    for it in items:
+        n = check_transitions(it)
+        q = it['video']['pose'][:, 3:]
+        d = (q[:-1] * q[1:]).sum(1)
+        exact = np.nonzero(np.isnan(d) | (d == 0.0))[0]
+        parity = np.concatenate([[1], np.where(np.cumsum(np.nan_to_num(d) < 0) % 2, -1, 1)])          # what carrying the sign over a tie would give
+        print('%s: %d degenerate transitions at %s; the reference and a pure parity differ on %d frames' % (it['name'], n, exact.tolist(), int((parity != it['ref']['signs']).sum())))
+        assert (parity != it['ref']['signs']).any()                                                   # the case does tell the two rules apart
+        entered = [int(it['ref']['signs'][i]) for i in exact[np.r_[True, np.diff(exact) > 1]]]        # the reference's sign on entering each degenerate stretch
+        assert -1 in entered and (it is six or set(entered) == {-1}), (it['name'], entered)
+        if it is not six:
+            assert 63 in exact and 255 in exact
+        check_prepared(it, it['host'], 'host')
 
 
 class FakeSet:
@@ -425,3 +598,131 @@ def test_skeleton_evaluate_equals_the_hand_written_loop():
         assert sorted(got) == sorted(want) and all(np.isfinite(v) for v in got.values())
         for k in want:
             assert abs(got[k] - want[k]) <= 1e-12 * max(1.0, abs(want[k])), k      # the same products, summed by Python instead of numpy
+
+
+# ------------------------------------------------------------------------------------------------------------------------ GPU: the kernels at their edges
+def device_prepare(videos, J, P, stride):
+    """``SkeletonClipSet.__init__``'s call of ``interdiff_skeleton_video_prepare`` with a ``signs`` buffer (the class passes None): every video of one geometry in
+    ONE launch, side by side behind seq_off / row_off.  -> per video dict(table, zero_pose_obj, report, signs) on the host"""
+    from interdiff_amd import _lib
+    m = sd_mod()
+    parts = [m._video_arrays(v, k, J, P) for k, v in enumerate(videos)]
+    counts = [F for F, _ in parts]
+    rows = [-(-F // stride) for F in counts]
+    seq_off, row_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    n, R, W = len(videos), int(row_off[-1]), 3 * (J + P) + 7
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    raw = [up(np.concatenate([a[i].reshape(F, -1) for F, a in parts])) for i in range(4)]
+    d_seq, d_row = up(seq_off), up(row_off)
+    table, zpo = torch.full((R, W), np.nan, dtype=torch.float32, device=DEV), torch.full((n, P, 3), np.nan, dtype=torch.float32, device=DEV)
+    report, rc = torch.full((n, 3), np.nan, dtype=torch.float64, device=DEV), torch.full((R,), np.nan, dtype=torch.float64, device=DEV)
+    signs = torch.zeros(int(seq_off[-1]), dtype=torch.int8, device=DEV)
+    _lib.check(_lib.load().interdiff_skeleton_video_prepare(*[_lib.dptr(a, torch.float64) for a in raw], _lib.dptr(d_seq, torch.int64), _lib.dptr(d_row, torch.int64), n, J, P,
+                                                            stride, _lib.dptr(table), _lib.dptr(zpo), _lib.dptr(report), _lib.dptr(rc), signs.data_ptr(), _lib.stream()),
+               'skeleton_video_prepare')
+    table, zpo, report, rc, signs = (t.cpu().numpy() for t in (table, zpo, report, rc, signs))
+    return [dict(table=table[row_off[k]:row_off[k + 1]], zero_pose_obj=zpo[k], signs=signs[seq_off[k]:seq_off[k + 1]],
+                 report=m.VideoReport(float(report[k, 0]), float(report[k, 1]), float(report[k, 2]), rc[row_off[k]:row_off[k + 1]])) for k in range(n)]
+
+
+def same_bits(got, host):
+    return (np.array_equal(got['table'].view(np.uint32), host['table'].view(np.uint32)) and np.array_equal(got['zero_pose_obj'].view(np.uint32), host['zero_pose_obj'].view(np.uint32))
+            and tuple(got['report'][:3]) == tuple(host['report'][:3]) and np.array_equal(got['report'].row_contact, host['report'].row_contact)
+            and np.array_equal(got['signs'], host['signs']))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('geom', GEOMETRIES)
+def test_device_prepare_on_adversarial_videos_gives_the_host_bits_and_the_references(geom):
+    """A4: every A1 and A2 video of one geometry in one launch (F from 1 to 700 side by side): table, zero_pose_obj, the three report doubles, the row contacts and
+    the signs ``==`` the host instance's, and the A1 assertions against the sequential sign loop / scipy / numpy hold for the device's own output."""
+    items = [it for it in synthetic_videos() if it['geom'] == geom]
+    assert len(items) == {(21, 12, 12): 17, (1, 1, 1): 3, (3, 64, 7): 3}[geom] and any(it['degenerate'] for it in items) and not all(it['degenerate'] for it in items)
+    got = device_prepare([it['video'] for it in items], *geom)
+    for it, g in zip(items, got):
+        print('%s: device report (%.17g, %.17g, %.17g); host (%.17g, %.17g, %.17g); %d signs differ from the host instance'
+              % ((it['name'],) + tuple(g['report'][:3]) + tuple(it['host']['report'][:3]) + (int((g['signs'] != it['host']['signs']).sum()),)))
+    for it, g in zip(items, got):
+        assert same_bits(g, it['host']), it['name']
+        check_prepared(it, g, 'device')
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_set(geom, window, hop=None):
+    J, P, stride = geom
+    items = [it for it in synthetic_videos() if it['geom'] == geom]
+    cs = sd_mod().SkeletonClipSet([it['video'] for it in items], window=window, stride=stride, hop=hop or stride, n_joints=J, n_points=P, device=DEV)
+    return cs, items
+
+
+def check_windows(cs, hosts, ids, starts):
+    """``assemble`` against plain slicing of the host instance's tables: everything bit-equal, ``gt`` the transpose."""
+    bt = cs.assemble(ids, starts)
+    T, J, P = cs.T, cs.J, cs.P
+    want = np.stack([hosts[k]['table'][r:r + T] for k, r in zip(ids, starts)])
+    assert want.shape == (len(ids), T, cs.W)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    for name, got, ref in (('body', bt[0], want[..., :3 * J].reshape(-1, T, J, 3)), ('obj', bt[1], want[..., 3 * J:3 * (J + P)].reshape(-1, T, P, 3)),
+                           ('pose', bt[2], want[..., 3 * (J + P):]), ('zero_pose_obj', bt[3], np.stack([hosts[k]['zero_pose_obj'] for k in ids])),
+                           ('gt', bt.gt, want.transpose(0, 2, 1)[:, None])):
+        assert got.dtype == torch.float32 and got.is_contiguous() and tuple(got.shape) == ref.shape, name
+        assert np.array_equal(bits(got.cpu().numpy()), bits(ref)), name
+    return bt
+
+
+@pytest.mark.gpu
+def test_public_route_and_batch_shapes_on_the_64_point_set():
+    """A4: ``SkeletonClipSet`` on the (3, 64, 7) videos reports the host instance's ``VideoReport``s.  B: windows of T = 5 (W = 208, LD = 209) at B = 1 and at
+    B = 65 with repeated windows, first and last admissible rows included."""
+    cs, items = synthetic_set((3, 64, 7), 35)
+    assert cs.T == 5 and cs.W == 208 and cs.rows == [43, 43, 43] and len(cs.reports) == 3
+    for rep, it in zip(cs.reports, items):
+        print('%s: class report (%.17g, %.17g, %.17g)' % ((it['name'],) + tuple(rep[:3])))
+        assert tuple(rep[:3]) == tuple(it['host']['report'][:3]) and np.array_equal(rep.row_contact, it['host']['report'].row_contact)
+    hosts = [it['host'] for it in items]
+    check_windows(cs, hosts, [1], [38])
+    ids = [k % 3 for k in range(65)]
+    starts = [(7 * k) % 39 for k in range(62)] + [0, 38, 38]
+    assert len(set(zip(ids, starts))) < 65 and 0 in starts and max(starts) == 43 - 5
+    check_windows(cs, hosts, ids, starts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('T', [1, 128])
+def test_windows_of_odd_width_have_no_padding_column(T):
+    """B: J = 1, P = 1 gives W = 13 = LD (W | 1 = W: the tile has no padding column), at T = 1 (window = stride) and T = 128 (the kernel's limit)."""
+    cs, items = synthetic_set((1, 1, 1), T)
+    assert cs.W == 13 and (cs.W | 1) == cs.W and cs.T == T and cs.rows == [300, 300, 300]
+    ids, starts = [0, 1, 0, 2, 1], [0, 300 - T, 300 - T, 0, 131 if T == 1 else 100]                 # the first and the last admissible start row of both videos
+    bt = check_windows(cs, [it['host'] for it in items], ids, starts)
+    assert tuple(bt.gt.shape) == (5, 1, 13, T) and not bool(torch.isnan(bt.gt).any())
+    with pytest.raises(ValueError):
+        cs.assemble([0], [300 - T + 1])
+
+
+@pytest.mark.gpu
+def test_a_nearly_full_tile_assembles_and_a_larger_one_is_refused_before_any_launch():
+    """B: J = 21, P = 64: W = 262, LD = 263.  T = 62 is 65,224 B of dynamic LDS (the launcher allows 65,536) and assembles bit for bit; T = 63 (66,276 B) is a
+    ValueError of the class and IDF_E_INVAL of the C entry called directly -- its outputs keep their sentinel."""
+    import ctypes as C
+    from interdiff_amd import _lib
+    m = sd_mod()
+    video, _ = synth_video(200, 21, 64, 1, (63, 64, 130), 900)
+    host = m.prepare_host(video, stride=1, n_joints=21, n_points=64)
+    cs = m.SkeletonClipSet([video], window=62, stride=1, hop=1, n_joints=21, n_points=64, device=DEV)
+    lds = cs.T * (cs.W | 1) * 4
+    print('tile: T %d x LD %d x 4 = %d B of %d' % (cs.T, cs.W | 1, lds, _lib.SKEL_WINDOW_LDS))
+    assert cs.W == 262 and lds == 65224 and lds <= _lib.SKEL_WINDOW_LDS < 63 * 263 * 4 == 66276
+    check_windows(cs, [host], [0, 0, 0], [0, 200 - 62, 77])
+    with pytest.raises(ValueError):
+        m.SkeletonClipSet([video], window=63, stride=1, hop=1, n_joints=21, n_points=64, device=DEV)
+    B, T = 1, 63
+    clips = torch.zeros(2, B, dtype=torch.int32, device=DEV)
+    new = lambda *shape: torch.full(shape, -7.0, dtype=torch.float32, device=DEV)
+    o = dict(body=new(B, T, 21, 3), obj=new(B, T, 64, 3), pose=new(B, T, 7), zero_pose_obj=new(B, 64, 3), gt=new(B, 1, 262, T))
+    wb = _lib.SkelWindowBatch()
+    for k in _lib.SKEL_WINDOW_FIELDS:
+        setattr(wb, k, o[k].data_ptr())
+    rc = cs.lib.interdiff_skeleton_window_batch(C.byref(cs.cset), _lib.dptr(clips, torch.int32), B, T, C.byref(wb), _lib.stream())
+    torch.cuda.synchronize()
+    assert rc == -22 and all(bool((t == -7.0).all()) for t in o.values())
