@@ -898,7 +898,7 @@ int interdiff_mdm_train_full_grads(const float *params, const float *pe, int32_t
 
 /* ------------------------------------------------------------------------------------
  * Fine-tuning of the SMPL denoiser's PointNet++ (csrc/pointnet2.hip, csrc/pointnet2_train.h / .hip): consumes the d_pc of the entry above.  Additive entries:
- * interdiff_abi_version() stays what it was.  Regime: pcEmbedding in eval() with autograd on (frozen running statistics); batch statistics are not built.
+ * interdiff_abi_version() stays what it was.  Regime: pcEmbedding in eval() with autograd on (frozen running statistics); the batch-statistic regime is the next block's.
  *
  *  interdiff_pointnet2_encode_saved   replaces PointNet2Encoder.forward (model/layers.py:141-175) as MDM._get_embeddings calls it with autograd on
  *      (model/diffusion_smpl.py:210-211): out [B,256] has the bits of interdiff_pointnet2_encode, and `saves` (interdiff_pointnet2_saves_bytes(B) bytes, 4-byte
@@ -924,6 +924,29 @@ size_t interdiff_pointnet2_finetune_workspace_bytes(int32_t B);
 int interdiff_pointnet2_finetune_grads(const idf_pointnet2 *pn, const float *theta, const float *stats, const float *obj_points, int32_t B, int32_t P,
                                        const void *saves, const float *d_pc, float *grads, void *ws, size_t ws_bytes, void *stream);
 int interdiff_pointnet2_refold(const idf_pointnet2 *pn, const float *theta, const float *stats, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Training of the SMPL denoiser's PointNet++ under BATCH statistics (csrc/pointnet2_bn_train.h / .hip): pcEmbedding in train(), the regime Lightning puts
+ * LitInteraction.model in.  Additive entries: interdiff_abi_version() stays what it was.  theta / grads: the 38 raw tensors of
+ * interdiff_pointnet2_finetune_param_table (the one table); stats [1472] as there.  Limits: 1 <= B <= 256, 1 <= P <= 2048 (IDF_E_INVAL beyond).
+ *
+ *  interdiff_pointnet2_train_forward  replaces PointNet2Encoder.forward (model/layers.py:141-175) as MDM._get_embeddings calls it (model/diffusion_smpl.py:210-211)
+ *      with the module in train(): each of the twelve BatchNorm2d sites normalises with the mean and biased variance of its own tensor -- in SA1 over all
+ *      B * 1024 * nsample rows, padding slots and repeated FPS positions counted as often as they occur; in SA2 over B * 16 and B * 32 rows.  It reads the RAW
+ *      tensors (no fold).  pc_out [B,256].  `ws` (interdiff_pointnet2_train_workspace_bytes(B) bytes, 256-byte aligned) keeps the sampling and grouping of every
+ *      centre, the batch statistics and what the backward reads.
+ *  interdiff_pointnet2_train_grads    replaces loss.backward() through pcEmbedding in train() (train_diffusion_smpl.py:60-166): grads [113,917] =
+ *      d sum(d_pc * pc) / d theta, through the batch statistics (BatchNorm2d's train-mode backward), of the forward that left `ws`.  d_pc[:, 0:3] reaches no
+ *      parameter; no gradient with respect to obj_points.  fp32 products, fixed summation orders, partial sums folded in index order in double, no atomics.
+ *  interdiff_pointnet2_train_stats    replaces the running-statistic update of BatchNorm2d.forward in train() (momentum 0.1 in the reference; the running variance
+ *      takes the unbiased batch variance): stats are rewritten in place from the batch statistics in `ws`, in double, rounded once.  num_batches_tracked is the
+ *      caller's.  interdiff_pointnet2_refold then rebuilds the eval pack from the new weights and statistics.
+ * ---------------------------------------------------------------------------------- */
+size_t interdiff_pointnet2_train_workspace_bytes(int32_t B);
+int interdiff_pointnet2_train_forward(const float *theta, const float *obj_points, int32_t B, int32_t P, float *pc_out, void *ws, size_t ws_bytes, void *stream);
+int interdiff_pointnet2_train_grads(const float *theta, const float *obj_points, int32_t B, int32_t P, const float *d_pc, float *grads, void *ws, size_t ws_bytes,
+                                    void *stream);
+int interdiff_pointnet2_train_stats(const void *ws, int32_t B, double momentum, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Scoring of a skeleton diffusion checkpoint (csrc/skeleton_losses.hip): the forward, scoring side of interdiff/train_diffusion_skeleton.py.

@@ -231,6 +231,10 @@ _SIGS = {
     'interdiff_pointnet2_finetune_workspace_bytes': (sz, [i32]),
     'interdiff_pointnet2_finetune_grads': (C.c_int, [C.POINTER(PointNet2), vp, vp, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
     'interdiff_pointnet2_refold': (C.c_int, [C.POINTER(PointNet2), vp, vp, vp]),
+    'interdiff_pointnet2_train_workspace_bytes': (sz, [i32]),
+    'interdiff_pointnet2_train_forward': (C.c_int, [vp, vp, i32, i32, vp, vp, sz, vp]),
+    'interdiff_pointnet2_train_grads': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, sz, vp]),
+    'interdiff_pointnet2_train_stats': (C.c_int, [vp, i32, C.c_double, vp, vp]),
     'interdiff_skeleton_sample_losses_workspace_bytes': (sz, [i32, i32]),
     'interdiff_skeleton_sample_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     'interdiff_skeleton_denoising_losses': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),

@@ -19,31 +19,6 @@ namespace {
 
 using namespace pn2;
 
-__device__ __forceinline__ float d2_exact(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// rank of this thread's hit among all hits of the block in thread order (exclusive), and the block total
-__device__ __forceinline__ int block_rank(bool hit, unsigned *wcount, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(hit);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NWV; ++w) {
-        const int c = (int)wcount[w];
-        if (w < wave) base += c;
-        tot += c;
-    }
-    __syncthreads();                           // wcount is reused by the next call
-    total = tot;
-    return base + below;
-}
-
 __device__ __forceinline__ void maxpool(const float *a, int stride, int ns, int cout, float *dst) {
     for (int o = threadIdx.x; o < cout; o += PT) {
         float m = a[o];
@@ -65,7 +40,7 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
     __shared__ float feat1[NSLOT][F1];
     __shared__ float xin[NS1 * 100], a1[NS1 * 64], a2[NS1 * 96], a3[NS1 * 128];
     __shared__ float f2[256];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float *ar = pn.arena;
     int *sv = SAVE ? saves + (size_t)b * SV_WORDS : nullptr;
 
@@ -77,71 +52,15 @@ __global__ __launch_bounds__(PT) void pointnet2_kernel(const idf_pointnet2 pn, c
     }
     __syncthreads();
 
-    // ---- 1. furthest point sampling 2048 -> 1024 (start at 0, skip |p|^2 <= 1e-3, arg-max = lowest index on ties)
-    {
-        float px[2], py[2], pz[2], tmp[2];
-        bool ok[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int i = tid + PT * k;
-            const float4 p = pts[i];
-            px[k] = p.x; py[k] = p.y; pz[k] = p.z;
-            tmp[k] = 1e10f;
-            ok[k] = i < P && d2_exact(p.x, p.y, p.z, 0.f, 0.f, 0.f) > 1e-3f;
-        }
-        if (tid == 0) fps[0] = 0;
-        int old = 0;
-        for (int j = 1; j < NP1; ++j) {
-            const float4 o = pts[old];
-            float bv = -1.0f;
-            int bi = 0x7fffffff;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (ok[k]) {
-                    const float d2 = fminf(d2_exact(px[k], py[k], pz[k], o.x, o.y, o.z), tmp[k]);
-                    tmp[k] = d2;
-                    if (d2 > bv) { bv = d2; bi = tid + PT * k; }      // k = 0 first: lower index wins ties inside the thread
-                }
-            }
-            const float wv = wave_max(bv);
-            const float wi = -wave_max(bv == wv ? -(float)bi : -3e9f);                   // lowest index among the wave's maxima
-            const int buf = j & 1;
-            if (lane == 0) { redv[buf][wave] = wv; redi[buf][wave] = wv > -1.0f ? (int)wi : 0x7fffffff; }
-            __syncthreads();
-            float fv = -1.0f;
-            int fi = 0x7fffffff;
-#pragma unroll
-            for (int w = 0; w < NWV; ++w) {
-                const float v = redv[buf][w];
-                const int ii = redi[buf][w];
-                if (v > fv || (v == fv && ii < fi)) { fv = v; fi = ii; }
-            }
-            old = fv > -1.0f ? fi : 0;
-            if (tid == 0) fps[j] = (unsigned short)old;
-        }
-    }
+    // ---- 1. furthest point sampling 2048 -> 1024 (csrc/pointnet2_train.h)
+    fps_sample(pts, P, fps, redv, redi);
     __syncthreads();
 
     // ---- 2. the key point (first sampled centre) and the SA1 centres it groups: r = 0.1 / 16 and r = 0.2 / 32, FPS order
     const float4 c0 = pts[fps[0]];
-    {
-        const float4 q = pts[fps[tid]];
-        const float d2 = d2_exact(q.x, q.y, q.z, c0.x, c0.y, c0.z);
-        const float r0 = 0.1f, r1 = 0.2f;
-        int tot;
-        int rk = block_rank(d2 < r0 * r0, wcount, tot);
-        if (d2 < r0 * r0 && rk < NS0) list[rk] = tid;
-        __syncthreads();
-        if (tid < NS0 && tid >= tot) list[tid] = tot > 0 ? list[0] : 0;
-        if (SAVE && tid == 0) sv[SV_CNT] = tot;
-        __syncthreads();
-        rk = block_rank(d2 < r1 * r1, wcount, tot);
-        if (d2 < r1 * r1 && rk < NS1) list[NS0 + rk] = tid;
-        __syncthreads();
-        if (tid < NS1 && tid >= tot) list[NS0 + tid] = tot > 0 ? list[NS0] : 0;
-        if (SAVE && tid == 0) sv[SV_CNT + 1] = tot;
-        __syncthreads();
-    }
+    int tot0, tot1;
+    sa2_slots(pts, fps, list, wcount, tot0, tot1);
+    if (SAVE && tid == 0) { sv[SV_CNT] = tot0; sv[SV_CNT + 1] = tot1; }
 
     // ---- 3. SA1 (radii 0.05 / 0.1, 16 / 32 samples, MLPs 4-16-16-32 and 4-32-32-64) for the grouped centres only
     for (int s = 0; s < NSLOT; ++s) {

@@ -27,6 +27,12 @@ model/diffusion_smpl.py:210-211) is trained with frozen normalisation statistics
 what that regime is and what is not built).  Its 38 tensors (``POINTNET_PARAM_NAMES``; 113,917 parameters) follow the 228 in the flat vectors, a batch carries raw
 ``obj_points`` [B,P,3] (never ``pc`` or ``cond``: their gradient could not reach the points), and one ``training_step`` is: encode with saves, the full pass, the
 PointNet++ backward on its ``d_pc``, AdamW over all 266 tensors, the device re-fold of eval BatchNorm -- so the encoder's pack is never stale.
+
+``pointnet_mode='train'`` (with ``train_pointnet``) is the reference's own regime: Lightning puts the whole model in ``train()``, so ``pcEmbedding`` normalises with
+batch statistics, back-propagates through them and moves its running statistics (``PointNetTrainer``).  One ``training_step`` is then: the train-mode forward, the
+full pass, the train-mode backward, AdamW over all 266 tensors, the statistics update, the re-fold.  ``encode_points`` (validation, the sampler, ``export_mdm``) goes
+on reading the eval pack, which now carries the moved statistics, as the reference's ``eval()`` does; ``state_dict()`` carries them too.  The default ``'eval'`` is
+the frozen regime above, bit for bit.
 """
 import ctypes as C
 import torch
@@ -35,7 +41,7 @@ from .eval import as_clip_batch
 from .flat_trainer import MAX_T, MAX_MEM
 from .losses import LOSS_KEYS, LossWeights
 from .mdm import MDM
-from .pointnet2_train import POINTNET_PARAM_NAMES, PointNetFineTuner, param_table as pointnet_param_table
+from .pointnet2_train import POINTNET_PARAM_NAMES, PointNetFineTuner, PointNetTrainer, param_table as pointnet_param_table
 
 QAN_LAYERS = (1, 2, 3, 4, 5, 6)
 
@@ -89,6 +95,7 @@ class DenoiserTrainer(flat_trainer.FlatAdamWTrainer):
     for; anything but 0 raises (not built).  ``weights`` / ``past_len``: the loss of ``forward_backward``; ``n_steps``: the cosine schedule's length.
     ``train_encoder``: the 84 encoder tensors are trained too (module docstring); a batch then carries ``pc`` or ``obj_points``, never ``cond``.
     ``train_pointnet`` (needs ``train_encoder``): the 38 ``pcEmbedding.*`` tensors are trained too, running statistics frozen; a batch carries ``obj_points``.
+    ``pointnet_mode``: ``'eval'`` (that frozen regime) or ``'train'`` (needs ``train_pointnet``): batch statistics, the backward through them, running statistics moved.
     ``state_dict()`` returns the trained tensors (144, 228 or 266) and every other tensor of the constructor's state_dict exactly as it came in.
 
     ``loss_and_grads`` returns, behind the four common elements, ``d_cond`` [mem_len,B,256] and, with ``train_encoder``, ``d_pc`` [B,256]; ``self.cond`` then
@@ -105,10 +112,14 @@ class DenoiserTrainer(flat_trainer.FlatAdamWTrainer):
     }
 
     def __init__(self, state_dict, device='cuda', lr=3e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, weights=LossWeights(), past_len=10, n_steps=1000,
-                 dropout=0.0, cond_mask_prob=0.0, train_encoder=False, train_pointnet=False):
+                 dropout=0.0, cond_mask_prob=0.0, train_encoder=False, train_pointnet=False, pointnet_mode='eval'):
         if train_pointnet and not train_encoder:
             raise ValueError('train_pointnet=True needs train_encoder=True: the gradient reaches pcEmbedding through the encoder')
-        self.train_encoder, self.train_pointnet = bool(train_encoder), bool(train_pointnet)
+        if pointnet_mode not in ('eval', 'train'):
+            raise ValueError("pointnet_mode must be 'eval' or 'train'")
+        if pointnet_mode == 'train' and not train_pointnet:
+            raise ValueError("pointnet_mode='train' needs train_pointnet=True: batch statistics are the regime of a trained pcEmbedding")
+        self.train_encoder, self.train_pointnet, self.pointnet_mode = bool(train_encoder), bool(train_pointnet), pointnet_mode
         self._takes, self._form, inputs, grads = self.MODES[self.train_encoder, self.train_pointnet]
         self._inputs, self._grads = getattr(self, inputs), getattr(self, grads)
         names, table = (FULL_PARAM_NAMES if self.train_encoder else PARAM_NAMES), param_table(self.train_encoder)
@@ -118,8 +129,9 @@ class DenoiserTrainer(flat_trainer.FlatAdamWTrainer):
         super().__init__(state_dict, names, table, device, lr, weight_decay, betas, eps, weights, past_len, n_steps, dropout, cond_mask_prob)
         self._mdm, self._pn, self.pointnet = None, None, None
         if self.train_pointnet:
-            self.pointnet = PointNetFineTuner(state_dict, self.device, params=self.params[n_mdm:], grad=self.grads[n_mdm:])
-            self.after_step = self.pointnet.refold                   # so the encoder's pack is never stale
+            tuner = PointNetTrainer if pointnet_mode == 'train' else PointNetFineTuner
+            self.pointnet = tuner(state_dict, self.device, params=self.params[n_mdm:], grad=self.grads[n_mdm:])
+            self.after_step = self._after_train_step if pointnet_mode == 'train' else self.pointnet.refold       # so the encoder's pack is never stale
 
     def export_mdm(self):
         """An ``interdiff_amd.mdm.MDM`` packed (on the host, ``pack_mdm_weights``) from the current weights: for sampling and ``validation_step``.
@@ -203,8 +215,20 @@ class DenoiserTrainer(flat_trainer.FlatAdamWTrainer):
             raise ValueError('train_pointnet=True takes a clip batch with gt [B,1,144,T] and obj_points [B,P,3]')
         return batch['gt'], batch['obj_points']
 
+    def _after_train_step(self):
+        self.pointnet.update_running_stats()
+        self.pointnet.refold()
+
+    def state_dict(self):
+        out = super().state_dict()
+        if self.pointnet_mode == 'train':                            # the moved statistics and counters
+            moved = self.pointnet.state_dict()
+            out.update({k: moved[k] for k in moved if k not in self.names})
+        return out
+
     def _pointnet_grads(self, x_t, t, obj_points, target, d_pred):
-        out = self._full_grads(x_t, t, self.pointnet.encode_saved(obj_points), target, d_pred)
+        pc = self.pointnet.forward(obj_points) if self.pointnet_mode == 'train' else self.pointnet.encode_saved(obj_points)
+        out = self._full_grads(x_t, t, pc, target, d_pred)
         self.pointnet.grads(out[3], flat=True)
         return out
 
