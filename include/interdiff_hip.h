@@ -302,6 +302,34 @@ int interdiff_sampler_advance(int64_t *state, int64_t *ts, int32_t B, void *stre
 int interdiff_posterior_step_dev_map(float *x, const float *x0, const float *gt, const uint8_t *mask, int64_t n,
                                      const float *table, const int64_t *tmap, int64_t *state, int64_t *ts, int32_t B, void *stream);
 int interdiff_sampler_advance_map(int64_t *state, int64_t *ts, const int64_t *tmap, int32_t B, void *stream);
+/* Pseudo linear multistep sampling (plms_sample, diffusion/gaussian_diffusion.py:1001-1083), graph-replayable like
+ * interdiff_posterior_step_dev_map: every per-step quantity is read from HBM through state[0] (loop-side t) and state[1] (loop index).
+ *   ptable f32[steps][4] = {sqrt(1/ab), sqrt(1/ab - 1), sqrt(ab_prev), sqrt(1 - ab_prev)} of the (spaced) process, each rounded once from fp64;
+ *   ring   f32[3][n]: the eps of the last three loop indices, slot = loop index % 3;  order 1..4 (the loops pass 2..4);
+ *   gt / mask optional in-kernel inpainting of x0 (x0 itself is not written); tmap as above (NULL = identity); state int64[8] as above.
+ * With n % 4 == 0, x / x0 / gt / ring / x_mid 16-byte and mask 4-byte aligned, every access is 16 bytes wide; any other n or alignment
+ * takes the scalar form of the same arithmetic (same bits per element).  No float atomics.  The update cancels (a x against r eps', sqrt(ab_prev / ab)
+ * times their difference), so every element is evaluated in fp64 from its fp32 operands and rounded once per stored value; the arithmetic is
+ * pinned (no contraction, explicit fma).
+ *
+ * interdiff_plms_step_dev   replaces :1044 (_predict_eps_from_xstart) and :1060-1083:  with t = state[0], it = state[1],
+ *     eps  = (a x - x0) / r
+ *     eps' = Adams-Bashforth over cur_order = min(order, it + 1) values, newest first: eps; (3, -1)/2; (23, -16, 5)/12; (55, -59, 37, -9)/24
+ *     x    = sqrt(ab_prev) (a x - r eps') + sqrt(1 - ab_prev) eps'      (t == 0: x = x0)
+ *   ring[it % 3] = eps -- the slot of loop index it - 3, the oldest, which each thread reads before it writes.  The last workgroup to
+ *   retire advances: state[0] = t - 1, state[1] = it + 1, ts[b] = tmap[max(t - 1, 0)].
+ * interdiff_plms_first_half_dev   replaces :1044 and :1053-1054, the first half of the "pseudo improved Euler" start (x is only read):
+ *     ring[it % 3] = eps;  x_mid = x0 sqrt(ab_prev) + sqrt(1 - ab_prev) eps;  then state[0] = t - 1, ts[b] = tmap[t - 1]; the loop index stays.
+ *   The caller then runs the denoiser (and inpainting, denoised_fn) on (x_mid, ts): they see t - 1 (:1055).
+ * interdiff_plms_second_half_dev  replaces :1055-1058 after that second call: with t - 1 = state[0],
+ *     eps2 = (a[t-1] x_mid - x0) / r[t-1];  eps' = (ring[it % 3] + eps2) / 2;  x = sqrt(ab_prev[t]) (a[t] x - r[t] eps') + sqrt(1 - ab_prev[t]) eps'
+ *   then state[1] = it + 1; state[0] and ts stay at t - 1, the next step's.  The ring keeps eps, not eps' (:1053). */
+int interdiff_plms_step_dev(float *x, const float *x0, const float *gt, const uint8_t *mask, float *ring, int64_t n, int32_t order,
+                            const float *ptable, const int64_t *tmap, int64_t *state, int64_t *ts, int32_t B, void *stream);
+int interdiff_plms_first_half_dev(const float *x, const float *x0, const float *gt, const uint8_t *mask, float *ring, float *x_mid, int64_t n,
+                                  const float *ptable, const int64_t *tmap, int64_t *state, int64_t *ts, int32_t B, void *stream);
+int interdiff_plms_second_half_dev(float *x, const float *x0, const float *gt, const uint8_t *mask, const float *ring, const float *x_mid,
+                                   int64_t n, const float *ptable, int64_t *state, void *stream);
 /* One PLAIN reverse step (no denoised_fn hook) = interdiff_mdm_forward + interdiff_posterior_step_dev(ts != NULL) with the x0
  * prediction consumed inside the denoiser's last GEMM: x [B,1,C,T] is the sampler state, updated in place; ts, table, gt, mask as
  * above; state is int64[8] here: [0..3] as above, [4..5] scratch (this step's {t, loop index}, parked by one thread of layer 0's

@@ -171,6 +171,9 @@ _SIGS = {
     'interdiff_sampler_advance': (C.c_int, [vp, vp, i32, vp]),
     'interdiff_posterior_step_dev_map': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp]),
     'interdiff_sampler_advance_map': (C.c_int, [vp, vp, vp, i32, vp]),
+    'interdiff_plms_step_dev': (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp]),
+    'interdiff_plms_first_half_dev': (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp]),
+    'interdiff_plms_second_half_dev': (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
     'interdiff_objprojector_sample': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, vp, vp]),
     'interdiff_objprojector_forward_workspace_bytes': (sz, [i32]),
     'interdiff_objprojector_forward': (C.c_int, [C.POINTER(ObjProj), vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]),

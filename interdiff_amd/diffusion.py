@@ -29,6 +29,10 @@ scalars {c1, c2, sigma} the kernels already take.  Two indices then exist per st
 Philox step counter, what ``denoised_fn`` is told and what its gate and blend weight act on -- and the model's timestep
 ``timestep_map[i]``, which only the denoiser's embedding sees (respace.py:124-126); on the device, ``state[0]`` holds the former and
 ``ts`` the latter (``_tmap``).
+PLMS and partial schedules: ``plms_sample_loop`` (gaussian_diffusion.py:1001-1196) is not a table row -- every step combines the
+current eps with up to three earlier ones, and its first step calls the denoiser twice, the second time at t - 1 -- so it has step kernels of its
+own (csrc/plms.hip: an eps ring f32[3][n], a table of four square roots per step, state-driven like the posterior step) and runs the two-call
+form on every route.  ``skip_timesteps`` / ``init_image`` on all three loops start from ``q_sample(init_image, first index, x_T)``.
 Only the configuration the eval path uses is implemented (ModelMeanType.START_X, ModelVarType.FIXED_SMALL, clip_denoised=False,
 rescale_timesteps=False); anything else raises NotImplementedError.
 """
@@ -211,6 +215,32 @@ class GaussianDiffusion:
             self._tables[key] = torch.from_numpy(self._rows(sampler)).to(device)
         return self._tables[key]
 
+    def _plms_rows(self):
+        """Host [steps,4] fp32 rows {sqrt(1/ab), sqrt(1/ab - 1), sqrt(ab_prev), sqrt(1 - ab_prev)} of the PLMS step kernels (csrc/plms.hip): what
+        ``plms_sample`` reads or forms per step (gaussian_diffusion.py:1044, :1054), each rounded ONCE from the fp64 tables, as ``_rows`` does."""
+        if 'plms' not in self._rows_cache:
+            ab, abp = self.alphas_cumprod, self.alphas_cumprod_prev
+            self._rows_cache['plms'] = np.ascontiguousarray(np.stack([np.sqrt(1.0 / ab), np.sqrt(1.0 / ab - 1.0), np.sqrt(abp), np.sqrt(1.0 - abp)], axis=1).astype(np.float32))
+        return self._rows_cache['plms']
+
+    def _plms_table(self, device):
+        """``_plms_rows`` on the device."""
+        key = (str(device), 'plms')
+        if key not in self._tables:
+            self._tables[key] = torch.from_numpy(self._plms_rows()).to(device)
+        return self._tables[key]
+
+    def _predict_x0(self, model, x, t, t_hook, model_kwargs, denoised_fn, rows_kw):
+        """The x0 a step works on: model(x, t) -> inpainting -> ``denoised_fn`` told ``t_hook`` (p_mean_variance, gaussian_diffusion.py:277-388)."""
+        y = model_kwargs.get('y', {})
+        x0 = model(x, t, **model_kwargs, **rows_kw)
+        mu8, gc = mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), x0)
+        if mu8 is not None:
+            inpaint(x0, gc, mu8)
+        if denoised_fn is not None:
+            x0 = denoised_fn(x0, t_hook, model_kwargs).contiguous()
+        return x0
+
     def _step(self, model, img, x0_buf, i, it, t, model_kwargs, denoised_fn, noise_i, seed, elem0=0, rows_kw={}, t_hook=None, rows=None):
         """``t``: what the model is called with; ``t_hook`` (default ``t``): what ``denoised_fn`` is; ``rows``: the sampler's ``_rows``."""
         lib = _lib.load()
@@ -241,7 +271,9 @@ class GaussianDiffusion:
         (a window of the loop for measurements; default T-1), ``shard=(first_clip, total_clips)``: the batch is clips
         [first, first + B) of a larger one -- noise counters and the feed-forward tile are the larger batch's (module docstring);
         ``noise`` / ``step_noise`` tensors, when given, are this shard's slices.  On a respaced schedule ``first_t``, ``n_steps`` and
-        ``dump_steps`` count spaced steps."""
+        ``dump_steps`` count spaced steps.  ``skip_timesteps`` / ``init_image`` (:701-709): x starts as ``q_sample(init_image, N - 1, x)`` -- after
+        the inpainting of a drawn x_T -- and the loop runs the spaced indices N - 1 ... skip_timesteps: the reference slices the FRONT of the index
+        list off (:705), so the last step still draws noise unless skip_timesteps == 0.  That quirk is kept."""
         return self._sample_loop(('ddpm',), model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
                                  init_image, randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed, n_steps, use_graph,
                                  first_t, shard)
@@ -253,17 +285,44 @@ class GaussianDiffusion:
         """``ddim_sample_loop`` (gaussian_diffusion.py:885-1000): ``p_sample_loop``'s keyword surface and extras, plus ``eta``.  The same
         loop on the table rows of ``ddim_coefficients``; inpainting and ``denoised_fn`` act on x0 before the update, and x_T drawn here
         (``noise=None``) is NOT inpainted (:960-963, unlike :695-699).  With ``eta = 0`` every sigma is 0: the noise is still drawn and
-        multiplied, so that the eager and the graph route stay one arithmetic (the result does not depend on ``seed``)."""
+        multiplied, so that the eager and the graph route stay one arithmetic (the result does not depend on ``seed``).  ``skip_timesteps`` /
+        ``init_image`` (:965-972): x starts as ``q_sample(init_image, N - 1 - skip, x)`` and the loop runs N - 1 - skip ... 0."""
         return self._sample_loop(('ddim', float(eta)), model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
                                  skip_timesteps, init_image, randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed,
                                  n_steps, use_graph, first_t, shard)
+
+    def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None,
+                         progress=False, skip_timesteps=0, init_image=None, randomize_class=False, cond_fn_with_grad=False, order=2,
+                         dump_steps=None, seed=None, n_steps=None, use_graph=True, shard=None):
+        """``plms_sample_loop`` (gaussian_diffusion.py:1085-1196), the pseudo linear multistep sampler: the reference's keywords plus ``seed`` (for
+        a drawn x_T only: the steps draw nothing), ``n_steps``, ``use_graph``, ``shard`` and ``dump_steps`` as in ``p_sample_loop``.  Every step
+        re-derives eps from the inpainted, ``denoised_fn``-corrected x0 and combines it with up to ``order`` - 1 earlier ones (csrc/plms.hip);
+        the first step calls the model twice, the second time on the half-way point and with t - 1 (:1051-1058) -- ``denoised_fn`` is told
+        t - 1 there too.  x_T drawn here is not inpainted (:1153-1156).  ``order`` 2, 3 or 4: the reference's ``order=1`` dies on its first
+        step (``old_out`` is None at :1061), so it is refused here.  ``skip_timesteps`` / ``init_image`` as in ``ddim_sample_loop`` (:1158-1165)."""
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= order <= 4:
+            raise ValueError('order must be 2, 3 or 4')
+        if order == 1:
+            raise ValueError('order=1 is not a sampler: the reference fails there too (TypeError on its first step, old_out is None)')
+        return self._sample_loop(('plms', int(order)), model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
+                                 init_image, randomize_class, cond_fn_with_grad, dump_steps, False, None, seed, n_steps, use_graph, None, shard)
 
     def _sample_loop(self, sampler, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps, init_image,
                      randomize_class, cond_fn_with_grad, dump_steps, const_noise, step_noise, seed, n_steps, use_graph, first_t, shard):
         if clip_denoised:
             raise NotImplementedError('clip_denoised=True is not used on the eval path (eval_smpl_short.py:153)')
-        if cond_fn is not None or skip_timesteps or init_image is not None or randomize_class or cond_fn_with_grad or const_noise:
-            raise NotImplementedError('only noise=, denoised_fn=, model_kwargs=, dump_steps= are live (SURVEY.md §8(b))')
+        if cond_fn is not None or randomize_class or cond_fn_with_grad or const_noise:
+            raise NotImplementedError('only noise=, denoised_fn=, model_kwargs=, dump_steps=, skip_timesteps=, init_image= are live (SURVEY.md §8(b))')
+        skip, N = int(skip_timesteps or 0), self.num_timesteps
+        started = bool(skip) or init_image is not None
+        if started and first_t is not None:
+            raise ValueError('first_t enters the schedule with noise taken as x_t; skip_timesteps / init_image start it from a noised motion: give one')
+        if not 0 <= skip < N:
+            raise ValueError('skip_timesteps must leave a step of the %d to run' % N)
+        if init_image is not None and (tuple(init_image.shape) != tuple(shape) or init_image.dtype != torch.float32):
+            raise ValueError('init_image must be float32 of shape %s' % (tuple(shape),))
+        if sampler[0] == 'plms' and N - skip < 2:
+            raise ValueError('PLMS needs two steps: its first step calls the model at t - 1 (the reference would index step -1)')
         if model_kwargs is None:
             model_kwargs = {}
         if seed is None:
@@ -289,19 +348,27 @@ class GaussianDiffusion:
             mu8, gc = mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), img) if sampler[0] == 'ddpm' else (None, None)
             if mu8 is not None:
                 inpaint(img, gc, mu8)
-        t_first = self.num_timesteps - 1 if first_t is None else int(first_t)
+        # p_sample_loop slices the skipped steps off the FRONT of the ascending index list (:705: N - 1 ... skip), the other two off its end (:967, :1161)
+        t_first = (N - 1 if sampler[0] == 'ddpm' else N - 1 - skip) if first_t is None else int(first_t)
         if not 0 <= t_first < self.num_timesteps:
             raise ValueError('first_t outside the schedule')
-        todo = t_first + 1 if n_steps is None else min(int(n_steps), t_first + 1)
+        left = t_first + 1 - (skip if sampler[0] == 'ddpm' else 0)
+        todo = left if n_steps is None else min(int(n_steps), left)
+        if started:                                     # x = q_sample(init_image, first index, x): the drawn or given noise serves as eps (:707-709)
+            x_start = torch.zeros_like(img) if init_image is None else init_image.to(device).contiguous()
+            img = self.q_sample(x_start, torch.full((shape[0],), t_first, dtype=torch.int64, device=device), noise=img)
         if (step_noise is None and use_graph and getattr(model, 'graph_safe', False) and img.is_cuda
                 and 'cond' in model_kwargs.get('y', {}) and os.environ.get('INTERDIFF_NO_GRAPH') != '1'):
             return graph_sampler.sample(self, model, img, model_kwargs, denoised_fn, seed, todo, dump_steps, t_first, shard, sampler)
         rows_kw = {'batch_rows': total * shape[-1]} if shard is not None and getattr(model, 'accepts_batch_rows', False) else {}
-        ts, ts_hook, rows = self._timesteps(shape[0], device), self._timesteps(shape[0], device, loop_side=True), self._rows(sampler)
+        ts, ts_hook = self._timesteps(shape[0], device), self._timesteps(shape[0], device, loop_side=True)
         dump = []
         cond = model_kwargs.get('y', {}).get('cond') if isinstance(model_kwargs.get('y', None), dict) else None
         if cond is not None and hasattr(model, 'prepare_memory'):
             model.prepare_memory(cond)                  # once per sample, like the graph route (never trust a cached fold across samples)
+        if sampler[0] == 'plms':
+            return self._plms_loop(sampler[1], model, img, ts, ts_hook, t_first, todo, model_kwargs, denoised_fn, rows_kw, dump_steps, seed, elem0)
+        rows = self._rows(sampler)
         for it, i in enumerate(range(t_first, t_first - todo, -1)):
             t, th = ts[i], ts_hook[i]
             t.host_value = th.host_value = i
@@ -312,6 +379,31 @@ class GaussianDiffusion:
             else:
                 nz = step_noise[it]
             self._step(model, img, None, i, it, t, model_kwargs, denoised_fn, nz, seed, elem0, rows_kw, th, rows)
+            if dump_steps is not None and it in dump_steps:
+                dump.append(img.clone())
+        return dump if dump_steps is not None else img
+
+    def _plms_loop(self, order, model, img, ts, ts_hook, t_first, todo, model_kwargs, denoised_fn, rows_kw, dump_steps, seed, elem0):
+        """The eager PLMS loop on the entries the graph route captures (graph_sampler.plms_*): sampler state, model timesteps, eps ring and
+        the half-way point live on the device; the model and ``denoised_fn`` are handed the host-known rows of ``ts`` / ``ts_hook``."""
+        dev, B = img.device, img.shape[0]
+        ptable, tmap = self._plms_table(dev), self._tmap(dev)
+        state = seeded_state(t_first, seed, elem0).to(dev)
+        ts_dev = torch.full((B,), self.timestep_map[t_first], dtype=torch.int64, device=dev)
+        ring, x_mid = torch.empty(3, img.numel(), dtype=torch.float32, device=dev), torch.empty_like(img)
+
+        def x0_at(x, i):
+            t, th = ts[i], ts_hook[i]
+            t.host_value = th.host_value = i
+            return self._predict_x0(model, x, t, th, model_kwargs, denoised_fn, rows_kw)
+        dump = []
+        for it, i in enumerate(range(t_first, t_first - todo, -1)):
+            x0 = x0_at(img, i)
+            if it == 0:                                 # pseudo improved Euler: the second call sees (x_mid, i - 1)
+                graph_sampler.plms_first_half(img, x0, None, None, ring, x_mid, ptable, state, ts_dev, tmap)
+                graph_sampler.plms_second_half(img, x0_at(x_mid, i - 1), None, None, ring, x_mid, ptable, state)
+            else:
+                graph_sampler.plms_step(img, x0, None, None, ring, order, ptable, state, ts_dev, tmap)
             if dump_steps is not None and it in dump_steps:
                 dump.append(img.clone())
         return dump if dump_steps is not None else img
@@ -378,14 +470,19 @@ class GaussianDiffusion:
         return model_output, x_start
 
 
-def sample_loop(diffusion, model, shape, sampler='ddpm', eta=0.0, **kw):
-    """``diffusion.p_sample_loop`` (sampler='ddpm', the default everywhere) or ``diffusion.ddim_sample_loop`` (sampler='ddim', with ``eta``): what the
-    eval and scoring entry points call, so that their ``loop_kw`` can choose the sampler."""
+def sample_loop(diffusion, model, shape, sampler='ddpm', eta=0.0, order=None, **kw):
+    """``diffusion.p_sample_loop`` (sampler='ddpm', the default everywhere), ``diffusion.ddim_sample_loop`` (sampler='ddim', with ``eta``) or
+    ``diffusion.plms_sample_loop`` (sampler='plms', with ``order``, which has no default here): what the eval and scoring entry points call, so that
+    their ``loop_kw`` can choose the sampler; ``skip_timesteps`` / ``init_image`` pass through ``kw``."""
     if sampler == 'ddpm':
         return diffusion.p_sample_loop(model, shape, **kw)
     if sampler == 'ddim':
         return diffusion.ddim_sample_loop(model, shape, eta=eta, **kw)
-    raise ValueError("sampler must be 'ddpm' or 'ddim'")
+    if sampler == 'plms':
+        if order is None:
+            raise ValueError("sampler='plms' needs order=2, 3 or 4")
+        return diffusion.plms_sample_loop(model, shape, order=order, **kw)
+    raise ValueError("sampler must be 'ddpm', 'ddim' or 'plms'")
 
 
 class SpacedDiffusion(GaussianDiffusion):

@@ -8,6 +8,8 @@ graph-safe denoiser (``MDM`` and its subclasses), so the denoiser's methods are 
     id(model) would replay freed memory once the id is recycled);
   * ``Run`` is one sample on an entry: it captures what the plan needs and is not there yet, and replays;
   * ``sample`` is the route: entry, this sample's inputs, warm-up, chains, hook buffers, plan, one replay or eager hook step per op.
+  * ``PlmsRun`` is a ``Run`` whose update is the PLMS step (``plms_step`` ... on csrc/plms.hip): one chain of two-call steps, the eps ring and the
+    half-way point on the entry, and the two-call first step as an op of its own in front of the plan (captured unless it takes an eager hook).
 The module constants that tools rebind (``GRAPH_BLOCKS`` ...) stay in diffusion.py and are read from there at call time.
 """
 import os
@@ -17,8 +19,8 @@ from . import _lib, diffusion
 HOOK_KEYS = ('hand_pose', 'beta', 'obj_points')          # what a captured hook step reads from ``y`` beside inpainted_motion
 
 
-def plan_steps(t_start, todo, active, dump_steps, fuse_hook):
-    """The ops of the ``todo`` steps t_start, t_start - 1, ... (loop index it = 0, 1, ...), ``active(t)`` telling the hook steps:
+def plan_steps(t_start, todo, active, dump_steps, fuse_hook, it0=0):
+    """The ops of the ``todo`` steps t_start, t_start - 1, ... (loop index it = ``it0``, ``it0`` + 1, ...), ``active(t)`` telling the hook steps:
       ('plain', k)      one captured graph of k plain steps
       ('hook', k)       one captured graph of k plain steps and the hook step after them (k = 0: a lone hook step); ``fuse_hook`` only
       ('eager_hook',)   the two-call hook step
@@ -27,7 +29,7 @@ def plan_steps(t_start, todo, active, dump_steps, fuse_hook):
     that fits: the 989 plain steps of a corrected 1000-step sample take 23 graphs with the hook fused."""
     blocks = diffusion.GRAPH_BLOCKS
     dumps = () if dump_steps is None else dump_steps
-    ops, i, it, end = [], t_start, 0, t_start - todo
+    ops, i, it, end = [], t_start, it0, t_start - todo
     while i > end:
         if active(i):
             ops.append(('hook', 0) if fuse_hook else ('eager_hook',))
@@ -64,6 +66,28 @@ def posterior_update(x, x0, gt, mask, table, state, ts, tmap=None):
                                                             x.numel(), _lib.dptr(table), _lib.dptr(tmap, torch.int64, allow_none=True), _lib.dptr(state),
                                                             _lib.dptr(ts), ts.numel(), _lib.stream()),
                'posterior_step_dev')
+
+
+def plms_step(x, x0, gt, mask, ring, order, ptable, state, ts, tmap=None):
+    """One multistep PLMS update of x from x0 (inpainted in the kernel when gt / mask are given): eps into ``ring`` f32[3][n], its Adams-Bashforth
+    combination with the earlier ones, the update; advances ``state`` and ``ts`` like ``posterior_update`` (interdiff_plms_step_dev)."""
+    _lib.check(_lib.load().interdiff_plms_step_dev(_lib.dptr(x), _lib.dptr(x0), _lib.dptr(gt, allow_none=True), _lib.dptr(mask, allow_none=True), _lib.dptr(ring),
+                                                   x.numel(), int(order), _lib.dptr(ptable), _lib.dptr(tmap, torch.int64, allow_none=True), _lib.dptr(state),
+                                                   _lib.dptr(ts), ts.numel(), _lib.stream()), 'plms_step_dev')
+
+
+def plms_first_half(x, x0, gt, mask, ring, x_mid, ptable, state, ts, tmap=None):
+    """First half of the first PLMS step: eps into the ring, the half-way point into ``x_mid``, ``state[0]`` / ``ts`` to t - 1 for the second
+    denoiser call; the loop index stays (interdiff_plms_first_half_dev)."""
+    _lib.check(_lib.load().interdiff_plms_first_half_dev(_lib.dptr(x), _lib.dptr(x0), _lib.dptr(gt, allow_none=True), _lib.dptr(mask, allow_none=True), _lib.dptr(ring),
+                                                         _lib.dptr(x_mid), x.numel(), _lib.dptr(ptable), _lib.dptr(tmap, torch.int64, allow_none=True),
+                                                         _lib.dptr(state), _lib.dptr(ts), ts.numel(), _lib.stream()), 'plms_first_half_dev')
+
+
+def plms_second_half(x, x0, gt, mask, ring, x_mid, ptable, state):
+    """Second half: the update of the ORIGINAL x from the mean of the two eps; advances the loop index (interdiff_plms_second_half_dev)."""
+    _lib.check(_lib.load().interdiff_plms_second_half_dev(_lib.dptr(x), _lib.dptr(x0), _lib.dptr(gt, allow_none=True), _lib.dptr(mask, allow_none=True), _lib.dptr(ring),
+                                                          _lib.dptr(x_mid), x.numel(), _lib.dptr(ptable), _lib.dptr(state), _lib.stream()), 'plms_second_half_dev')
 
 
 class Chain:
@@ -114,11 +138,12 @@ class Entry:
         self.kwargs = {'y': {'cond': self.cond}}            # what the captured denoiser calls see
         if zpo is not None:
             self.kwargs['zero_pose_obj'] = self.zpo
-        self.graphs = {}             # (k, fused, split): k plain steps; ('hook', hook uid, k, fused, split): and a hook step; 'fwd': the denoiser forward of an eager hook step
+        self.graphs = {}             # (k, fused, split): k plain steps; ('hook', hook uid, k, fused, split): and a hook step; 'fwd': the denoiser forward of an eager hook step; PLMS: ('first', hook uid or None, hooked at t, hooked at t - 1): the first step, 'fwd_mid': the forward on x_mid
         self.chains = []             # empty until the split route is first taken
         self.hooks = {}              # hook uid -> HookBuffers
         self.chain_steps = None      # whether the captured plain steps carry the next step's embedding (baked into the graphs)
         self.pool_keys = ()          # the denoiser's per-shape buffers that were allocated FOR this entry (``MDM.shape_buffer_keys``)
+        self.ring = self.x_mid = None            # a PLMS entry's eps ring f32[3][n] and the half-way point of its first step
 
     @staticmethod
     def of(model, key, img, cond, has_mask, zpo):
@@ -147,6 +172,17 @@ class Entry:
         if mask is not None:
             self.gt.copy_(gt)
             self.mask.copy_(mask)
+
+    def warm_up_plms(self, model, ptable, rows, tmap=None):
+        """``warm_up`` of a PLMS entry: the forward and the three step kernels, on copies of x / ts and a state of their own."""
+        model(self.x, self.ts, out=self.x0, **self.kwargs, batch_rows=rows)
+        t0 = min(2, ptable.shape[0] - 1)
+        x, ts, state = self.x.clone(), self.ts.clone(), diffusion.seeded_state(t0, 1, 0).to(self.x.device)
+        plms_first_half(x, self.x0, self.gt, self.mask, self.ring, self.x_mid, ptable, state, ts, tmap)
+        plms_second_half(x, self.x0, self.gt, self.mask, self.ring, self.x_mid, ptable, state)
+        state.copy_(diffusion.seeded_state(t0, 1, 0))
+        plms_step(x, self.x0, self.gt, self.mask, self.ring, 2, ptable, state, ts, tmap)
+        torch.cuda.synchronize(self.x.device)
 
     def warm_up(self, model, table, rows, tmap=None):
         """First launches of everything a plain step can consist of, outside a capture (where a launch error cannot be reported): the
@@ -177,7 +213,7 @@ class Entry:
         hk = self.hooks.get(hook._uid)
         if hk is None or hk.shapes != shapes:
             hk = self.hooks[hook._uid] = HookBuffers(hook, self, y, shapes)
-            for stale in [gk for gk in self.graphs if isinstance(gk, tuple) and gk[0] == 'hook' and gk[1] == hook._uid]:
+            for stale in [gk for gk in self.graphs if isinstance(gk, tuple) and gk[0] in ('hook', 'first') and gk[1] == hook._uid]:
                 del self.graphs[stale]
         for k in HOOK_KEYS + (() if self.gt is not None else ('inpainted_motion',)):
             hk.y[k].copy_(y[k])
@@ -281,6 +317,9 @@ class Run:
             diffusion.inpaint(st.x0, st.gt, st.mask)
         self.finish_hook_step(self.hook(st.x0, t, model_kwargs).contiguous())
 
+    def first_step(self, t, ts_all, model_kwargs):
+        raise NotImplementedError('only a PLMS plan has a first step')
+
     def play(self, plan, t_start, ts_all, model_kwargs):
         """One replay or eager hook step per op; the dumps.  ``ts_all``: the LOOP-side timesteps, what an eager hook is handed."""
         st, dump, i = self.entry, [], t_start
@@ -291,6 +330,9 @@ class Run:
             elif op[0] == 'hook':
                 self.hook_block(op[1]).replay()
                 i -= op[1] + 1
+            elif op[0] == 'first':
+                self.first_step(i, ts_all, model_kwargs)
+                i -= 1
             elif op[0] == 'eager_hook':
                 t = ts_all[i]
                 t.host_value = i
@@ -299,6 +341,66 @@ class Run:
             else:
                 dump.append(st.x.clone())
         return dump
+
+
+class PlmsRun(Run):
+    """One PLMS sample on ``entry``: every step is the two-call form [forward -> inpaint -> hook -> PLMS update] on one chain (the update needs
+    the eps ring, which the fused tail of the denoiser does not carry), so ``Run``'s blocks serve with the update swapped; the first step --
+    two denoiser calls around the two halves of its update -- is an op of its own."""
+
+    def __init__(self, model, entry, table, ptable, order, rows, hook, hk, tmap=None):
+        super().__init__(model, entry, table, rows, False, False, hook, hk, tmap)
+        self.ptable, self.order = ptable, order
+
+    def enqueue_plain(self, k):
+        st = self.entry
+        for _ in range(k):
+            self.enqueue_forward()
+            plms_step(st.x, st.x0, st.gt, st.mask, st.ring, self.order, self.ptable, st.state, st.ts, self.tmap)
+
+    def finish_hook_step(self, x0):
+        st = self.entry
+        plms_step(st.x, x0, None, None, st.ring, self.order, self.ptable, st.state, st.ts, self.tmap)
+
+    def enqueue_forward_mid(self):
+        st = self.entry
+        self.model(st.x_mid, st.ts, out=st.x0, **st.kwargs, batch_rows=self.rows)
+
+    def enqueue_first(self, hooked):
+        """The first step with the captured hook in the calls ``hooked`` = (at t, at t - 1) says: the second call finds ``state[0]`` == t - 1,
+        which is where ``apply_dev`` reads its blend weight."""
+        st = self.entry
+        for half, with_hook in enumerate(hooked):
+            self.enqueue_forward() if half == 0 else self.enqueue_forward_mid()
+            if st.mask is not None:
+                diffusion.inpaint(st.x0, st.gt, st.mask)
+            if with_hook:
+                self.hook.apply_dev(st.x0, self.table, st.state, self.hk.y, self.hk.ws)
+            if half == 0:
+                plms_first_half(st.x, st.x0, None, None, st.ring, st.x_mid, self.ptable, st.state, st.ts, self.tmap)
+            else:
+                plms_second_half(st.x, st.x0, None, None, st.ring, st.x_mid, self.ptable, st.state)
+
+    def first_step(self, t, ts_all, model_kwargs):
+        """Captured when no call of it takes an eager hook; else the two forwards are replayed and the rest runs eagerly."""
+        st, gate = self.entry, hook_gate(self.hook)
+        hooked = (bool(gate(t)), bool(gate(t - 1)))
+        if self.hk is not None or not any(hooked):
+            self.graph(('first', self.hook._uid if any(hooked) else None) + hooked, self.enqueue_first, hooked).replay()        # (a first step without a hook call serves any hook)
+            return
+        for half, (ti, with_hook) in enumerate(zip((t, t - 1), hooked)):
+            self.graph('fwd' if half == 0 else 'fwd_mid', self.enqueue_forward if half == 0 else self.enqueue_forward_mid).replay()
+            if st.mask is not None:
+                diffusion.inpaint(st.x0, st.gt, st.mask)
+            x0 = st.x0
+            if with_hook:
+                th = ts_all[ti]
+                th.host_value = ti
+                x0 = self.hook(st.x0, th, model_kwargs).contiguous()
+            if half == 0:
+                plms_first_half(st.x, x0, None, None, st.ring, st.x_mid, self.ptable, st.state, st.ts, self.tmap)
+            else:
+                plms_second_half(st.x, x0, None, None, st.ring, st.x_mid, self.ptable, st.state)
 
 
 def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start, shard=None, sampler=('ddpm',)):
@@ -313,7 +415,8 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
     per_clip = img.numel() // B
     elem0 = first * per_clip                    # position of this batch's x[0] inside the whole (possibly sharded) batch: the Philox counter base (p_sample_loop checked it)
     rows = total * T                            # the WHOLE batch's token rows: what every launch's feed-forward tile is picked by (MDM._pick_ffn_tile)
-    table, tmap = diff._table(dev, sampler), diff._tmap(dev)
+    plms = sampler[0] == 'plms'                 # ('plms', order): the hook still reads its blend weight from a {c1, c2, sigma, t/1000} table
+    table, tmap = diff._table(dev, ('ddpm',) if plms else sampler), diff._tmap(dev)
     mask, gt = diffusion.mask_operands(y.get('inpainting_mask'), y.get('inpainted_motion'), img)
     cond, zpo = y['cond'], model_kwargs.get('zero_pose_obj')
     key = (diff._uid, tuple(img.shape), mask is not None, tuple(cond.shape), model.ffn_graph_key(rows)) + (() if sampler == ('ddpm',) and tmap is None else (sampler, tmap is not None))    # the captured launches bake the feed-forward kernel choice in
@@ -323,11 +426,13 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
     st.load(cond, zpo, gt, mask)
     pools_before = model.shape_buffer_keys() if fresh else None      # (taken before the first fold of this shape allocates its memory context)
     model.prepare_memory(st.cond)                   # once per sample, on the current stream (inside the caller's clock)
+    if plms and st.ring is None:
+        st.ring, st.x_mid = torch.empty(3, img.numel(), dtype=torch.float32, device=dev), torch.empty_like(img)
     if fresh:
-        st.warm_up(model, table, rows, tmap)
+        st.warm_up_plms(model, diff._plms_table(dev), rows, tmap) if plms else st.warm_up(model, table, rows, tmap)
         st.pool_keys = model.shape_buffer_keys() - pools_before      # what this entry made the denoiser allocate: released with the entry
 
-    fused = diff.fuse_plain_step and model.supports_forward_step
+    fused = diff.fuse_plain_step and model.supports_forward_step and not plms
     # Chains: at <= 16 clips every kernel of a step is one partial wave of workgroups bounded by latency (operand round trips,
     # kernel boundaries), so the two halves of the batch, stepped as independent kernel chains on two branches of the SAME captured
     # graph, overlap each other's dead time.  Clips never interact in a plain step, the noise of a chain is drawn at the whole
@@ -349,7 +454,11 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
         st.graphs.clear()
         st.chain_steps = chain_steps
     fuse_hook = hook_capturable(hook, y)
-    run = Run(model, st, table, rows, fused, split, hook, st.hook_buffers(hook, y, table) if fuse_hook else None, tmap)
+    hk = st.hook_buffers(hook, y, table) if fuse_hook else None
+    if plms:
+        run = PlmsRun(model, st, table, diff._plms_table(dev), sampler[1], rows, hook, hk, tmap)
+    else:
+        run = Run(model, st, table, rows, fused, split, hook, hk, tmap)
 
     st.x.copy_(img)
     st.state.copy_(diffusion.seeded_state(t_start, seed, elem0))
@@ -357,5 +466,10 @@ def sample(diff, model, img, model_kwargs, hook, seed, todo, dump_steps, t_start
         for ch in st.chains[1:]:                    # (an odd offset when T % 4 != 0: the per-row form of the fused update takes any)
             ch.state.copy_(diffusion.seeded_state(t_start, seed, elem0 + ch.sl.start * per_clip))
     st.ts.fill_(diff.timestep_map[t_start])
-    dump = run.play(plan_steps(t_start, todo, hook_gate(hook), dump_steps, fuse_hook), t_start, diff._timesteps(B, dev, loop_side=True), model_kwargs)
+    if plms:                                        # the first step is loop step 0: the plan of the rest starts at loop index 1
+        plan = [('first',)] + ([('dump', 0)] if dump_steps is not None and 0 in dump_steps else [])
+        plan += plan_steps(t_start - 1, todo - 1, hook_gate(hook), dump_steps, fuse_hook, it0=1)
+    else:
+        plan = plan_steps(t_start, todo, hook_gate(hook), dump_steps, fuse_hook)
+    dump = run.play(plan, t_start, diff._timesteps(B, dev, loop_side=True), model_kwargs)
     return dump if dump_steps is not None else st.x.clone()
